@@ -14,7 +14,8 @@ ships with the reference.
 A step = one upscale() of the rank's 16 images plus, when N > 1, the gather of all output images on rank 0
 (the only collective of the path).  Inputs and weights are resident in HBM before the timed region.
 
-Rank 0 prints ONE JSON line.  Besides the driver's contract it carries
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the steps and prints it (`--dump-outputs DIR` also writes
+what the last timed step returned, see dump_outputs()).  With `--full` the line also carries
   roofline     : live HIP-event timing of the dominant kernel family (the 3x3 implicit-GEMM convolution):
                  algorithmic FLOPs of all its launches in one step / their summed device time, against the
                  dense bf16 MFMA peak of 2.5 PFLOP/s (`frac`) AND against what this very device sustains on a bare,
@@ -24,6 +25,8 @@ Rank 0 prints ONE JSON line.  Besides the driver's contract it carries
   cpu_baseline : the CPU oracle (oracle/mewzoom_oracle.py, torch CPU fp32 on all host cores): `value` is timed on a
                  bounded sample of the SAME model as the GPU workload (with the GPU-vs-oracle PSNR / max-abs on that
                  sample), `cfg1` is BASELINE.md section 3's procedure (2X-48 model, 1x3x256x256, median of >= 5).
+  secondary    : short runs of the other BASELINE readings (N = 1, default workload; see secondary_readings()).
+  value_without_gather : N > 1, the same steps again without the gather of outputs.
 """
 
 from __future__ import annotations
@@ -36,8 +39,10 @@ import statistics
 import subprocess
 import sys
 import time
+from concurrent.futures import ThreadPoolExecutor
 from pathlib import Path
 
+import numpy as np
 import torch
 import torch.distributed as dist
 
@@ -69,6 +74,14 @@ PEAK_TFLOPS = {"bf16": 2500.0, "f16": 2500.0, "f32": 157.3}  # dense MFMA, MI355
 def parameter_shapes(cfg):
     m = MewZoom(**cfg)
     return {k: tuple(v.shape) for k, v in m.state_dict().items()}
+
+
+def synth_weights(shapes, seed):
+    """synth_state_dict() with one thread per tensor: every value depends only on (name, seed, index), so the result is the
+    same, and the 434 M parameters of the headline model take ~2 s instead of ~10."""
+    with ThreadPoolExecutor(min(8, host_cores())) as ex:
+        parts = ex.map(lambda item: synth_state_dict(dict([item]), seed=seed), shapes.items())
+    return {k: v for part in parts for k, v in part.items()}
 
 
 def host_cores() -> int:
@@ -224,14 +237,36 @@ def self_launch(n: int) -> int:
 
 
 def timed_steps(step, sync, steps, warmup):
+    """Seconds taken by `steps` calls of step() after `warmup` untimed ones, and what the last call returned."""
     for _ in range(warmup):
         step()
     sync()
     t0 = time.perf_counter()
-    for _ in range(steps):
+    for _ in range(steps - 1):
         step()
+    out = step()
     sync()
-    return time.perf_counter() - t0
+    return time.perf_counter() - t0, out
+
+
+DUMP_VALUES = 1 << 23  # per output: 32 MB of float32
+
+
+def dump_outputs(out_dir, outputs):
+    """Writes each output tensor as <out_dir>/<name>.npy in float32.  One of more than DUMP_VALUES elements is written as a fixed
+    sample instead: the flattened tensor cut into DUMP_VALUES equal slices, one position per slice drawn with a fixed seed, so that
+    the positions depend only on the tensor's size and two builds can be compared value for value."""
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    for name, t in outputs.items():
+        flat = t.reshape(-1)
+        if flat.numel() > DUMP_VALUES:
+            stride = flat.numel() // DUMP_VALUES
+            pos = np.arange(DUMP_VALUES, dtype=np.int64) * stride + np.random.default_rng(0).integers(0, stride, DUMP_VALUES)
+            vals = flat[torch.from_numpy(pos).to(flat.device)]
+        else:
+            vals = t
+        np.save(out_dir / f"{name}.npy", vals.float().cpu().numpy())
 
 
 def secondary_readings(device, want_sample, sample_hw):
@@ -246,7 +281,7 @@ def secondary_readings(device, want_sample, sample_hw):
         cfg = MODELS[model_name]
         dtype = DTYPES[dtype_name]
         if model_name not in sds:
-            sds[model_name] = synth_state_dict(parameter_shapes(cfg), seed=1234)
+            sds[model_name] = synth_weights(parameter_shapes(cfg), seed=1234)
         m = MewZoom(**cfg)
         m.load_state_dict(sds[model_name])
         m = m.to(device, dtype).eval()
@@ -257,7 +292,7 @@ def secondary_readings(device, want_sample, sample_hw):
             desc = desc + ", uint8 images in and out (upscale_uint8)"
         else:
             fwd = m.upscale
-        el = timed_steps(lambda: fwd(x), lambda: torch.cuda.synchronize(device), steps, warmup)
+        el = timed_steps(lambda: fwd(x), lambda: torch.cuda.synchronize(device), steps, warmup)[0]
         r = cfg["upscale_ratio"]
         h = m._engine.handle
         h.profile_enable(True)
@@ -299,14 +334,23 @@ def main():
     ap.add_argument("--workload", default="cfg3_1080p", choices=list(WORKLOADS))
     ap.add_argument("--dtype", default="bf16", choices=list(DTYPES))
     ap.add_argument("--images-in-flight", type=int, default=0, help="micro-batch inside the library (0 = default)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-microbench", action="store_true", help="skip the on-box MFMA peak micro-benchmark (profiling runs)")
-    ap.add_argument("--dump-launches", default="", help="write a per-launch CSV (shape, ms, TFLOP/s) of the profiled step")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the last timed step returned to DIR/<name>.npy (float32; a fixed sample of a large output)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the roofline step, the on-box MFMA peak, the CPU baseline, the secondary readings (N = 1) "
+                         "and the compute-only rate (N > 1)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-microbench", action="store_true", help="with --full: skip the on-box MFMA peak micro-benchmark (profiling runs)")
+    ap.add_argument("--dump-launches", default="", help="with --full: write a per-launch CSV (shape, ms, TFLOP/s) of the profiled step")
     ap.add_argument("--no-gather", action="store_true", help="skip the output gather in the timed step (N > 1)")
     ap.add_argument("--images-per-gpu", type=int, default=0, help="override the workload's batch (profiling runs only)")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the short cfg2 / fp16 / fp32 side readings (N = 1)")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the short cfg2 / fp16 / fp32 side readings (N = 1)")
     ap.add_argument("--dry-run", action="store_true", help="rendezvous, barrier and JSON line only: no GPU work (launcher tests)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_launches and not args.full:
+        ap.error("--dump-launches needs --full (it writes the profiled step)")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(self_launch(args.gpus))
@@ -320,7 +364,8 @@ def main():
         args.gpus = world
     # the on-box MFMA peak: a child process, started BEFORE this process initialises HIP (rank 0, single-GPU runs; never in a dry run,
     # which promises no GPU work at all)
-    mfma_peak = measured_mfma_peak() if (rank == 0 and world == 1 and not args.no_microbench and not args.dry_run) else None
+    mfma_peak = (measured_mfma_peak() if (args.full and rank == 0 and world == 1 and not args.no_microbench and not args.dry_run)
+                 else None)
     # one rank per GPU; MZ_BENCH_BACKEND=gloo lets several ranks share one GPU for plumbing rehearsals on a 1-GPU box
     backend = os.environ.get("MZ_BENCH_BACKEND", "nccl")
     if args.dry_run:  # the launcher's plumbing without a GPU: rendezvous over gloo, one all-reduce, rank 0's line
@@ -355,8 +400,8 @@ def main():
     dtype = DTYPES[args.dtype]
     r = cfg["upscale_ratio"]
 
-    sd = synth_state_dict(parameter_shapes(cfg), seed=1234)
     model = MewZoom(**cfg)
+    sd = synth_weights({k: tuple(v.shape) for k, v in model.state_dict().items()}, seed=1234)
     model.load_state_dict(sd)
     model = model.to(device, dtype).eval()
     model.max_images_in_flight = args.images_in_flight
@@ -388,11 +433,15 @@ def main():
             return t.item()
         return sec
 
-    elapsed = max_over_ranks(timed_steps(step, sync, args.steps, args.warmup))
+    elapsed, last = timed_steps(step, sync, args.steps, args.warmup)
+    elapsed = max_over_ranks(elapsed)
+    if args.dump_outputs and rank == 0:  # N > 1: the whole global batch with the gather, rank 0's images without it
+        dump_outputs(args.dump_outputs, {"upscale": last})
+    del last
     # N > 1: the compute-only rate as well (the same steps without the gather), reported next to the headline value
     elapsed_no_gather = None
-    if do_gather:
-        elapsed_no_gather = max_over_ranks(timed_steps(lambda: model.upscale(x), sync, args.steps, 1))
+    if do_gather and args.full:
+        elapsed_no_gather = max_over_ranks(timed_steps(lambda: model.upscale(x), sync, args.steps, 1)[0])
 
     out_mpix_per_step = global_batch * (H * r) * (W * r) / 1e6
     value = out_mpix_per_step * args.steps / elapsed
@@ -401,19 +450,6 @@ def main():
     if rank == 0:
         engine = model._engine
         flops_step = engine.handle.flops_per_image(H, W) * per_gpu  # this rank
-        # ---- roofline leg: one extra, separately profiled step ----
-        engine.handle.profile_enable(True)
-        model.upscale(x)
-        torch.cuda.synchronize(device)
-        if args.dump_launches:
-            engine.handle.profile_dump(args.dump_launches)
-        prof = engine.handle.profile_read()
-        engine.handle.profile_enable(False)
-        conv_tflops = prof["conv_flops"] / (prof["conv_ms"] * 1e-3) / 1e12 if prof["conv_ms"] > 0 else 0.0
-        peak = PEAK_TFLOPS[args.dtype]
-        pmc, pmc_note = traffic_from_profile(args)
-        alg_bytes_per_launch = prof["conv_bytes"] / max(1.0, prof["conv_launches"])
-        measured_peak = mfma_peak["measured_peak_tflops"] if (mfma_peak and args.dtype != "f32") else None
         result = {
             "metric": f"upscaled MPix/sec, MewZoom-4X 1080p {args.dtype} batched inference" if args.workload.startswith("cfg3")
             else "upscaled MPix/sec",
@@ -438,31 +474,45 @@ def main():
             },
             "whole_path_tflops_per_gpu": flops_step * args.steps / elapsed / 1e12,
             "value_without_gather": out_mpix_per_step * args.steps / elapsed_no_gather if elapsed_no_gather else None,
-            "roofline": {
-                "bound": "mfma",
-                "kernel": "3x3 implicit-GEMM convolution kernels (all 3x3 launches of one step, rank 0)",
-                "achieved": conv_tflops,
-                "peak": peak,
-                "unit": "TFLOP/s",
-                "frac": conv_tflops / peak,
-                "measured_peak": measured_peak,
-                "frac_of_measured_peak": conv_tflops / measured_peak if measured_peak else None,
-                "measured_peak_detail": mfma_peak,
-                # HBM-side bytes per launch (FETCH_SIZE x 2 + WRITE_SIZE, rocprofv3 PMC passes) next to the algorithmic
-                # bytes per launch (each conv reads its input once and writes its output once, weights once)
-                "traffic": pmc["traffic_bytes_per_launch"] if pmc else None,
-                "traffic_note": pmc_note or f"{TRAFFIC_PROFILE.name}: {pmc['launches']} launches of one {pmc.get('images', 3)}-image "
-                                            "micro-batch forward, same kernel sources (sha256 match)",
-                "algorithmic_bytes_per_launch": alg_bytes_per_launch,
-                "traffic_over_algorithmic": pmc["traffic_bytes_per_launch"] / alg_bytes_per_launch if pmc and alg_bytes_per_launch else None,
-                "traffic_bytes_per_step": pmc["traffic_bytes_per_launch"] * prof["conv_launches"] if pmc else None,
-                "launches": prof["conv_launches"],
-                "avg_launch_ms": prof["conv_ms"] / max(1.0, prof["conv_launches"]),
-                "algorithmic_tflop_per_step": prof["conv_flops"] / 1e12,
-                "conv_ms_per_step": prof["conv_ms"],
-                "other_kernels_ms_per_step": prof["other_ms"],
-                "algorithmic_GBps": prof["conv_bytes"] / (prof["conv_ms"] * 1e-3) / 1e9 if prof["conv_ms"] > 0 else 0.0,
-            },
+        }
+    if rank == 0 and args.full:
+        # ---- roofline leg: one extra, separately profiled step ----
+        engine.handle.profile_enable(True)
+        model.upscale(x)
+        torch.cuda.synchronize(device)
+        if args.dump_launches:
+            engine.handle.profile_dump(args.dump_launches)
+        prof = engine.handle.profile_read()
+        engine.handle.profile_enable(False)
+        conv_tflops = prof["conv_flops"] / (prof["conv_ms"] * 1e-3) / 1e12 if prof["conv_ms"] > 0 else 0.0
+        peak = PEAK_TFLOPS[args.dtype]
+        pmc, pmc_note = traffic_from_profile(args)
+        alg_bytes_per_launch = prof["conv_bytes"] / max(1.0, prof["conv_launches"])
+        measured_peak = mfma_peak["measured_peak_tflops"] if (mfma_peak and args.dtype != "f32") else None
+        result["roofline"] = {
+            "bound": "mfma",
+            "kernel": "3x3 implicit-GEMM convolution kernels (all 3x3 launches of one step, rank 0)",
+            "achieved": conv_tflops,
+            "peak": peak,
+            "unit": "TFLOP/s",
+            "frac": conv_tflops / peak,
+            "measured_peak": measured_peak,
+            "frac_of_measured_peak": conv_tflops / measured_peak if measured_peak else None,
+            "measured_peak_detail": mfma_peak,
+            # HBM-side bytes per launch (FETCH_SIZE x 2 + WRITE_SIZE, rocprofv3 PMC passes) next to the algorithmic
+            # bytes per launch (each conv reads its input once and writes its output once, weights once)
+            "traffic": pmc["traffic_bytes_per_launch"] if pmc else None,
+            "traffic_note": pmc_note or f"{TRAFFIC_PROFILE.name}: {pmc['launches']} launches of one {pmc.get('images', 3)}-image "
+                                        "micro-batch forward, same kernel sources (sha256 match)",
+            "algorithmic_bytes_per_launch": alg_bytes_per_launch,
+            "traffic_over_algorithmic": pmc["traffic_bytes_per_launch"] / alg_bytes_per_launch if pmc and alg_bytes_per_launch else None,
+            "traffic_bytes_per_step": pmc["traffic_bytes_per_launch"] * prof["conv_launches"] if pmc else None,
+            "launches": prof["conv_launches"],
+            "avg_launch_ms": prof["conv_ms"] / max(1.0, prof["conv_launches"]),
+            "algorithmic_tflop_per_step": prof["conv_flops"] / 1e12,
+            "conv_ms_per_step": prof["conv_ms"],
+            "other_kernels_ms_per_step": prof["other_ms"],
+            "algorithmic_GBps": prof["conv_bytes"] / (prof["conv_ms"] * 1e-3) / 1e9 if prof["conv_ms"] > 0 else 0.0,
         }
         want_sample = None
         sample = (384, 640) if model_name == "4x96" else (540, 960)  # ~10-20 s of CPU work in total
@@ -472,6 +522,7 @@ def main():
             del x
             torch.cuda.empty_cache()
             result["secondary"] = secondary_readings(device, want_sample, sample)
+    if rank == 0:
         print(json.dumps(result), flush=True)
     if world > 1:
         dist.barrier()
