@@ -177,6 +177,14 @@ const char* mz_debug_last_kernel(void);
  * number of tiles listed (== B * tiles_y * tiles_x * ntiles), negative on bad arguments.  No reference counterpart. */
 int mz_debug_tile_list(int B, int tiles_y, int tiles_x, int ntiles, int gm, int gn, int blk4, int th, int tw, unsigned int* out, int cap);
 
+/* Host-only (no GPU): the kernel family (a name as mz_debug_last_kernel() reports it) that a launch of one layer would run on a device
+ * with `cus` compute units, under the MZ_* knobs of the environment.  op: 0 conv1 + SiLU, 1 plain conv3x3,
+ * 2 conv3x3 + PixelShuffle(2) into 2H x 2W (cout = 4 x the shuffled channels), 3 image head (cout = 12), 4 quality-head conv,
+ * 5 FiLM conv (mz_op_conv_film), 6 a block's conv2 (cin = the hidden channels) as mz_forward runs it: fused with the mix, or alone,
+ * 7 the unfused AdaptiveResidualMix (cin = 2 cout).  Returns NULL where the launch would be refused (mz_last_error() says why).
+ * No reference counterpart. */
+const char* mz_debug_select(int dtype, int op, int cin, int cout, int B, int H, int W, int cus);
+
 /* Hardware probe (ultrazoom_amd/csrc/mz_probe.hip; tests/test_store_hazard_gpu.py): on every CU, 16-byte buffer stores each followed --
  * `wait_states` (0, 1, 2) wait states later -- by a vector instruction that overwrites data register `dword` (0..3) of the store:
  * follower 0 v_mov_b32, 1 v_mul_f32, 2 v_cvt_pk_bf16_f32, 3 v_exp_f32, 4 v_pk_mul_f32, 5 v_mfma_f32_16x16x32_bf16;

@@ -62,36 +62,28 @@ static int ensure_device_ready() {
 // Environment knobs (A/B timing and test coverage of every kernel variant).  Read ONCE, when a
 // handle is created (or per mz_op_* call), never on the launch path.
 struct Knobs {
-    int use_glds = 1;       // MZ_USE_GLDS=0: stage through registers instead of LDS-DMA (needs a -DMZ_REG_STAGING build)
     bool wide = true;       // MZ_NO_WIDE=1: force the 256-pixel kernel
     bool fuse = true;       // MZ_NO_FUSE=1: conv2 and the mix as two launches
     bool s16 = true;        // MZ_NO_S16=1: keep 16-bit types on the 32x32x16 kernels
     bool fuse16 = true;     // MZ_NO_FUSE16=1: the fused mix stays on the 32x32x16 kernel
-    bool mix16 = true;      // MZ_NO_MIX16=1: C = k * 192 mixes on the general 1x1 kernel
-    bool mix16b = true;     // MZ_NO_MIX16B=1: ... on mix16_kernel (blend in accumulator layout, x and z read twice) instead of mix16b_kernel
+    bool mix16b = true;     // MZ_NO_MIX16B=1: C = 192 mixes on mix16_kernel (blend in accumulator layout, x and z read twice) instead of mix16b_kernel
     int persist = -1;       // MZ_NO_PERSIST=1 -> 0 (one workgroup per tile); MZ_PERSIST_WGS=n -> n; -1 = one per CU
     int kpad_pct = 12;      // MZ_KPAD_PCT=n: the 16x16x32 kernels take Cin whose padding to whole 32-channel chunks is <= n %
     int blk4 = 1;           // MZ_NO_BLK4=1: row-major tile walk inside an image (A/B of the L2 sharing of vertical halos)
     int r = 1;              // MZ_NO_R=1: never use conv3r_kernel (96-channel N tiles, 8 x 48 / 8 x 40 pixel tiles, role-alternating waves: epilogues under the next K loop)
-    int geo40 = 1;          // MZ_NO_GEO40=1: conv3r_kernel keeps its 8 x 48 tiles where 8 x 40 tiles would pad fewer pixels
     int r2 = 1;             // MZ_NO_R2=1: Cin = 48 -> 96-channel N tiles (conv1 of the 48-channel models' level-1 block) stays off conv3r_kernel's ragged variant
-    int head256 = 1;        // MZ_NO_HEAD256=1: the image head (EPI_FINAL) stays on the 512-pixel per-tile kernel instead of the 256-pixel one
     int t = 1;              // MZ_NO_T=1: never use conv3t_kernel (the same structure for ONE N tile of <= 48 channels, 12 x 64 tiles)
 };
 static Knobs read_knobs() {
     Knobs k;
-    if (const char* e = getenv("MZ_USE_GLDS")) k.use_glds = atoi(e) != 0;
     k.wide = getenv("MZ_NO_WIDE") == nullptr;
     k.fuse = getenv("MZ_NO_FUSE") == nullptr;
     k.s16 = getenv("MZ_NO_S16") == nullptr;
     k.fuse16 = getenv("MZ_NO_FUSE16") == nullptr;
-    k.mix16 = getenv("MZ_NO_MIX16") == nullptr;
     k.mix16b = getenv("MZ_NO_MIX16B") == nullptr;
     k.r = getenv("MZ_NO_R") == nullptr;
     k.t = getenv("MZ_NO_T") == nullptr;
-    k.head256 = getenv("MZ_NO_HEAD256") == nullptr;
     k.r2 = getenv("MZ_NO_R2") == nullptr;
-    k.geo40 = getenv("MZ_NO_GEO40") == nullptr;
     k.blk4 = getenv("MZ_NO_BLK4") == nullptr;
     if (const char* e = getenv("MZ_KPAD_PCT")) k.kpad_pct = atoi(e);
     if (getenv("MZ_NO_PERSIST") != nullptr) k.persist = 0;
@@ -244,28 +236,36 @@ static void add_slot(mz_handle* h, const std::string& name, int kind, std::initi
     h->slots.push_back(s);
 }
 
+// The gate weights of a block's mix once more, packed for the fused conv2 + mix epilogue (SRC_MIXF) in conv2's N tile
+static void plan_mixf(ConvW& f, int dtype, const ConvW& conv2) {
+    const int c = conv2.cout;
+    f.cout = c; f.cin = 2 * c; f.kh = f.kw = 1;
+    f.mode = MODE_GEMM1; f.taps = 1;
+    f.nt = conv2.nt; f.ntiles = 1;
+    f.out_map = OUT_PLAIN; f.in_map = SRC_MIXF;
+    f.c0 = c; f.cp0 = pad16(c); f.c1 = c;
+    const int zg = dtype == DT_F32 ? 4 : 2;
+    f.nchunks = f.nchunks_real = f.cp0 / chunk_channels(dtype) + f.nt * zg;
+    f.packed_sz = packed_bytes(1, f.nt, 1, f.nchunks);
+    if (dtype != DT_F32) {  // second packing for the fused epilogue of the 16x16x32 kernel: 2 nt K-steps x 2 nt fragments
+        f.nchunks16 = (f.cp0 + 31) / 32 + f.nt;
+        f.packed16_sz = packed_bytes(1, 2 * f.nt, 1, f.nchunks16);
+        if (f.cp0 == 48) f.packed16t_sz = packed_bytes(1, 3, 1, 3);  // conv3t_kernel's gate: three K steps x three fragments
+    }
+}
+
+// EncoderBlock / DecoderBlock of c channels with `hidden` channels between its two convolutions
+static void plan_block(BlockW& b, int dtype, int c, int hidden) {
+    plan_conv(b.conv1, dtype, MODE_CONV3, hidden, c, 3, 3, OUT_PLAIN, SRC_PLAIN, 0, 0);      // model.py:742-744
+    plan_conv(b.conv2, dtype, MODE_CONV3, c, hidden, 3, 3, OUT_PLAIN, SRC_PLAIN, 0, 0);      // model.py:746-748
+    plan_conv(b.mix, dtype, MODE_GEMM1, c, 2 * c, 1, 1, OUT_PLAIN, SRC_CONCAT, c, c);        // model.py:805
+    b.fused = b.conv2.ntiles == 1 && b.conv2.nt <= 3;
+    if (b.fused) plan_mixf(b.mixf, dtype, b.conv2);
+}
+
 static void add_block(mz_handle* h, BlockW* b, const std::string& prefix, int c) {
     const int hr = h->cfg.hidden_ratio;
-    plan_conv(b->conv1, h->dtype, MODE_CONV3, hr * c, c, 3, 3, OUT_PLAIN, SRC_PLAIN, 0, 0);      // model.py:742-744
-    plan_conv(b->conv2, h->dtype, MODE_CONV3, c, hr * c, 3, 3, OUT_PLAIN, SRC_PLAIN, 0, 0);      // model.py:746-748
-    plan_conv(b->mix, h->dtype, MODE_GEMM1, c, 2 * c, 1, 1, OUT_PLAIN, SRC_CONCAT, c, c);        // model.py:805
-    b->fused = b->conv2.ntiles == 1 && b->conv2.nt <= 3;
-    if (b->fused) {
-        ConvW& f = b->mixf;
-        f.cout = c; f.cin = 2 * c; f.kh = f.kw = 1;
-        f.mode = MODE_GEMM1; f.taps = 1;
-        f.nt = b->conv2.nt; f.ntiles = 1;
-        f.out_map = OUT_PLAIN; f.in_map = SRC_MIXF;
-        f.c0 = c; f.cp0 = pad16(c); f.c1 = c;
-        const int zg = h->dtype == DT_F32 ? 4 : 2;
-        f.nchunks = f.nchunks_real = f.cp0 / chunk_channels(h->dtype) + f.nt * zg;
-        f.packed_sz = packed_bytes(1, f.nt, 1, f.nchunks);
-        if (h->dtype != DT_F32) {  // second packing for the fused epilogue of the 16x16x32 kernel: 2 nt K-steps x 2 nt fragments
-            f.nchunks16 = (f.cp0 + 31) / 32 + f.nt;
-            f.packed16_sz = packed_bytes(1, 2 * f.nt, 1, f.nchunks16);
-            if (f.cp0 == 48) f.packed16t_sz = packed_bytes(1, 3, 1, 3);  // conv3t_kernel's gate: three K steps x three fragments
-        }
-    }
+    plan_block(*b, h->dtype, c, hr * c);
     add_slot(h, prefix + ".convnet.conv1.weight", SK_CONV, {hr * c, c, 3, 3});
     h->slots.back().conv = &b->conv1;
     add_slot(h, prefix + ".convnet.conv2.weight", SK_CONV, {c, hr * c, 3, 3});
@@ -612,11 +612,8 @@ extern "C" int mz_debug_read(unsigned long long* host_dst) {
     return hipMemcpy(host_dst, b, 16 * 64 * 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost) == hipSuccess ? 0 : -6;
 }
 
-// workgroups of a persistent launch: one per CU of the CURRENT device, a multiple of 8 (one equal share per XCD).
-// Knobs::persist overrides: 0 = one workgroup per tile everywhere (A/B timing); n = force n (tests use 8 / 16 so that
-// small images walk several tiles per workgroup).
-static int persistent_workgroups(const Knobs& k) {
-    if (k.persist >= 0) return k.persist;
+// CUs of the CURRENT device, a multiple of 8 (one equal share per XCD); 0 if unknown
+static int current_cus() {
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDevices) return 0;
     return g_dev_cus[dev];
@@ -654,32 +651,234 @@ static void tile_list(const ConvArgs& a, int th, int tw, std::vector<uint32_t>& 
     }
 }
 
+// Tile groups of gm pixel tiles x gn N tiles (gm * gn ~ the workgroups resident on one XCD): inside a group both operands are shared
+// through the XCD's L2; per group the activations are re-read ntiles/gn times and the weights mtiles/gm times in total.  Picks the shape
+// with the least total re-read traffic and sets the walk of a (a.mtiles, a.ntiles, a.tiles_x, a.tiles_y set): a.grid and its divisors.
+static void pick_order(ConvArgs& a, const ConvW& c, double act_bytes, const Knobs& k, int resident_per_xcd = 32) {
+    const double W = (double)c.packed_sz, A = act_bytes;
+    int best_gm = a.mtiles, best_gn = 1;
+    double best = 1e300;
+    for (int gn = 1; gn <= a.ntiles; ++gn) {
+        if (gn > resident_per_xcd) break;
+        if (a.ntiles % gn != 0 && gn != a.ntiles) continue;
+        int gm = resident_per_xcd / gn;
+        if (gm < 1) gm = 1;
+        if (gm > a.mtiles) gm = a.mtiles;
+        const double groups_n = std::ceil((double)a.ntiles / gn), groups_m = std::ceil((double)a.mtiles / gm);
+        const double traffic = A * groups_n + W * groups_m;
+        if (traffic < best) { best = traffic; best_gm = gm; best_gn = gn; }
+    }
+    a.gm = best_gm; a.gn = best_gn;
+    const long long groups = (long long)((a.mtiles + a.gm - 1) / a.gm) * ((a.ntiles + a.gn - 1) / a.gn);
+    a.grid = (int)(groups * a.gm * a.gn);
+    a.groups_m = (a.mtiles + a.gm - 1) / a.gm;
+    a.inv_gsz = 1.0f / (float)(a.gm * a.gn);
+    a.inv_groups_m = 1.0f / (float)a.groups_m;
+    a.inv_gn = 1.0f / (float)a.gn;
+    a.inv_tpi = a.tiles_x > 0 ? 1.0f / (float)(a.tiles_x * a.tiles_y) : 1.0f;
+    a.inv_tiles_x = a.tiles_x > 0 ? 1.0f / (float)a.tiles_x : 1.0f;
+    a.inv_bsz = a.tiles_x > 0 ? 1.0f / (float)(4 * a.tiles_x) : 1.0f;
+    a.blk4 = k.blk4 && a.tiles_x > 0 && 4 * a.tiles_x < 65536 ? 1 : 0;  // the tile walk inside an image: conv3s_kernel, and the tile lists of conv3r / conv3t
+    auto magic = [](long long d) { return d <= 1 ? 0xffffffffu : (uint32_t)(4294967296ULL / (unsigned long long)d); };
+    a.mg_gsz = magic((long long)a.gm * a.gn); a.mg_groups_m = magic(a.groups_m); a.mg_gn = magic(a.gn);
+    a.mg_tpi = magic(a.tiles_x > 0 ? (long long)a.tiles_x * a.tiles_y : 1); a.mg_tiles_x = magic(a.tiles_x > 0 ? a.tiles_x : 1);
+    a.mg_bsz = magic(a.tiles_x > 0 ? 4LL * a.tiles_x : 1);
+}
+
+// ------------------------------------------------------------------------------------------------
+// kernel selection: which kernel runs a 3x3 convolution or a mix, in which geometry.  Functions of the plan (ConvW sizes, never
+// whether a buffer happens to be allocated), the knobs, the shape and the CU count only -- no HIP call: mz_debug_select() runs them
+// without a GPU, and tests/test_select_cpu.py pins their table.
+// ------------------------------------------------------------------------------------------------
+enum Launcher { L_CONV, L_CONV3R, L_CONV3T, L_MIX16, L_MIX16B };
+
+struct KernelChoice {
+    const char* name = nullptr;  // what mz_debug_last_kernel() reports; nullptr = the launch is refused (mz_last_error() says why)
+    int launcher = L_CONV;
+    int mode = MODE_GEMM1;       // launch_conv's ConvMode; 3x3: that of the 512 / 256-pixel kernels even where conv3r / conv3t run
+                                 // (it also sizes the fused mix's x ring, ConvArgs::x_via_lds)
+    int th = 0, tw = 0;          // 3x3: pixel tile
+    int geo = 0;                 // conv3r_kernel: 1 = 8 x 40 tiles
+    int ragged_planes = 0;       // conv3r_kernel's ragged variant (Cin = 48)
+    bool s16 = false;            // the 16x16x32-MFMA packing (ConvW::packed16 / packed16r / packed16t)
+    bool tile_list = false;      // walks a tile table (conv3r / conv3t, Runner::tile_table)
+    int persist = 0;             // persistent workgroups at most; 0 = one workgroup per tile
+};
+
+// workgroups of a persistent launch: one per CU, a multiple of 8 (one equal share per XCD).  Knobs::persist overrides: 0 = one
+// workgroup per tile everywhere (A/B timing); n = force n (tests use 8 / 16 so that small images walk several tiles per workgroup).
+static int persistent_workgroups(const Knobs& k, int cus) { return k.persist >= 0 ? k.persist : cus; }
+
+// 32-bit buffer offsets: `planes` 16-byte channel planes of `pixels` pixels stay below 4 GiB
+static bool offsets_fit(double planes, double pixels) { return planes * pixels * 16.0 < 4294967296.0; }
+
+// the gate weights in accumulator-row order (ConvW::packed16r): exactly where pack_conv() packs them
+static bool has_packed16r(const ConvW& c) {
+    return c.packed16_sz > 0 && ((c.in_map == SRC_MIXF && c.nt == 3) || (c.in_map == SRC_CONCAT && c.nchunks16 == 12));
+}
+
+// conv2 + AdaptiveResidualMix of a block in one launch: all output channels in one workgroup (BlockW::fused), on the 512-pixel kernels
+static bool fuse_mix(const Knobs& k, const BlockW& b) { return b.fused && k.wide && k.fuse; }
+
+// conv3x3, pad 1: epi STORE / D2S (into Hout x Wout) / FINAL / FUSEDMIX (mixf = the block's gate weights); film = FiLM epilogue
+static KernelChoice choose_conv3(const Knobs& k, int dtype, const ConvW& c, const ConvW* mixf, int epi, int silu, bool film,
+                                 int B, int H, int W, int Hout, int Wout, int cus) {
+    KernelChoice ch;
+    const int wgs = persistent_workgroups(k, cus);
+    const double px = (double)H * W;  // the offset guards hold inside one image
+    // tile shape: the 512-pixel kernels (NT <= 3) in the shape that wastes fewer padded pixels, else 8 x 32
+    int mode = MODE_CONV3, th = 8, tw = 32;
+    if (c.nt <= 3 && k.wide) {
+        const long long waste16 = (long long)((H + 15) / 16 * 16) * ((W + 31) / 32 * 32);
+        const long long waste8 = (long long)((H + 7) / 8 * 8) * ((W + 63) / 64 * 64);
+        if (waste8 <= waste16) { mode = MODE_C3W8; th = 8; tw = 64; }
+        else { mode = MODE_C3W16; th = 16; tw = 32; }
+    }
+    // The image head (12 output channels + PixelShuffle + bicubic skip + clamp) is a per-tile kernel whose load, K loop and long
+    // epilogue run one after the other: on 512-pixel tiles (183 KB of LDS) a CU holds ONE workgroup and nothing overlaps; on the
+    // 256-pixel kernel several fit and one tile's epilogue runs under another's loads (2160 x 3840, Cin = 96: 2.34 -> 1.60 ms per 3
+    // images).  Chosen by dtype only, never by the image size.
+    if (epi == EPI_FINAL && dtype != DT_F32) { mode = MODE_CONV3; th = 8; tw = 32; }
+    ch.mode = mode;
+
+    // what every 16x16x32-MFMA kernel needs: a 16-bit type, a persistent launch
+    const bool s16 = k.s16 && dtype != DT_F32 && wgs > 0;
+    // ... and (all but conv3t) padding K to whole 32-channel chunks only where that wastes less than the shape gains (~12 %)
+    const bool k_fits = c.nchunks16 * 32 * 100 <= c.cp0 * (100 + k.kpad_pct);
+    const bool halo_fits = offsets_fit(4, px);  // 32-bit halo offsets span four planes
+    const int p0 = c.cp0 * dtype_size(dtype) / 16;
+    // conv3r / conv3t walk a tile list whose entries hold image, N tile and pixel coordinates in 16 bits each
+    auto listed = [&](const char* name, int launcher, int lth, int ltw) {
+        ch.name = name; ch.launcher = launcher; ch.th = lth; ch.tw = ltw;
+        ch.s16 = ch.tile_list = true;
+        ch.persist = wgs;
+        if (B >= 65536 || c.ntiles >= 65536 || (H + lth - 1) / lth * lth >= 65536 || (W + ltw - 1) / ltw * ltw >= 65536) {
+            fail(MZ_ERR_INVALID_ARGUMENT, "tile table: image, batch or N-tile index beyond 16 bits");
+            ch.name = nullptr;
+        }
+        return ch;
+    };
+
+    // conv3t_kernel: ONE N tile of 33..48 channels (the level-1 block of the 48-channel models), whole 32-channel chunks, three or six
+    // and more of them; 12 x 64 pixel tiles; stores and x loads carry 32-bit offsets inside six planes.  The choice depends on channel
+    // counts only (never on H or W): its fused variant sums the gate in another order than conv3s_kernel<.., FUSE> -- equal to <= 1 ulp,
+    // not bit for bit --, and a tile of upscale_tiled() must run the kernel the whole image runs.
+    const bool t_fuse = epi == EPI_FUSEDMIX && k.fuse16 && mixf && mixf->packed16t_sz > 0;
+    if (k.t && s16 && !film && c.packed16t_sz > 0 && c.ntiles == 1 && (c.nchunks16t == 3 || c.nchunks16t >= 6) &&
+        (epi == EPI_STORE || t_fuse) && halo_fits && offsets_fit(6, px))
+        return listed(t_fuse ? "conv3t_fused" : "conv3t", L_CONV3T, 12, 64);
+
+    // conv3r_kernel's ragged variant: conv1 + SiLU with Cin = 48 (two 32-channel chunks, the second with two real planes) into 96-channel
+    // N tiles.  The kernel it replaces (conv3p_kernel: 32x32x16 MFMA, exact 16-channel chunks) sums in another order, so the choice
+    // depends on channel counts, dtype and knobs only -- never on H or W.
+    if (k.r && k.r2 && s16 && !film && c.nt == 3 && c.packed16_sz > 0 && epi == EPI_STORE && silu && c.nchunks16 == 2 && c.cp0 == 48 &&
+        halo_fits && offsets_fit(12, px)) {
+        ch.ragged_planes = (c.cp0 - 32) / 8;
+        return listed("conv3r_ragged", L_CONV3R, 8, 48);
+    }
+
+    // conv3r_kernel's fused variant (conv2 + AdaptiveResidualMix, C = 96): six or more chunks (one pixel fragment's gate GEMM and blend
+    // per chunk), the gate weights packed in accumulator-row order, x and out within 32-bit offsets.  NOT a function of H and W: this
+    // kernel and conv3s_kernel<.., FUSE> sum the x half of the gate in different orders inside a 32-wide K step -- equal to <= 1 ulp, not
+    // bit for bit -- and a tile of upscale_tiled() must run the kernel the whole image runs, or "tiled == untiled bit for bit"
+    // (ultrazoom_amd/tiling.py) breaks.
+    if (k.r && k.fuse16 && epi == EPI_FUSEDMIX && s16 && c.nt == 3 && c.ntiles == 1 && c.packed16_sz > 0 && mixf && has_packed16r(*mixf) &&
+        (mixf->cp0 + 31) / 32 == c.nt && c.nchunks16 >= 6 && p0 % 4 == 0 && k_fits && halo_fits && offsets_fit(12, px))
+        return listed("conv3r_fused", L_CONV3R, 8, 48);
+
+    // conv3r_kernel: 96-channel N tiles, any chunk count >= 3 of four whole planes (its halo loads carry the plane in the scalar offset,
+    // which the hardware's range check does not cover); its stores carry 32-bit offsets inside 12 output planes / one D2S target image.
+    // Its tiles are 8 x 48, or 8 x 40 (five pixel fragments per wave: widths like 120 that 48 does not divide) where those pad fewer
+    // pixels, and it runs where they pad no more than the better of the 8 x 64 / 16 x 32 tiles.  (The plain variants accumulate in the
+    // same order as conv3s_kernel whatever the tile shape: bit-identical, so this choice may follow H and W.)
+    if (k.r && s16 && !film && c.nt == 3 && c.packed16_sz > 0 && (epi == EPI_STORE || epi == EPI_D2S) && k_fits && halo_fits &&
+        c.nchunks16 >= 3 && p0 % 4 == 0 &&
+        (epi == EPI_D2S ? offsets_fit(c.cq_p * dtype_size(dtype) / 16, (double)Hout * Wout) : offsets_fit(12, px))) {
+        const long long rows8 = (long long)((H + 7) / 8 * 8);
+        const long long pad48 = rows8 * ((W + 47) / 48 * 48), pad40 = rows8 * ((W + 39) / 40 * 40);
+        const long long pads = (long long)((H + th - 1) / th) * th * ((W + tw - 1) / tw) * tw;
+        const int geo = pad40 < pad48 ? 1 : 0;
+        if ((geo ? pad40 : pad48) <= pads) {
+            ch.geo = geo;
+            return listed(geo ? "conv3r_8x40" : "conv3r", L_CONV3R, 8, geo ? 40 : 48);
+        }
+    }
+
+    // the 512-pixel kernels (per tile: conv3w; persistent: conv3p, or conv3s on the 16x16x32 MFMA) and the 256-pixel conv_kernel
+    ch.th = th; ch.tw = tw;
+    const bool fused = epi == EPI_FUSEDMIX;
+    const bool fuse16 = fused && mixf && mixf->packed16_sz > 0 && k.fuse16 &&
+                        (mixf->cp0 + 31) / 32 == c.nt;  // x K-steps == z K-steps (always so for C <= 96)
+    if (mode != MODE_CONV3 && (epi == EPI_STORE || epi == EPI_D2S || fuse16) && wgs > 0) {
+        ConvArgs g;  // the per-tile grid
+        memset(&g, 0, sizeof(g));
+        g.tiles_x = (W + tw - 1) / tw; g.tiles_y = (H + th - 1) / th;
+        g.mtiles = B * g.tiles_x * g.tiles_y; g.ntiles = c.ntiles;
+        pick_order(g, c, (double)B * H * W * c.cp0 * (double)dtype_size(dtype), k);
+        if (s16 && c.packed16_sz > 0 && k_fits && halo_fits) {  // conv3s: 32-bit halo offsets span four planes
+            ch.s16 = true;
+            ch.persist = wgs;
+        } else if (g.grid > wgs && offsets_fit(2, px)) {
+            // conv3p_kernel: 32-bit halo offsets span the two planes of a 16-channel stage; larger images stay on the per-tile
+            // kernel (64-bit addresses)
+            ch.persist = wgs;
+        }
+    }
+    if (film && !ch.s16) {
+        fail(MZ_ERR_INVALID_ARGUMENT, "the FiLM epilogue exists on the 16x16x32 kernel only: bf16 / fp16, at most 96 output channels per "
+                                      "N tile, input channels within 12.5 %% of a multiple of 32");
+        return ch;
+    }
+    ch.launcher = L_CONV;
+    ch.name = mode == MODE_CONV3 ? "conv_kernel"
+              : ch.persist > 0  ? (ch.s16 ? (fused ? "conv3s_fused" : "conv3s") : "conv3p")
+                                : (fused ? "conv3w_fused" : "conv3w");
+    return ch;
+}
+
+// AdaptiveResidualMix of C channels (c: the [C, 2C] gate weights, SRC_CONCAT) over B x H x W pixels
+static KernelChoice choose_mix(const Knobs& k, int dtype, const ConvW& c, int B, int H, int W, int cus) {
+    KernelChoice ch;
+    ch.mode = MODE_GEMM1;
+    // mix16_kernel: C = k * 192 (192-channel N tiles, x / z straight into MFMA operands), 32-bit buffer offsets inside each tensor;
+    // mix16b_kernel (C = 192) is persistent, also under MZ_NO_PERSIST=1: it has no per-tile form
+    const bool mix16 = c.packed16_sz > 0 && offsets_fit(c.cp0 * dtype_size(dtype) / 16.0, (double)B * H * W);
+    const int wgs = k.persist > 0 ? k.persist : cus;
+    if (mix16 && k.mix16b && has_packed16r(c) && c.nchunks16 == 12 && wgs > 0) {
+        ch.name = "mix16b"; ch.launcher = L_MIX16B; ch.s16 = true; ch.persist = wgs;
+    } else if (mix16) {
+        ch.name = "mix16"; ch.launcher = L_MIX16; ch.s16 = true;
+    } else {
+        ch.name = "conv_kernel_mix"; ch.launcher = L_CONV;
+    }
+    return ch;
+}
+
 struct Runner {
     mz_handle* h;
     hipStream_t s;
     int dtype;
     int rc = MZ_OK;
     const Knobs knobs = h->knobs;
-    bool wide_tiles = knobs.wide;
-    bool no_fuse = !knobs.fuse;
     int io_u8 = 0;                                        // images at both ends are uint8 (mz_forward_u8)
     const float* film_gamma = nullptr;                    // mz_op_conv_film: per-image per-channel affine on the next conv3 call
     const float* film_beta = nullptr;
-    bool use_s16 = knobs.s16;
-    int persist_wgs = persistent_workgroups(knobs);       // 0: one workgroup per tile everywhere
+    int cus = current_cus();
 
-    void prof_begin(ProfRec*& r, double flops, double bytes, int is_conv3) {
-        r = nullptr;
-        if (!h || !h->prof) return;
+    // the profiling record of one launch (kind: 0 conv3, 1 mix, 2 crush); nullptr unless the handle profiles
+    ProfRec* prof_begin(int kind, const ConvArgs& a, const ConvW& c, double flops, double bytes) {
+        if (!h || !h->prof) return nullptr;
         if (h->recs_used == h->recs.size()) {
             ProfRec n;
-            if (hipEventCreate(&n.a) != hipSuccess || hipEventCreate(&n.b) != hipSuccess) return;
+            if (hipEventCreate(&n.a) != hipSuccess || hipEventCreate(&n.b) != hipSuccess) return nullptr;
             h->recs.push_back(n);
         }
-        r = &h->recs[h->recs_used++];
-        r->flops = flops; r->bytes = bytes; r->is_conv3 = is_conv3;
-        r->kind = r->B = r->H = r->W = r->cin = r->cout = r->nt = r->ntiles = r->mtiles = r->n_fast = 0;
+        ProfRec* r = &h->recs[h->recs_used++];
+        r->flops = flops; r->bytes = bytes; r->is_conv3 = kind == 0;
+        r->kind = kind; r->B = a.B; r->H = a.H; r->W = a.W; r->cin = c.cin; r->cout = c.cout; r->nt = c.nt; r->ntiles = a.ntiles;
+        r->mtiles = a.mtiles; r->n_fast = a.gm * 1000 + a.gn;
         (void)hipEventRecord(r->a, s);
+        return r;
     }
     void prof_end(ProfRec* r) {
         if (r) (void)hipEventRecord(r->b, s);
@@ -698,55 +897,17 @@ struct Runner {
         a.nchunks = c.nchunks;
         a.nchunks_real = c.nchunks_real;
         a.ntiles = c.ntiles;
-        a.use_glds = knobs.use_glds;
-    }
-
-    void pick_order(ConvArgs& a, const ConvW& c, double act_bytes, int resident_per_xcd = 32) {
-        // Tile groups of gm pixel tiles x gn N tiles (gm * gn ~ the workgroups resident on one XCD): inside a group
-        // both operands are shared through the XCD's L2; per group the activations are re-read ntiles/gn times and
-        // the weights mtiles/gm times in total.  Pick the shape with the least total re-read traffic.
-        const double W = (double)c.packed_sz, A = act_bytes;
-        int best_gm = a.mtiles, best_gn = 1;
-        double best = 1e300;
-        for (int gn = 1; gn <= a.ntiles; ++gn) {
-            if (gn > resident_per_xcd) break;
-            if (a.ntiles % gn != 0 && gn != a.ntiles) continue;
-            int gm = resident_per_xcd / gn;
-            if (gm < 1) gm = 1;
-            if (gm > a.mtiles) gm = a.mtiles;
-            const double groups_n = std::ceil((double)a.ntiles / gn), groups_m = std::ceil((double)a.mtiles / gm);
-            const double traffic = A * groups_n + W * groups_m;
-            if (traffic < best) { best = traffic; best_gm = gm; best_gn = gn; }
-        }
-        a.gm = best_gm; a.gn = best_gn;
-        const long long groups = (long long)((a.mtiles + a.gm - 1) / a.gm) * ((a.ntiles + a.gn - 1) / a.gn);
-        a.grid = (int)(groups * a.gm * a.gn);
-        a.groups_m = (a.mtiles + a.gm - 1) / a.gm;
-        a.inv_gsz = 1.0f / (float)(a.gm * a.gn);
-        a.inv_groups_m = 1.0f / (float)a.groups_m;
-        a.inv_gn = 1.0f / (float)a.gn;
-        a.inv_tpi = a.tiles_x > 0 ? 1.0f / (float)(a.tiles_x * a.tiles_y) : 1.0f;
-        a.inv_tiles_x = a.tiles_x > 0 ? 1.0f / (float)a.tiles_x : 1.0f;
-        a.inv_bsz = a.tiles_x > 0 ? 1.0f / (float)(4 * a.tiles_x) : 1.0f;
-        a.blk4 = knobs.blk4 && a.tiles_x > 0 && 4 * a.tiles_x < 65536 ? 1 : 0;  // the tile walk inside an image: conv3s_kernel, and the tile lists of conv3r / conv3t
-        auto magic = [](long long d) { return d <= 1 ? 0xffffffffu : (uint32_t)(4294967296ULL / (unsigned long long)d); };
-        a.mg_gsz = magic((long long)a.gm * a.gn); a.mg_groups_m = magic(a.groups_m); a.mg_gn = magic(a.gn);
-        a.mg_tpi = magic(a.tiles_x > 0 ? (long long)a.tiles_x * a.tiles_y : 1); a.mg_tiles_x = magic(a.tiles_x > 0 ? a.tiles_x : 1);
-        a.mg_bsz = magic(a.tiles_x > 0 ? 4LL * a.tiles_x : 1);
+        a.use_glds = 1;  // read by no kernel today; kept so that the argument block stays as it was
     }
 
     // conv3r_kernel / conv3t_kernel: the launch's tiles in walk order as a table in HBM (ConvArgs::tile_tab), so that the kernels'
     // helper role -- the critical path of their short tiles -- reads a tile's coordinates with one scalar load instead of running
     // the divisions of the group walk (tile_of_s / tile_rc_s, mz_device.h) three times per phase.  The order IS that walk's: ids
     // 0 .. grid - 1 in gm x gn groups, the tiles of an image in block rows of four tile rows (blk4), padding ids dropped.  Needs
-    // pick_order() done; sets a.tile_tab, a.grid (= tiles listed) and a.persist.  One table per geometry, kept with the handle.
-    void tile_table(ConvArgs& a, int th, int tw) {
-        if (rc) return;
-        if (a.B >= 65536 || a.ntiles >= 65536 || a.tiles_y * th >= 65536 || a.tiles_x * tw >= 65536) {
-            rc = fail(MZ_ERR_INVALID_ARGUMENT, "tile table: image, batch or N-tile index beyond 16 bits");
-            return;
-        }
-        const int pad = 4 * ((persist_wgs > 256 ? persist_wgs : 256) / 8) + 8;
+    // pick_order() done; sets a.tile_tab and a.grid (= tiles listed), padded for up to wgs workgroups.  One table per geometry, kept
+    // with the handle.
+    void tile_table(ConvArgs& a, int th, int tw, int wgs) {
+        const int pad = 4 * ((wgs > 256 ? wgs : 256) / 8) + 8;
         const std::vector<int> key = {th, tw, a.B, a.tiles_x, a.tiles_y, a.ntiles, a.gm, a.gn, a.grid, a.blk4, pad};
         auto it = h->tile_tabs.find(key);
         if (it == h->tile_tabs.end()) {
@@ -762,15 +923,27 @@ struct Runner {
         }
         a.tile_tab = it->second.first;
         a.grid = it->second.second;
-        const int need = (a.grid + 7) / 8 * 8;
-        a.persist = need < persist_wgs ? need : persist_wgs;
     }
 
-    // conv3x3, pad 1 (model.py:742-748, 900-909, 1010). epi: STORE / D2S / FINAL
+    void launch(const KernelChoice& ch, const ConvArgs& a, int nt, ProfRec* r) {
+        g_last_kernel = ch.name;
+        switch (ch.launcher) {
+            case L_CONV3T: check(launch_conv3t(dtype, a, s), ch.name); break;
+            case L_CONV3R: check(launch_conv3r(dtype, a, s), ch.name); break;
+            case L_MIX16: check(launch_mix16(dtype, a, s), ch.name); break;
+            case L_MIX16B: check(launch_mix16b(dtype, a, s, ch.persist), ch.name); break;
+            default: check(launch_conv(dtype, ch.mode, nt, a, s), ch.name); break;
+        }
+        prof_end(r);
+    }
+
+    // conv3x3, pad 1 (model.py:742-748, 900-909, 1010). epi: STORE / D2S / FINAL / FUSEDMIX
     void conv3(const ConvW& c, const void* in, void* out, int B, int H, int W, int epi, int silu, int Hout, int Wout,
                const void* img = nullptr, int R = 0, int clamp = 0, const void* zero_override = nullptr,
                const ConvW* mixf = nullptr, const void* xin = nullptr, float alpha = 0.f) {
         if (rc) return;
+        const KernelChoice ch = choose_conv3(knobs, dtype, c, mixf, epi, silu, film_gamma != nullptr, B, H, W, Hout, Wout, cus);
+        if (!ch.name) { rc = MZ_ERR_INVALID_ARGUMENT; return; }
         ConvArgs a;
         base_args(a, c);
         if (zero_override) a.zero = zero_override;
@@ -778,20 +951,7 @@ struct Runner {
         a.B = B; a.H = H; a.W = W; a.Ho = H; a.Wo = W;
         a.p0 = c.cp0 * dtype_size(dtype) / 16;
         a.src = SRC_PLAIN;
-        // tile shape: the 512-pixel kernels (NT <= 3) in the shape that wastes fewer padded pixels, else 8 x 32
-        int mode = MODE_CONV3, th = 8, tw = 32;
-        if (c.nt <= 3 && wide_tiles) {
-            const long long waste16 = (long long)((H + 15) / 16 * 16) * ((W + 31) / 32 * 32);
-            const long long waste8 = (long long)((H + 7) / 8 * 8) * ((W + 63) / 64 * 64);
-            if (waste8 <= waste16) { mode = MODE_C3W8; th = 8; tw = 64; }
-            else { mode = MODE_C3W16; th = 16; tw = 32; }
-        }
-        // The image head (12 output channels + PixelShuffle + bicubic skip + clamp) is a per-tile kernel whose load, K loop and long
-        // epilogue run one after the other: on 512-pixel tiles (183 KB of LDS) a CU holds ONE workgroup and nothing overlaps; on the
-        // 256-pixel kernel several fit and one tile's epilogue runs under another's loads (2160 x 3840, Cin = 96: 2.34 -> 1.60 ms per 3
-        // images).  Chosen by dtype and knobs only, never by the image size.
-        if (epi == EPI_FINAL && knobs.head256 && dtype != DT_F32) { mode = MODE_CONV3; th = 8; tw = 32; }
-        a.tiles_x = (W + tw - 1) / tw; a.tiles_y = (H + th - 1) / th;
+        a.tiles_x = (W + ch.tw - 1) / ch.tw; a.tiles_y = (H + ch.th - 1) / ch.th;
         a.mtiles = B * a.tiles_x * a.tiles_y;
         a.epi = epi; a.silu = silu;
         a.cp_out = epi == EPI_D2S ? c.cq_p : pad16(c.cout);
@@ -799,171 +959,48 @@ struct Runner {
         a.Hout = Hout; a.Wout = Wout;
         a.img = img; a.R = R; a.clamp = clamp;
         if (epi == EPI_FINAL) { a.Hi = Hout / R; a.Wi = Wout / R; a.io_u8 = io_u8; }
-        double extra_flops = 0.0;
-        if (epi == EPI_FUSEDMIX) {
+        const bool fused = epi == EPI_FUSEDMIX;
+        if (fused) {
             a.in1 = xin;
             a.p1 = pad16(c.cout) * dtype_size(dtype) / 16;
             a.wmix = mixf->packed;
             a.mix_pieces = mixf->nchunks * mixf->nt;
             {   // room for the 8 compute waves' x fragments next to the gate weights in ring slots 1-2?
-                const int a_slot = (mode == MODE_C3W16 ? 2 * 640 : 2 * 672) * 16;
+                const int a_slot = (ch.mode == MODE_C3W16 ? 2 * 640 : 2 * 672) * 16;
                 const int slot = a_slot + 9 * c.nt * 1024;
                 const int ncx = a.p1 / 2;
                 a.x_via_lds = (a.mix_pieces * 1024 + 8 * ncx * 1024 <= 2 * slot) ? 1 : 0;
             }
             a.mix_scale = 1.0f / (1.0f + std::exp(-alpha));
             a.inv_mix_scale = inv_sigmoid(alpha);
-            extra_flops = 2.0 * (double)B * H * W * 2.0 * c.cout * c.cout;
         }
+        a.geo = ch.geo;
+        a.ragged_planes = ch.ragged_planes;
         const double sz = dtype_size(dtype);
         const double px = (double)B * H * W;
-        // what conv3r_kernel's plain variants need in common: 16-bit type, 96-channel N tiles, the 16x16x32 packing, K padding within the knob
-        const bool r_common = use_s16 && !film_gamma && dtype != DT_F32 && c.nt == 3 && c.packed16 && (epi == EPI_STORE || epi == EPI_D2S) &&
-                        persist_wgs > 0 && c.nchunks16 * 32 * 100 <= c.cp0 * (100 + knobs.kpad_pct) &&
-                        (double)H * W * 64.0 < 4294967296.0;
-        // conv3t_kernel: ONE N tile of 33..48 channels (the level-1 block of the 48-channel models), whole 32-channel chunks, three or six
-        // and more of them; 12 x 64 pixel tiles; stores and x loads carry 32-bit offsets inside six planes.  The choice depends on channel
-        // counts only (never on H or W): its fused variant sums the gate in another order than conv3s_kernel<.., FUSE> -- equal to <= 1 ulp,
-        // not bit for bit --, and a tile of upscale_tiled() must run the kernel the whole image runs.
-        const bool t_fuse = epi == EPI_FUSEDMIX && knobs.fuse16 && mixf && mixf->packed16t;
-        const bool use_t = knobs.t && use_s16 && !film_gamma && dtype != DT_F32 && c.packed16t && c.ntiles == 1 && persist_wgs > 0 &&
-                           (c.nchunks16t == 3 || c.nchunks16t >= 6) && ((epi == EPI_STORE) || t_fuse) &&
-                           (double)H * W * 64.0 < 4294967296.0 && 6.0 * H * W * 16.0 < 4294967296.0;
-        if (use_t) {
-            a.tiles_x = (W + 63) / 64; a.tiles_y = (H + 11) / 12;
-            a.mtiles = B * a.tiles_x * a.tiles_y;
-            pick_order(a, c, px * c.cp0 * sz);
-            a.s16 = 1; a.wpk16 = c.packed16t; a.nchunks16 = c.nchunks16t;
-            if (t_fuse) a.wmix16 = mixf->packed16t;
-            tile_table(a, 12, 64);
-            if (rc) return;
-            const double extra_bytes = epi == EPI_FUSEDMIX ? px * c.cout * sz : 0.0;
-            ProfRec* r;
-            prof_begin(r, 2.0 * px * 9.0 * c.cin * c.cout + extra_flops, px * (c.cin + c.cout) * sz + 9.0 * c.cin * c.cout * sz + extra_bytes, 1);
-            if (r) { r->kind = 0; r->B = B; r->H = H; r->W = W; r->cin = c.cin; r->cout = c.cout; r->nt = c.nt; r->ntiles = a.ntiles; r->mtiles = a.mtiles; r->n_fast = a.gm * 1000 + a.gn; }
-            g_last_kernel = t_fuse ? "conv3t_fused" : "conv3t";
-            check(launch_conv3t(dtype, a, s), "conv3t launch");
-            prof_end(r);
-            return;
+        pick_order(a, c, px * c.cp0 * sz, knobs);
+        if (ch.s16) {
+            const bool t = ch.launcher == L_CONV3T;
+            a.s16 = 1;
+            a.wpk16 = t ? c.packed16t : c.packed16;
+            a.nchunks16 = t ? c.nchunks16t : c.nchunks16;
+            if (fused) a.wmix16 = t ? mixf->packed16t : (ch.launcher == L_CONV3R ? mixf->packed16r : mixf->packed16);
         }
-        // conv3r_kernel's ragged variant: conv1 + SiLU with Cin = 48 (two 32-channel chunks, the second with two real planes) into 96-channel
-        // N tiles.  The kernel it replaces (conv3p_kernel: 32x32x16 MFMA, exact 16-channel chunks) sums in another order, so the choice
-        // depends on channel counts, dtype and knobs only -- never on H or W.
-        const bool use_r2 = knobs.r && knobs.r2 && use_s16 && !film_gamma && dtype != DT_F32 && c.nt == 3 && c.packed16 && epi == EPI_STORE && silu &&
-                            persist_wgs > 0 && c.nchunks16 == 2 && c.cp0 == 48 && (double)H * W * 64.0 < 4294967296.0 &&
-                            12.0 * H * W * 16.0 < 4294967296.0;
-        if (use_r2) {
-            a.tiles_x = (W + 47) / 48; a.tiles_y = (H + 7) / 8;
-            a.mtiles = B * a.tiles_x * a.tiles_y;
-            pick_order(a, c, px * c.cp0 * sz);
-            a.s16 = 1; a.wpk16 = c.packed16; a.nchunks16 = 2;
-            a.ragged_planes = (c.cp0 - 32) / 8;
-            tile_table(a, 8, 48);
-            if (rc) return;
-            ProfRec* r;
-            prof_begin(r, 2.0 * px * 9.0 * c.cin * c.cout, px * (c.cin + c.cout) * sz + 9.0 * c.cin * c.cout * sz, 1);
-            if (r) { r->kind = 0; r->B = B; r->H = H; r->W = W; r->cin = c.cin; r->cout = c.cout; r->nt = c.nt; r->ntiles = a.ntiles; r->mtiles = a.mtiles; r->n_fast = a.gm * 1000 + a.gn; }
-            g_last_kernel = "conv3r_ragged";
-            check(launch_conv3r(dtype, a, s), "conv3r ragged launch");
-            prof_end(r);
-            return;
-        }
-        // padded pixels of conv3r's 8 x 48 tiles -- and of its second geometry, 8 x 40 (five pixel fragments per wave: widths
-        // like 120 that 48 does not divide) -- against the better of the 8 x 64 / 16 x 32 tiles.  (All plain variants accumulate in the same
-        // order whatever the tile shape: bit-identical, so this choice may depend on H and W.)
-        const long long rows8 = (long long)((H + 7) / 8 * 8);
-        const long long pad48 = rows8 * ((W + 47) / 48 * 48), pad40 = rows8 * ((W + 39) / 40 * 40);
-        const long long pads = (long long)a.tiles_y * th * a.tiles_x * tw;
-        // conv3r_kernel: any chunk count >= 3 of four whole planes (its halo loads carry the plane in the scalar offset, which the
-        // hardware's range check does not cover); its stores carry 32-bit offsets inside 12 output planes / one D2S target image
-        const bool r_ok = knobs.r && r_common && c.nchunks16 >= 3 && a.p0 % 4 == 0 &&
-                          (epi == EPI_D2S ? (double)(c.cq_p * dtype_size(dtype) / 16) * Hout * Wout * 16.0 < 4294967296.0
-                                          : 12.0 * H * W * 16.0 < 4294967296.0);
-        const int geo = (r_ok && knobs.geo40 && pad40 < pad48) ? 1 : 0;
-        const int tw_r = geo ? 40 : 48;
-        const bool use_r = r_ok && (geo ? pad40 : pad48) <= pads;
-        // ... and its fused variant (conv2 + AdaptiveResidualMix, C = 96): six or more chunks (one pixel fragment's gate GEMM and
-        // blend per chunk), the gate weights packed in accumulator-row order, x and out within 32-bit offsets
-        bool use_rf = knobs.r && knobs.fuse16 && epi == EPI_FUSEDMIX && use_s16 && dtype != DT_F32 && c.nt == 3 && c.ntiles == 1 && c.packed16 &&
-                      mixf && mixf->packed16r && (mixf->cp0 + 31) / 32 == c.nt && persist_wgs > 0 && c.nchunks16 >= 6 && a.p0 % 4 == 0 &&
-                      c.nchunks16 * 32 * 100 <= c.cp0 * (100 + knobs.kpad_pct) && (double)H * W * 64.0 < 4294967296.0 &&
-                      12.0 * H * W * 16.0 < 4294967296.0;
-        // (NOT a function of H and W: this kernel and conv3s_kernel<.., FUSE> sum the x half of the gate in different orders inside a
-        // 32-wide K step -- equal to <= 1 ulp, not bit for bit -- and a tile of upscale_tiled() must run the kernel the whole image runs,
-        // or "tiled == untiled bit for bit" (ultrazoom_amd/tiling.py) breaks.  The plain variants above ARE bit-identical to
-        // conv3s_kernel, so their choice may follow the padded-pixel count.)
-        if (use_rf) {
-            a.tiles_x = (W + 47) / 48; a.tiles_y = (H + 7) / 8;
-            a.mtiles = B * a.tiles_x * a.tiles_y;
-            pick_order(a, c, px * c.cp0 * sz);
-            a.s16 = 1; a.wpk16 = c.packed16; a.nchunks16 = c.nchunks16;
-            a.wmix16 = mixf->packed16r;
-            tile_table(a, 8, 48);
-            if (rc) return;
-            ProfRec* r;
-            prof_begin(r, 2.0 * px * 9.0 * c.cin * c.cout + extra_flops, px * (c.cin + c.cout) * sz + 9.0 * c.cin * c.cout * sz + px * c.cout * sz, 1);
-            if (r) { r->kind = 0; r->B = B; r->H = H; r->W = W; r->cin = c.cin; r->cout = c.cout; r->nt = c.nt; r->ntiles = a.ntiles; r->mtiles = a.mtiles; r->n_fast = a.gm * 1000 + a.gn; }
-            g_last_kernel = "conv3r_fused";
-            check(launch_conv3r(dtype, a, s), "conv3r fused launch");
-            prof_end(r);
-            return;
-        }
-        if (use_r) {
-            a.geo = geo;
-            a.tiles_x = (W + tw_r - 1) / tw_r; a.tiles_y = (H + 7) / 8;
-            a.mtiles = B * a.tiles_x * a.tiles_y;
-            pick_order(a, c, px * c.cp0 * sz);
-            a.s16 = 1; a.wpk16 = c.packed16; a.nchunks16 = c.nchunks16;
-            tile_table(a, 8, tw_r);
-            if (rc) return;
-            ProfRec* r;
-            prof_begin(r, 2.0 * px * 9.0 * c.cin * c.cout, px * (c.cin + c.cout) * sz + 9.0 * c.cin * c.cout * sz, 1);
-            if (r) { r->kind = 0; r->B = B; r->H = H; r->W = W; r->cin = c.cin; r->cout = c.cout; r->nt = c.nt; r->ntiles = a.ntiles; r->mtiles = a.mtiles; r->n_fast = a.gm * 1000 + a.gn; }
-            g_last_kernel = a.geo ? "conv3r_8x40" : "conv3r";
-            check(launch_conv3r(dtype, a, s), "conv3r launch");
-            prof_end(r);
-            return;
-        }
-        pick_order(a, c, px * c.cp0 * sz);
-        const bool fuse16 = epi == EPI_FUSEDMIX && mixf && mixf->packed16 && knobs.fuse16 &&
-                            (mixf->cp0 + 31) / 32 == c.nt;  // x K-steps == z K-steps (always so for C <= 96)
-        if (mode != MODE_CONV3 && (epi == EPI_STORE || epi == EPI_D2S || fuse16) && persist_wgs > 0) {
-            // 16-bit types: the 16x16x32-MFMA kernel (persistent only; 32-bit halo offsets span four planes)
-            // ... and only where padding K to whole 32-channel chunks wastes less than the shape gains (~12 %)
-            const bool k_fits = c.nchunks16 * 32 * 100 <= c.cp0 * (100 + knobs.kpad_pct);
-            if (c.packed16 && use_s16 && k_fits && (double)H * W * 64.0 < 4294967296.0) {
-                a.s16 = 1; a.wpk16 = c.packed16; a.nchunks16 = c.nchunks16;
-                if (fuse16) a.wmix16 = mixf->packed16;
-                const int need = (a.grid + 7) / 8 * 8;
-                a.persist = need < persist_wgs ? need : persist_wgs;
-            } else if (a.grid > persist_wgs && (double)H * W * 32.0 < 4294967296.0) {
-                // conv3p_kernel: 32-bit halo offsets span the two planes of a 16-channel stage; larger images stay on
-                // the per-tile kernel (64-bit addresses)
-                a.persist = persist_wgs;
-            }
-        }
-        if (film_gamma) {
-            if (!a.s16) {
-                rc = fail(MZ_ERR_INVALID_ARGUMENT, "the FiLM epilogue exists on the 16x16x32 kernel only: bf16 / fp16, at most 96 output "
-                                                   "channels per N tile, input channels within 12.5 %% of a multiple of 32");
-                return;
-            }
-            a.film_gamma = film_gamma; a.film_beta = film_beta;
-        }
-        // algorithmic bytes: input once, output once, weights once; a fused conv2 + mix also reads the block input x once
-        const double extra_bytes = epi == EPI_FUSEDMIX ? px * c.cout * sz : 0.0;
-        ProfRec* r;
-        prof_begin(r, 2.0 * px * 9.0 * c.cin * c.cout + extra_flops, px * (c.cin + c.cout) * sz + 9.0 * c.cin * c.cout * sz + extra_bytes, 1);
-        if (r) { r->kind = 0; r->B = B; r->H = H; r->W = W; r->cin = c.cin; r->cout = c.cout; r->nt = c.nt; r->ntiles = a.ntiles; r->mtiles = a.mtiles; r->n_fast = a.gm * 1000 + a.gn; }
-        g_last_kernel = mode == MODE_CONV3 ? "conv_kernel" : (a.persist > 0 ? (a.s16 ? (epi == EPI_FUSEDMIX ? "conv3s_fused" : "conv3s") : "conv3p")
-                                                                            : (epi == EPI_FUSEDMIX ? "conv3w_fused" : "conv3w"));
-        check(launch_conv(dtype, mode, c.nt, a, s), "conv3x3 launch");
-        prof_end(r);
+        if (ch.tile_list) tile_table(a, ch.th, ch.tw, ch.persist);
+        if (rc) return;
+        a.persist = std::min((a.grid + 7) / 8 * 8, ch.persist);
+        a.film_gamma = film_gamma; a.film_beta = film_beta;
+        // algorithmic flops and bytes: input once, output once, weights once; a fused conv2 + mix also runs the gate GEMM and reads the
+        // block input x once
+        const double flops = 2.0 * px * 9.0 * c.cin * c.cout + (fused ? 2.0 * px * 2.0 * c.cout * c.cout : 0.0);
+        const double bytes = px * (c.cin + c.cout) * sz + 9.0 * c.cin * c.cout * sz + (fused ? px * c.cout * sz : 0.0);
+        launch(ch, a, c.nt, prof_begin(0, a, c, flops, bytes));
     }
 
     // AdaptiveResidualMix (model.py:826-839): out = x + sigmoid(alpha)*sigmoid(W[x;z])*(z - x)
     void mix(const ConvW& c, float alpha, const void* x, const void* z, void* out, int B, int H, int W) {
         if (rc) return;
+        const KernelChoice ch = choose_mix(knobs, dtype, c, B, H, W, cus);
         ConvArgs a;
         base_args(a, c);
         a.in0 = x; a.in1 = z; a.out = out;
@@ -979,28 +1016,13 @@ struct Runner {
         a.p_out = a.cp_out * sz / 16;
         a.mix_scale = 1.0f / (1.0f + std::exp(-alpha));
         a.inv_mix_scale = inv_sigmoid(alpha);
-        const bool mix16 = c.packed16 != nullptr && knobs.mix16 &&
-                           (double)npix * c.cp0 * sz < 4294967296.0;  // 32-bit buffer offsets inside each tensor
-        int mix16b_wgs = knobs.persist > 0 ? knobs.persist : 0;  // persistent (also under MZ_NO_PERSIST=1: it has no per-tile form)
-        if (mix16b_wgs == 0) {
-            int dev = 0;
-            if (hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < kMaxDevices) mix16b_wgs = g_dev_cus[dev];
-        }
-        const bool mix16b = mix16 && knobs.mix16b && c.packed16r != nullptr && c.nchunks16 == 12 && mix16b_wgs > 0;  // C = 192
-        if (mix16) {  // 192-channel N tiles, x / z straight into MFMA operands (mix16_kernel / mix16b_kernel)
+        if (ch.s16) {  // 192-channel N tiles, x / z straight into MFMA operands (mix16_kernel / mix16b_kernel)
             a.ntiles = c.cout / 192;
-            a.wpk16 = mix16b ? c.packed16r : c.packed16;
+            a.wpk16 = ch.launcher == L_MIX16B ? c.packed16r : c.packed16;
             a.nchunks16 = c.nchunks16;
         }
-        pick_order(a, c, (double)npix * (c.cp0 + pad16(c.c1)) * sz, mix16 ? 32 : 64);
-        ProfRec* r;
-        prof_begin(r, 2.0 * (double)npix * c.cin * c.cout, (double)npix * 3.0 * c.cout * sz, 0);
-        if (r) { r->kind = 1; r->B = B; r->H = H; r->W = W; r->cin = c.cin; r->cout = c.cout; r->nt = c.nt; r->ntiles = a.ntiles; r->mtiles = a.mtiles; r->n_fast = a.gm * 1000 + a.gn; }
-        g_last_kernel = mix16b ? "mix16b" : (mix16 ? "mix16" : "conv_kernel_mix");
-        if (mix16b) check(launch_mix16b(dtype, a, s, mix16b_wgs), "mix16b launch");
-        else if (mix16) check(launch_mix16(dtype, a, s), "mix16 launch");
-        else check(launch_conv(dtype, MODE_GEMM1, c.nt, a, s), "mix launch");
-        prof_end(r);
+        pick_order(a, c, (double)npix * (c.cp0 + pad16(c.c1)) * sz, knobs, ch.s16 ? 32 : 64);
+        launch(ch, a, c.nt, prof_begin(1, a, c, 2.0 * (double)npix * c.cin * c.cout, (double)npix * 3.0 * c.cout * sz));
     }
 
     // PixelCrush (model.py:857-863, 881-882): conv 2x2 stride 2, floors odd sizes
@@ -1020,10 +1042,8 @@ struct Runner {
         a.cp_out = pad16(c.cout);
         a.p_out = a.cp_out * dtype_size(dtype) / 16;
         const double sz = dtype_size(dtype);
-        pick_order(a, c, (double)B * H * W * c.cp0 * sz, 64);
-        ProfRec* r;
-        prof_begin(r, 2.0 * (double)npix * 4.0 * c.cin * c.cout, ((double)B * H * W * c.cin + (double)npix * c.cout) * sz, 0);
-        if (r) { r->kind = 2; r->B = B; r->H = H; r->W = W; r->cin = c.cin; r->cout = c.cout; r->nt = c.nt; r->ntiles = a.ntiles; r->mtiles = a.mtiles; r->n_fast = a.gm * 1000 + a.gn; }
+        pick_order(a, c, (double)B * H * W * c.cp0 * sz, knobs, 64);
+        ProfRec* r = prof_begin(2, a, c, 2.0 * (double)npix * 4.0 * c.cin * c.cout, ((double)B * H * W * c.cin + (double)npix * c.cout) * sz);
         check(launch_conv(dtype, MODE_GEMM1, c.nt, a, s), "crush launch");
         prof_end(r);
     }
@@ -1043,7 +1063,7 @@ static int forward_micro(mz_handle* h, const char* x, char* out_sr, float* out_q
     auto block = [&](const BlockW& b, const void* xin, void* hid, void* z, void* yout, int hh, int ww) {
         // EncoderBlock / DecoderBlock (model.py:507-511): conv1 -> SiLU -> conv2 -> adaptive mix with the input
         run.conv3(b.conv1, xin, hid, nb, hh, ww, EPI_STORE, 1, 0, 0);
-        if (b.fused && run.wide_tiles && !run.no_fuse) {
+        if (fuse_mix(run.knobs, b)) {
             // conv2 + AdaptiveResidualMix in one launch (all output channels live in one workgroup)
             run.conv3(b.conv2, hid, yout, nb, hh, ww, EPI_FUSEDMIX, 0, 0, 0, nullptr, 0, 0, nullptr, &b.mixf, xin, b.alpha);
         } else {
@@ -1212,7 +1232,7 @@ extern "C" int mz_op_conv(int dtype, int kind, const void* in0, const void* in1,
     packed16r.p = c.packed16r;   // kind 3, C = 192: the second packing of the gate weights (mix16b_kernel)
     packed16t.p = c.packed16t;   // kind 0, one N tile of 33..48 channels: conv3t_kernel's packing
     if (rc) return rc;
-    // a throw-away handle carries the zero page / staging choice for Runner
+    // a throw-away handle carries the zero page and the knobs for Runner
     mz_handle fake;
     fake.zero_page = zero.p;
     fake.knobs = read_knobs();
@@ -1243,23 +1263,10 @@ extern "C" int mz_op_conv_mix(int dtype, const void* hid, const void* x, const f
     if (rc) return rc;
     if (!hid || !x || !w2_dev_f32 || !wmix_dev_f32 || !out) return fail(MZ_ERR_INVALID_ARGUMENT, "null argument");
     hipStream_t s = (hipStream_t)hip_stream;
-    ConvW c2;
-    plan_conv(c2, dtype, MODE_CONV3, cout, cin, 3, 3, OUT_PLAIN, SRC_PLAIN, 0, 0);
-    if (!(c2.ntiles == 1 && c2.nt <= 3)) return fail(MZ_ERR_INVALID_ARGUMENT, "the fused conv2 + mix needs all output channels in one N tile (cout <= 96)");
-    ConvW f;  // as plan_model()'s BlockW::mixf
-    f.cout = cout; f.cin = 2 * cout; f.kh = f.kw = 1;
-    f.mode = MODE_GEMM1; f.taps = 1;
-    f.nt = c2.nt; f.ntiles = 1;
-    f.out_map = OUT_PLAIN; f.in_map = SRC_MIXF;
-    f.c0 = cout; f.cp0 = pad16(cout); f.c1 = cout;
-    const int zg = dtype == DT_F32 ? 4 : 2;
-    f.nchunks = f.nchunks_real = f.cp0 / chunk_channels(dtype) + f.nt * zg;
-    f.packed_sz = packed_bytes(1, f.nt, 1, f.nchunks);
-    if (dtype != DT_F32) {
-        f.nchunks16 = (f.cp0 + 31) / 32 + f.nt;
-        f.packed16_sz = packed_bytes(1, 2 * f.nt, 1, f.nchunks16);
-        if (f.cp0 == 48) f.packed16t_sz = packed_bytes(1, 3, 1, 3);
-    }
+    BlockW b;
+    plan_block(b, dtype, cout, cin);
+    if (!b.fused) return fail(MZ_ERR_INVALID_ARGUMENT, "the fused conv2 + mix needs all output channels in one N tile (cout <= 96)");
+    ConvW &c2 = b.conv2, &f = b.mixf;
     TempBuf zero, p0, p1, p2, p3, p4, p5, p6;
     HIPCHK(hipMalloc(&zero.p, 4096));
     HIPCHK(hipMemsetAsync(zero.p, 0, 4096, s));
@@ -1381,6 +1388,57 @@ extern "C" int mz_debug_tile_list(int B, int tiles_y, int tiles_x, int ntiles, i
     const int n = (int)(t.size() / 2);
     for (int i = 0; i < n && i < cap; ++i) { out[2 * i] = t[2 * i]; out[2 * i + 1] = t[2 * i + 1]; }
     return n;
+}
+// Host-only (no GPU): the kernel family Runner::conv3 / Runner::mix would launch for one layer (ops: include/mewzoom_hip.h), with
+// ConvW planned as the model and the mz_op_* entries plan it and the knobs read from the environment as the mz_op_* entries read them.
+extern "C" const char* mz_debug_select(int dtype, int op, int cin, int cout, int B, int H, int W, int cus) {
+    if ((dtype != MZ_F32 && dtype != MZ_BF16 && dtype != MZ_F16) || cin < 1 || cout < 1 || B < 1 || H < 1 || W < 1 || cus < 0) {
+        fail(MZ_ERR_INVALID_ARGUMENT, "bad arguments");
+        return nullptr;
+    }
+    const Knobs k = read_knobs();
+    ConvW c;
+    BlockW b;
+    KernelChoice ch;
+    switch (op) {
+        case 0: case 1: case 4:  // conv1 + SiLU, plain 3x3, QA head
+            plan_conv(c, dtype, MODE_CONV3, cout, cin, 3, 3, OUT_PLAIN, SRC_PLAIN, 0, 0);
+            ch = choose_conv3(k, dtype, c, nullptr, EPI_STORE, op == 0, false, B, H, W, 0, 0, cus);
+            break;
+        case 2:  // SubpixelConv2d: 3x3 + PixelShuffle(2) into 2H x 2W
+            plan_conv(c, dtype, MODE_CONV3, cout, cin, 3, 3, OUT_D2S, SRC_PLAIN, 0, 0);
+            ch = choose_conv3(k, dtype, c, nullptr, EPI_D2S, 0, false, B, H, W, 2 * H, 2 * W, cus);
+            break;
+        case 3:  // image head
+            plan_conv(c, dtype, MODE_CONV3, cout, cin, 3, 3, OUT_FINAL, SRC_PLAIN, 0, 0);
+            ch = choose_conv3(k, dtype, c, nullptr, EPI_FINAL, 0, false, B, H, W, 2 * H, 2 * W, cus);
+            break;
+        case 5:  // FiLM conv (mz_op_conv_film)
+            if (dtype != DT_BF16 && dtype != DT_F16) {
+                fail(MZ_ERR_INVALID_ARGUMENT, "the FiLM epilogue is implemented for bf16 / fp16");
+                return nullptr;
+            }
+            plan_conv(c, dtype, MODE_CONV3, cout, cin, 3, 3, OUT_PLAIN, SRC_PLAIN, 0, 0);
+            ch = choose_conv3(k, dtype, c, nullptr, EPI_STORE, 0, true, B, H, W, 0, 0, cus);
+            break;
+        case 6:  // a block's conv2 (cin = the hidden channels), as forward runs it: with the mix fused, or alone
+            plan_block(b, dtype, cout, cin);
+            ch = fuse_mix(k, b) ? choose_conv3(k, dtype, b.conv2, &b.mixf, EPI_FUSEDMIX, 0, false, B, H, W, 0, 0, cus)
+                                : choose_conv3(k, dtype, b.conv2, nullptr, EPI_STORE, 0, false, B, H, W, 0, 0, cus);
+            break;
+        case 7:  // unfused AdaptiveResidualMix of cout channels (cin = 2 cout)
+            if (cin != 2 * cout) {
+                fail(MZ_ERR_INVALID_ARGUMENT, "a mix has cin = 2 cout");
+                return nullptr;
+            }
+            plan_conv(c, dtype, MODE_GEMM1, cout, cin, 1, 1, OUT_PLAIN, SRC_CONCAT, cout, cout);
+            ch = choose_mix(k, dtype, c, B, H, W, cus);
+            break;
+        default:
+            fail(MZ_ERR_INVALID_ARGUMENT, "bad op %d", op);
+            return nullptr;
+    }
+    return ch.name;
 }
 extern "C" const char* mz_version(void) { return "mewzoom_hip 0.1 (gfx950)"; }
 
