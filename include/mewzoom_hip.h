@@ -185,6 +185,15 @@ int mz_debug_tile_list(int B, int tiles_y, int tiles_x, int ntiles, int gm, int 
  * No reference counterpart. */
 const char* mz_debug_select(int dtype, int op, int cin, int cout, int B, int H, int W, int cus);
 
+/* Host-only (no GPU): one packing of one layer's weights as the library plans and packs it.  dtype, op, cin, cout as for
+ * mz_debug_select(), and op 8 = the gate weights of a block's mix, packed for the fused conv2 + mix (cin, cout: those of conv2).
+ * layout: 0 the 32x32-MFMA packing every layer has, 1 3x3 for conv3s / conv3r, 2 mix16, 3 conv3s's fused gate, 4 mix16b,
+ * 5 conv3r's fused gate, 6 3x3 for conv3t, 7 conv3t's fused gate (PackLayout, ultrazoom_amd/csrc/mz_kernels.h).  Element i of the
+ * packing holds weight out[i] of the float32 [cout][cin][kh][kw] tensor, -1 = a zero of the padding; at most `cap` entries are
+ * written.  Returns the number of elements, negative where the layer does not have that packing (mz_last_error() says so) or on bad
+ * arguments.  No reference counterpart. */
+long long mz_debug_pack(int dtype, int op, int cin, int cout, int layout, long long* out, long long cap);
+
 /* Hardware probe (ultrazoom_amd/csrc/mz_probe.hip; tests/test_store_hazard_gpu.py): on every CU, 16-byte buffer stores each followed --
  * `wait_states` (0, 1, 2) wait states later -- by a vector instruction that overwrites data register `dword` (0..3) of the store:
  * follower 0 v_mov_b32, 1 v_mul_f32, 2 v_cvt_pk_bf16_f32, 3 v_exp_f32, 4 v_pk_mul_f32, 5 v_mfma_f32_16x16x32_bf16;

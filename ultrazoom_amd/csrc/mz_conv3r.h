@@ -557,7 +557,7 @@ __global__ __launch_bounds__(512) void conv3r_kernel(const ConvArgs a) {
     //   A: x (the block input, a.in1) arrives in ACCUMULATOR layout, 8 bytes per channel fragment and lane; z is rounded to the
     //      storage type and packed into MFMA B operands (two 16-channel accumulator fragments = one 32-wide K step);
     //   C: gate beta = Wx.x + Wz.z on the MFMA: both halves of the gate weights are packed in accumulator-row order
-    //      (PackArgs::frag16 = 2), so a pair of x fragments IS a B operand too -- x is fetched once; the 36 KB of gate weights
+    //      (PK_GATE16R), so a pair of x fragments IS a B operand too -- x is fetched once; the 36 KB of gate weights
     //      stay in LDS for the whole launch;
     //   D: blend x + sigmoid(alpha) sigmoid(beta) (z - x) into the accumulator registers, then the three entries as usual.
     // The arithmetic is conv3s_kernel<.., FUSE>'s, operation for operation, EXCEPT the summation order of the x half of the gate inside a

@@ -21,7 +21,7 @@
 //     after v_permlane16_swap lane row g holds plane 4 + (g >> 1) of pixel fragment 2 k + (g & 1).  18 entries per wave and tile.
 //   * EPI_FUSEDMIX: per pixel fragment a "unit": z rounded to the storage type and packed; gate GEMM beta = W [x ; z] as three K steps
 //     of two 16-channel fragments each in accumulator-row order -- (x0, x1), (x2, z0), (z1, z2): x arrives in accumulator layout, so
-//     pairs of fragments ARE B operands as they stand (gate weights packed to match, PackArgs::frag16 = 4) --; blend; entries.  The
+//     pairs of fragments ARE B operands as they stand (gate weights packed to match, PK_GATE16T) --; blend; entries.  The
 //     x of a step's units is requested in the step BEFORE, ahead of that step's LDS-DMA: the step's closing vmcnt wait covers it and
 //     no unit ever waits for HBM.  Twelve units over the tile's first three chunks (three chunks: 0 + 2 + 2, 1 + 1 + 2, 1 + 1 + 2
 //     per step) or six (0 + 1 + 1 per chunk: the steps that carry the halo DMA stay free).

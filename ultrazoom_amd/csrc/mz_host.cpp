@@ -17,7 +17,7 @@
 #include <vector>
 
 #include "../../include/mewzoom_hip.h"
-#include "mz_kernels.h"
+#include "mz_pack.h"
 
 using namespace mz;
 
@@ -94,6 +94,20 @@ static Knobs read_knobs() {
 // ------------------------------------------------------------------------------------------------
 // model description
 // ------------------------------------------------------------------------------------------------
+// A device allocation that frees itself.
+struct DevBuf {
+    void* p = nullptr;
+    DevBuf() = default;
+    DevBuf(DevBuf&& o) noexcept : p(o.p) { o.p = nullptr; }
+    DevBuf& operator=(DevBuf&& o) noexcept { std::swap(p, o.p); return *this; }
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    ~DevBuf() {
+        if (p) (void)hipFree(p);
+    }
+    hipError_t alloc(size_t bytes) { return p ? hipSuccess : hipMalloc(&p, bytes); }  // once: a weight set again is packed in place
+};
+
 struct ConvW {
     // logical (reference) shape
     int cout = 0, cin = 0, kh = 0, kw = 0;
@@ -102,18 +116,31 @@ struct ConvW {
     int out_map = OUT_PLAIN, cq = 0, cq_p = 0;
     int in_map = SRC_PLAIN, c0 = 0, cp0 = 0, c1 = 0;
     int n_logical_padded = 0;
-    void* packed = nullptr;
-    size_t packed_sz = 0;
-    // second packing for the 16x16x32-MFMA kernel (16-bit types, wide 3x3 convs that are not the image head)
-    void* packed16 = nullptr;
-    size_t packed16_sz = 0;
-    int nchunks16 = 0;
-    void* packed16r = nullptr;  // fused gate weights once more, both halves in accumulator-row order (conv3r_kernel; PackArgs::frag16 = 2)
-    void* packed16t = nullptr;  // conv3t_kernel (one N tile of <= 48 channels): three 16-channel fragments per tap; SRC_MIXF: its gate (frag16 = 4)
-    size_t packed16t_sz = 0;
-    int nchunks16t = 0;
+    int nchunks32 = 0;     // 32-channel chunks of in0: the K steps of the 16x16x32 kernels over cp0
+    unsigned layouts = 0;  // the planned packings, one bit per PackLayout
+    DevBuf packed[PK_COUNT];
     bool set = false;
+    bool has(int layout) const { return layouts >> layout & 1u; }
 };
+
+// One packing of a layer: fragments per tap and N tile, N tiles, K chunks (PackArgs; ConvArgs::nchunks16 of the 16-bit layouts)
+struct PackShape {
+    int frags, ntiles, nchunks;
+};
+static PackShape pack_shape(const ConvW& c, int layout) {
+    switch (layout) {
+        case PK_MAIN: return {c.nt, c.ntiles, c.nchunks};
+        case PK_CONV16: return {2 * c.nt, c.ntiles, c.nchunks32};
+        case PK_MIX16: case PK_MIX16B: return {12, c.cout / 192, 2 * c.cout / 32};  // 192-channel N tiles over [x ; z]
+        case PK_GATE16: case PK_GATE16R: return {2 * c.nt, 1, c.nchunks32 + c.nt};   // x K steps, then one per pair of z fragments
+        case PK_CONV16T: return {3, 1, c.nchunks32};
+        default: return {3, 1, 3};  // PK_GATE16T: three K steps x three fragments
+    }
+}
+static size_t pack_bytes(const ConvW& c, int layout) {
+    const PackShape sh = pack_shape(c, layout);
+    return packed_bytes(c.taps, sh.frags, sh.ntiles, sh.nchunks);
+}
 
 static void plan_conv(ConvW& c, int dtype, int mode, int cout, int cin, int kh, int kw, int out_map, int in_map,
                       int c0, int c1) {
@@ -149,20 +176,18 @@ static void plan_conv(ConvW& c, int dtype, int mode, int cout, int cin, int kh, 
         const int S = gemm1_chunks_per_stage();
         c.nchunks = (c.nchunks + S - 1) / S * S;
     }
-    c.packed_sz = packed_bytes(c.taps, c.nt, c.ntiles, c.nchunks);
-    if (mode == MODE_CONV3 && dtype != DT_F32 && in_map == SRC_PLAIN && out_map != OUT_FINAL && c.nt <= 3) {
-        c.nchunks16 = (c.cp0 + 31) / 32;
-        c.packed16_sz = packed_bytes(c.taps, 2 * c.nt, c.ntiles, c.nchunks16);
-    }
-    // one N tile of 33..48 channels over whole 32-channel chunks: third packing, for conv3t_kernel (three fragments per tap)
-    if (mode == MODE_CONV3 && dtype != DT_F32 && in_map == SRC_PLAIN && out_map == OUT_PLAIN && c.n_logical_padded == 48 && c.cp0 % 32 == 0) {
-        c.nchunks16t = c.cp0 / 32;
-        c.packed16t_sz = packed_bytes(c.taps, 3, 1, c.nchunks16t);
-    }
-    // AdaptiveResidualMix with C = k * 192: second packing for mix16_kernel (192-channel N tiles = 12 fragments of 16)
-    if (mode == MODE_GEMM1 && dtype != DT_F32 && in_map == SRC_CONCAT && cout % 192 == 0 && c0 == cout && c1 == cout) {
-        c.nchunks16 = 2 * cout / 32;
-        c.packed16_sz = packed_bytes(1, 12, cout / 192, c.nchunks16);
+    c.nchunks32 = (c.cp0 + 31) / 32;
+    c.layouts = 1u << PK_MAIN;
+    const bool s16 = dtype != DT_F32;
+    // wide 3x3 convolutions that are not the image head: the 16x16x32 kernels
+    if (mode == MODE_CONV3 && s16 && in_map == SRC_PLAIN && out_map != OUT_FINAL && c.nt <= 3) c.layouts |= 1u << PK_CONV16;
+    // one N tile of 33..48 channels over whole 32-channel chunks: conv3t_kernel
+    if (mode == MODE_CONV3 && s16 && in_map == SRC_PLAIN && out_map == OUT_PLAIN && c.n_logical_padded == 48 && c.cp0 % 32 == 0)
+        c.layouts |= 1u << PK_CONV16T;
+    // AdaptiveResidualMix with C = k * 192: mix16_kernel; C = 192: mix16b_kernel too
+    if (mode == MODE_GEMM1 && s16 && in_map == SRC_CONCAT && cout % 192 == 0 && c0 == cout && c1 == cout) {
+        c.layouts |= 1u << PK_MIX16;
+        if (cout == 192) c.layouts |= 1u << PK_MIX16B;
     }
 }
 
@@ -205,10 +230,10 @@ struct mz_handle {
     bool skip_alpha_set[3] = {false, false, false};
     std::vector<std::unique_ptr<ConvW>> head_up;
     ConvW qa_conv;
-    float* stem_w4 = nullptr;  // [cp0][4]
-    float* qa_bias = nullptr;  // [F]
+    DevBuf stem_w4;  // float [cp0][4]
+    DevBuf qa_bias;  // float [F]
     bool stem_w_set = false, stem_b_set = false, qa_b_set = false;
-    void* zero_page = nullptr;
+    DevBuf zero_page;
     std::vector<Slot> slots;
     std::unordered_map<std::string, int> slot_index;
     bool device_ready = false;
@@ -218,11 +243,7 @@ struct mz_handle {
     std::vector<ProfRec> recs;
     size_t recs_used = 0;
     // tile lists of the role-alternating kernels (Runner::tile_table): one per launch geometry, built on first use
-    std::map<std::vector<int>, std::pair<void*, int>> tile_tabs;
-    ~mz_handle() {
-        for (auto& t : tile_tabs)
-            if (t.second.first) (void)hipFree(t.second.first);
-    }
+    std::map<std::vector<int>, std::pair<DevBuf, int>> tile_tabs;
 };
 
 static void add_slot(mz_handle* h, const std::string& name, int kind, std::initializer_list<int64_t> shape) {
@@ -246,11 +267,12 @@ static void plan_mixf(ConvW& f, int dtype, const ConvW& conv2) {
     f.c0 = c; f.cp0 = pad16(c); f.c1 = c;
     const int zg = dtype == DT_F32 ? 4 : 2;
     f.nchunks = f.nchunks_real = f.cp0 / chunk_channels(dtype) + f.nt * zg;
-    f.packed_sz = packed_bytes(1, f.nt, 1, f.nchunks);
-    if (dtype != DT_F32) {  // second packing for the fused epilogue of the 16x16x32 kernel: 2 nt K-steps x 2 nt fragments
-        f.nchunks16 = (f.cp0 + 31) / 32 + f.nt;
-        f.packed16_sz = packed_bytes(1, 2 * f.nt, 1, f.nchunks16);
-        if (f.cp0 == 48) f.packed16t_sz = packed_bytes(1, 3, 1, 3);  // conv3t_kernel's gate: three K steps x three fragments
+    f.nchunks32 = (f.cp0 + 31) / 32;
+    f.layouts = 1u << PK_MAIN;
+    if (dtype != DT_F32) {  // the fused epilogues of the 16x16x32 kernels: conv3s, conv3r (three fragments), conv3t (48 channels)
+        f.layouts |= 1u << PK_GATE16;
+        if (f.nt == 3) f.layouts |= 1u << PK_GATE16R;
+        if (f.cp0 == 48) f.layouts |= 1u << PK_GATE16T;
     }
 }
 
@@ -372,26 +394,8 @@ extern "C" int mz_create(const mz_config* cfg, int dtype, mz_handle** out) {
     return MZ_OK;
 }
 
-static void free_conv(ConvW& c) {
-    if (c.packed) (void)hipFree(c.packed);
-    c.packed = nullptr;
-    if (c.packed16) (void)hipFree(c.packed16);
-    c.packed16 = nullptr;
-    if (c.packed16r) (void)hipFree(c.packed16r);
-    c.packed16r = nullptr;
-    if (c.packed16t) (void)hipFree(c.packed16t);
-    c.packed16t = nullptr;
-}
-
 extern "C" int mz_destroy(mz_handle* h) {
     if (!h) return MZ_OK;
-    for (auto& s : h->slots) {
-        if (s.kind == SK_CONV && s.conv) free_conv(*s.conv);
-        if (s.kind == SK_CONV && s.block && s.conv == &s.block->mix) free_conv(s.block->mixf);
-    }
-    if (h->stem_w4) (void)hipFree(h->stem_w4);
-    if (h->qa_bias) (void)hipFree(h->qa_bias);
-    if (h->zero_page) (void)hipFree(h->zero_page);
     for (auto& r : h->recs) {
         (void)hipEventDestroy(r.a);
         (void)hipEventDestroy(r.b);
@@ -417,48 +421,33 @@ static int prepare_device(mz_handle* h, hipStream_t st) {
     if (rc) return rc;
     // zero fills go to the CALLER's stream, like every later use of these buffers (a blocking memset on the NULL stream
     // is not ordered with work on a non-blocking stream)
-    HIPCHK(hipMalloc(&h->zero_page, 4096));
-    HIPCHK(hipMemsetAsync(h->zero_page, 0, 4096, st));
+    HIPCHK(h->zero_page.alloc(4096));
+    HIPCHK(hipMemsetAsync(h->zero_page.p, 0, 4096, st));
     const int cp0 = pad16(h->ch[0]);
-    HIPCHK(hipMalloc((void**)&h->stem_w4, sizeof(float) * 4 * cp0));
-    HIPCHK(hipMemsetAsync(h->stem_w4, 0, sizeof(float) * 4 * cp0, st));
-    HIPCHK(hipMalloc((void**)&h->qa_bias, sizeof(float) * std::max(1, h->cfg.num_deg_features)));
+    HIPCHK(h->stem_w4.alloc(sizeof(float) * 4 * cp0));
+    HIPCHK(hipMemsetAsync(h->stem_w4.p, 0, sizeof(float) * 4 * cp0, st));
+    HIPCHK(h->qa_bias.alloc(sizeof(float) * std::max(1, h->cfg.num_deg_features)));
     h->device_ready = true;
     return MZ_OK;
 }
 
-static int pack_conv(ConvW& c, int dtype, const float* w_dev, hipStream_t s) {
-    if (!c.packed) HIPCHK(hipMalloc(&c.packed, c.packed_sz));
+static PackArgs pack_args(const ConvW& c, int layout, int dtype, const float* w_dev, void* dst) {
+    const PackShape sh = pack_shape(c, layout);
     PackArgs p;
-    p.w = w_dev; p.dst = c.packed; p.dtype = dtype;
+    p.w = w_dev; p.dst = dst; p.dtype = dtype; p.layout = layout;
     p.cout = c.cout; p.cin = c.cin; p.kh = c.kh; p.kw = c.kw;
-    p.taps = c.taps; p.nt = c.nt; p.ntiles = c.ntiles; p.nchunks = c.nchunks;
+    p.taps = c.taps; p.frags = sh.frags; p.ntiles = sh.ntiles; p.nchunks = sh.nchunks;
     p.out_map = c.out_map; p.cq = c.cq; p.cq_p = c.cq_p;
     p.in_map = c.in_map; p.c0 = c.c0; p.cp0 = c.cp0; p.c1 = c.c1;
-    p.frag16 = 0; p.nfr = 0;
-    HIPCHK(launch_pack(p, s));
-    if (c.packed16_sz) {
-        if (!c.packed16) HIPCHK(hipMalloc(&c.packed16, c.packed16_sz));
-        p.dst = c.packed16; p.frag16 = 1; p.nchunks = c.nchunks16;
-        if (c.in_map == SRC_CONCAT) { p.nt = 6; p.ntiles = c.cout / 192; }  // mix16_kernel: 12 fragments per K step
-        HIPCHK(launch_pack(p, s));
-        if (c.in_map == SRC_CONCAT && c.nchunks16 == 12) {  // C = 192, mix16b_kernel: rows in B-operand order, own channels first
-            if (!c.packed16r) HIPCHK(hipMalloc(&c.packed16r, c.packed16_sz));
-            p.dst = c.packed16r; p.frag16 = 3;
-            HIPCHK(launch_pack(p, s));
-        }
-        if (c.in_map == SRC_MIXF && c.nt == 3) {
-            if (!c.packed16r) HIPCHK(hipMalloc(&c.packed16r, c.packed16_sz));
-            p.dst = c.packed16r; p.frag16 = 2;
-            HIPCHK(launch_pack(p, s));
-        }
-    }
-    if (c.packed16t_sz) {  // conv3t_kernel: three 16-channel fragments per tap (its gate: PackArgs::frag16 = 4)
-        if (!c.packed16t) HIPCHK(hipMalloc(&c.packed16t, c.packed16t_sz));
-        p.dst = c.packed16t; p.nt = c.nt; p.ntiles = 1; p.nfr = 3;
-        if (c.in_map == SRC_MIXF) { p.frag16 = 4; p.nchunks = 3; }
-        else { p.frag16 = 1; p.nchunks = c.nchunks16t; }
-        HIPCHK(launch_pack(p, s));
+    return p;
+}
+
+// every planned packing, in PackLayout order
+static int pack_conv(ConvW& c, int dtype, const float* w_dev, hipStream_t s) {
+    for (int l = 0; l < PK_COUNT; ++l) {
+        if (!c.has(l)) continue;
+        HIPCHK(c.packed[l].alloc(pack_bytes(c, l)));
+        HIPCHK(launch_pack(pack_args(c, l, dtype, w_dev, c.packed[l].p), s));
     }
     c.set = true;
     return MZ_OK;
@@ -494,15 +483,15 @@ extern "C" int mz_set_weight(mz_handle* h, const char* name, const float* dev_f3
             return MZ_OK;
         }
         case SK_STEM_W:
-            HIPCHK(launch_pack_stem(dev_f32, nullptr, h->stem_w4, h->ch[0], pad16(h->ch[0]), st));
+            HIPCHK(launch_pack_stem(dev_f32, nullptr, (float*)h->stem_w4.p, h->ch[0], pad16(h->ch[0]), st));
             h->stem_w_set = true;
             return MZ_OK;
         case SK_STEM_B:
-            HIPCHK(launch_pack_stem(nullptr, dev_f32, h->stem_w4, h->ch[0], pad16(h->ch[0]), st));
+            HIPCHK(launch_pack_stem(nullptr, dev_f32, (float*)h->stem_w4.p, h->ch[0], pad16(h->ch[0]), st));
             h->stem_b_set = true;
             return MZ_OK;
         case SK_QA_B:
-            HIPCHK(hipMemcpyAsync(h->qa_bias, dev_f32, sizeof(float) * h->cfg.num_deg_features, hipMemcpyDeviceToDevice, st));
+            HIPCHK(hipMemcpyAsync(h->qa_bias.p, dev_f32, sizeof(float) * h->cfg.num_deg_features, hipMemcpyDeviceToDevice, st));
             h->qa_b_set = true;
             return MZ_OK;
     }
@@ -655,7 +644,7 @@ static void tile_list(const ConvArgs& a, int th, int tw, std::vector<uint32_t>& 
 // through the XCD's L2; per group the activations are re-read ntiles/gn times and the weights mtiles/gm times in total.  Picks the shape
 // with the least total re-read traffic and sets the walk of a (a.mtiles, a.ntiles, a.tiles_x, a.tiles_y set): a.grid and its divisors.
 static void pick_order(ConvArgs& a, const ConvW& c, double act_bytes, const Knobs& k, int resident_per_xcd = 32) {
-    const double W = (double)c.packed_sz, A = act_bytes;
+    const double W = (double)pack_bytes(c, PK_MAIN), A = act_bytes;
     int best_gm = a.mtiles, best_gn = 1;
     double best = 1e300;
     for (int gn = 1; gn <= a.ntiles; ++gn) {
@@ -686,7 +675,7 @@ static void pick_order(ConvArgs& a, const ConvW& c, double act_bytes, const Knob
 }
 
 // ------------------------------------------------------------------------------------------------
-// kernel selection: which kernel runs a 3x3 convolution or a mix, in which geometry.  Functions of the plan (ConvW sizes, never
+// kernel selection: which kernel runs a 3x3 convolution or a mix, in which geometry.  Functions of the plan (ConvW::has(), never
 // whether a buffer happens to be allocated), the knobs, the shape and the CU count only -- no HIP call: mz_debug_select() runs them
 // without a GPU, and tests/test_select_cpu.py pins their table.
 // ------------------------------------------------------------------------------------------------
@@ -700,7 +689,8 @@ struct KernelChoice {
     int th = 0, tw = 0;          // 3x3: pixel tile
     int geo = 0;                 // conv3r_kernel: 1 = 8 x 40 tiles
     int ragged_planes = 0;       // conv3r_kernel's ragged variant (Cin = 48)
-    bool s16 = false;            // the 16x16x32-MFMA packing (ConvW::packed16 / packed16r / packed16t)
+    int layout = PK_MAIN;        // the packing the kernel reads; any other than PK_MAIN: a 16x16x32-MFMA kernel (ConvArgs::wpk16)
+    int gate = PK_MAIN;          // EPI_FUSEDMIX on those: the packing of the gate weights (ConvArgs::wmix16)
     bool tile_list = false;      // walks a tile table (conv3r / conv3t, Runner::tile_table)
     int persist = 0;             // persistent workgroups at most; 0 = one workgroup per tile
 };
@@ -711,11 +701,6 @@ static int persistent_workgroups(const Knobs& k, int cus) { return k.persist >= 
 
 // 32-bit buffer offsets: `planes` 16-byte channel planes of `pixels` pixels stay below 4 GiB
 static bool offsets_fit(double planes, double pixels) { return planes * pixels * 16.0 < 4294967296.0; }
-
-// the gate weights in accumulator-row order (ConvW::packed16r): exactly where pack_conv() packs them
-static bool has_packed16r(const ConvW& c) {
-    return c.packed16_sz > 0 && ((c.in_map == SRC_MIXF && c.nt == 3) || (c.in_map == SRC_CONCAT && c.nchunks16 == 12));
-}
 
 // conv2 + AdaptiveResidualMix of a block in one launch: all output channels in one workgroup (BlockW::fused), on the 512-pixel kernels
 static bool fuse_mix(const Knobs& k, const BlockW& b) { return b.fused && k.wide && k.fuse; }
@@ -744,13 +729,14 @@ static KernelChoice choose_conv3(const Knobs& k, int dtype, const ConvW& c, cons
     // what every 16x16x32-MFMA kernel needs: a 16-bit type, a persistent launch
     const bool s16 = k.s16 && dtype != DT_F32 && wgs > 0;
     // ... and (all but conv3t) padding K to whole 32-channel chunks only where that wastes less than the shape gains (~12 %)
-    const bool k_fits = c.nchunks16 * 32 * 100 <= c.cp0 * (100 + k.kpad_pct);
+    const bool k_fits = c.nchunks32 * 32 * 100 <= c.cp0 * (100 + k.kpad_pct);
     const bool halo_fits = offsets_fit(4, px);  // 32-bit halo offsets span four planes
     const int p0 = c.cp0 * dtype_size(dtype) / 16;
     // conv3r / conv3t walk a tile list whose entries hold image, N tile and pixel coordinates in 16 bits each
-    auto listed = [&](const char* name, int launcher, int lth, int ltw) {
+    auto listed = [&](const char* name, int launcher, int lth, int ltw, int layout, int gate) {
         ch.name = name; ch.launcher = launcher; ch.th = lth; ch.tw = ltw;
-        ch.s16 = ch.tile_list = true;
+        ch.layout = layout; ch.gate = gate;
+        ch.tile_list = true;
         ch.persist = wgs;
         if (B >= 65536 || c.ntiles >= 65536 || (H + lth - 1) / lth * lth >= 65536 || (W + ltw - 1) / ltw * ltw >= 65536) {
             fail(MZ_ERR_INVALID_ARGUMENT, "tile table: image, batch or N-tile index beyond 16 bits");
@@ -763,18 +749,18 @@ static KernelChoice choose_conv3(const Knobs& k, int dtype, const ConvW& c, cons
     // and more of them; 12 x 64 pixel tiles; stores and x loads carry 32-bit offsets inside six planes.  The choice depends on channel
     // counts only (never on H or W): its fused variant sums the gate in another order than conv3s_kernel<.., FUSE> -- equal to <= 1 ulp,
     // not bit for bit --, and a tile of upscale_tiled() must run the kernel the whole image runs.
-    const bool t_fuse = epi == EPI_FUSEDMIX && k.fuse16 && mixf && mixf->packed16t_sz > 0;
-    if (k.t && s16 && !film && c.packed16t_sz > 0 && c.ntiles == 1 && (c.nchunks16t == 3 || c.nchunks16t >= 6) &&
+    const bool t_fuse = epi == EPI_FUSEDMIX && k.fuse16 && mixf && mixf->has(PK_GATE16T);
+    if (k.t && s16 && !film && c.has(PK_CONV16T) && c.ntiles == 1 && (c.nchunks32 == 3 || c.nchunks32 >= 6) &&
         (epi == EPI_STORE || t_fuse) && halo_fits && offsets_fit(6, px))
-        return listed(t_fuse ? "conv3t_fused" : "conv3t", L_CONV3T, 12, 64);
+        return listed(t_fuse ? "conv3t_fused" : "conv3t", L_CONV3T, 12, 64, PK_CONV16T, t_fuse ? PK_GATE16T : PK_MAIN);
 
     // conv3r_kernel's ragged variant: conv1 + SiLU with Cin = 48 (two 32-channel chunks, the second with two real planes) into 96-channel
     // N tiles.  The kernel it replaces (conv3p_kernel: 32x32x16 MFMA, exact 16-channel chunks) sums in another order, so the choice
     // depends on channel counts, dtype and knobs only -- never on H or W.
-    if (k.r && k.r2 && s16 && !film && c.nt == 3 && c.packed16_sz > 0 && epi == EPI_STORE && silu && c.nchunks16 == 2 && c.cp0 == 48 &&
+    if (k.r && k.r2 && s16 && !film && c.nt == 3 && c.has(PK_CONV16) && epi == EPI_STORE && silu && c.nchunks32 == 2 && c.cp0 == 48 &&
         halo_fits && offsets_fit(12, px)) {
         ch.ragged_planes = (c.cp0 - 32) / 8;
-        return listed("conv3r_ragged", L_CONV3R, 8, 48);
+        return listed("conv3r_ragged", L_CONV3R, 8, 48, PK_CONV16, PK_MAIN);
     }
 
     // conv3r_kernel's fused variant (conv2 + AdaptiveResidualMix, C = 96): six or more chunks (one pixel fragment's gate GEMM and blend
@@ -782,17 +768,17 @@ static KernelChoice choose_conv3(const Knobs& k, int dtype, const ConvW& c, cons
     // kernel and conv3s_kernel<.., FUSE> sum the x half of the gate in different orders inside a 32-wide K step -- equal to <= 1 ulp, not
     // bit for bit -- and a tile of upscale_tiled() must run the kernel the whole image runs, or "tiled == untiled bit for bit"
     // (ultrazoom_amd/tiling.py) breaks.
-    if (k.r && k.fuse16 && epi == EPI_FUSEDMIX && s16 && c.nt == 3 && c.ntiles == 1 && c.packed16_sz > 0 && mixf && has_packed16r(*mixf) &&
-        (mixf->cp0 + 31) / 32 == c.nt && c.nchunks16 >= 6 && p0 % 4 == 0 && k_fits && halo_fits && offsets_fit(12, px))
-        return listed("conv3r_fused", L_CONV3R, 8, 48);
+    if (k.r && k.fuse16 && epi == EPI_FUSEDMIX && s16 && c.nt == 3 && c.ntiles == 1 && c.has(PK_CONV16) && mixf && mixf->has(PK_GATE16R) &&
+        mixf->nchunks32 == c.nt && c.nchunks32 >= 6 && p0 % 4 == 0 && k_fits && halo_fits && offsets_fit(12, px))
+        return listed("conv3r_fused", L_CONV3R, 8, 48, PK_CONV16, PK_GATE16R);
 
     // conv3r_kernel: 96-channel N tiles, any chunk count >= 3 of four whole planes (its halo loads carry the plane in the scalar offset,
     // which the hardware's range check does not cover); its stores carry 32-bit offsets inside 12 output planes / one D2S target image.
     // Its tiles are 8 x 48, or 8 x 40 (five pixel fragments per wave: widths like 120 that 48 does not divide) where those pad fewer
     // pixels, and it runs where they pad no more than the better of the 8 x 64 / 16 x 32 tiles.  (The plain variants accumulate in the
     // same order as conv3s_kernel whatever the tile shape: bit-identical, so this choice may follow H and W.)
-    if (k.r && s16 && !film && c.nt == 3 && c.packed16_sz > 0 && (epi == EPI_STORE || epi == EPI_D2S) && k_fits && halo_fits &&
-        c.nchunks16 >= 3 && p0 % 4 == 0 &&
+    if (k.r && s16 && !film && c.nt == 3 && c.has(PK_CONV16) && (epi == EPI_STORE || epi == EPI_D2S) && k_fits && halo_fits &&
+        c.nchunks32 >= 3 && p0 % 4 == 0 &&
         (epi == EPI_D2S ? offsets_fit(c.cq_p * dtype_size(dtype) / 16, (double)Hout * Wout) : offsets_fit(12, px))) {
         const long long rows8 = (long long)((H + 7) / 8 * 8);
         const long long pad48 = rows8 * ((W + 47) / 48 * 48), pad40 = rows8 * ((W + 39) / 40 * 40);
@@ -800,23 +786,24 @@ static KernelChoice choose_conv3(const Knobs& k, int dtype, const ConvW& c, cons
         const int geo = pad40 < pad48 ? 1 : 0;
         if ((geo ? pad40 : pad48) <= pads) {
             ch.geo = geo;
-            return listed(geo ? "conv3r_8x40" : "conv3r", L_CONV3R, 8, geo ? 40 : 48);
+            return listed(geo ? "conv3r_8x40" : "conv3r", L_CONV3R, 8, geo ? 40 : 48, PK_CONV16, PK_MAIN);
         }
     }
 
     // the 512-pixel kernels (per tile: conv3w; persistent: conv3p, or conv3s on the 16x16x32 MFMA) and the 256-pixel conv_kernel
     ch.th = th; ch.tw = tw;
     const bool fused = epi == EPI_FUSEDMIX;
-    const bool fuse16 = fused && mixf && mixf->packed16_sz > 0 && k.fuse16 &&
-                        (mixf->cp0 + 31) / 32 == c.nt;  // x K-steps == z K-steps (always so for C <= 96)
+    const bool fuse16 = fused && mixf && mixf->has(PK_GATE16) && k.fuse16 &&
+                        mixf->nchunks32 == c.nt;  // x K-steps == z K-steps (always so for C <= 96)
     if (mode != MODE_CONV3 && (epi == EPI_STORE || epi == EPI_D2S || fuse16) && wgs > 0) {
         ConvArgs g;  // the per-tile grid
         memset(&g, 0, sizeof(g));
         g.tiles_x = (W + tw - 1) / tw; g.tiles_y = (H + th - 1) / th;
         g.mtiles = B * g.tiles_x * g.tiles_y; g.ntiles = c.ntiles;
         pick_order(g, c, (double)B * H * W * c.cp0 * (double)dtype_size(dtype), k);
-        if (s16 && c.packed16_sz > 0 && k_fits && halo_fits) {  // conv3s: 32-bit halo offsets span four planes
-            ch.s16 = true;
+        if (s16 && c.has(PK_CONV16) && k_fits && halo_fits) {  // conv3s: 32-bit halo offsets span four planes
+            ch.layout = PK_CONV16;
+            ch.gate = fused ? PK_GATE16 : PK_MAIN;
             ch.persist = wgs;
         } else if (g.grid > wgs && offsets_fit(2, px)) {
             // conv3p_kernel: 32-bit halo offsets span the two planes of a 16-channel stage; larger images stay on the per-tile
@@ -824,14 +811,14 @@ static KernelChoice choose_conv3(const Knobs& k, int dtype, const ConvW& c, cons
             ch.persist = wgs;
         }
     }
-    if (film && !ch.s16) {
+    if (film && ch.layout == PK_MAIN) {
         fail(MZ_ERR_INVALID_ARGUMENT, "the FiLM epilogue exists on the 16x16x32 kernel only: bf16 / fp16, at most 96 output channels per "
                                       "N tile, input channels within 12.5 %% of a multiple of 32");
         return ch;
     }
     ch.launcher = L_CONV;
     ch.name = mode == MODE_CONV3 ? "conv_kernel"
-              : ch.persist > 0  ? (ch.s16 ? (fused ? "conv3s_fused" : "conv3s") : "conv3p")
+              : ch.persist > 0  ? (ch.layout != PK_MAIN ? (fused ? "conv3s_fused" : "conv3s") : "conv3p")
                                 : (fused ? "conv3w_fused" : "conv3w");
     return ch;
 }
@@ -842,12 +829,12 @@ static KernelChoice choose_mix(const Knobs& k, int dtype, const ConvW& c, int B,
     ch.mode = MODE_GEMM1;
     // mix16_kernel: C = k * 192 (192-channel N tiles, x / z straight into MFMA operands), 32-bit buffer offsets inside each tensor;
     // mix16b_kernel (C = 192) is persistent, also under MZ_NO_PERSIST=1: it has no per-tile form
-    const bool mix16 = c.packed16_sz > 0 && offsets_fit(c.cp0 * dtype_size(dtype) / 16.0, (double)B * H * W);
+    const bool mix16 = c.has(PK_MIX16) && offsets_fit(c.cp0 * dtype_size(dtype) / 16.0, (double)B * H * W);
     const int wgs = k.persist > 0 ? k.persist : cus;
-    if (mix16 && k.mix16b && has_packed16r(c) && c.nchunks16 == 12 && wgs > 0) {
-        ch.name = "mix16b"; ch.launcher = L_MIX16B; ch.s16 = true; ch.persist = wgs;
+    if (mix16 && k.mix16b && c.has(PK_MIX16B) && wgs > 0) {
+        ch.name = "mix16b"; ch.launcher = L_MIX16B; ch.layout = PK_MIX16B; ch.persist = wgs;
     } else if (mix16) {
-        ch.name = "mix16"; ch.launcher = L_MIX16; ch.s16 = true;
+        ch.name = "mix16"; ch.launcher = L_MIX16; ch.layout = PK_MIX16;
     } else {
         ch.name = "conv_kernel_mix"; ch.launcher = L_CONV;
     }
@@ -891,8 +878,8 @@ struct Runner {
 
     void base_args(ConvArgs& a, const ConvW& c) {
         memset(&a, 0, sizeof(a));
-        a.wpk = c.packed;
-        a.zero = h ? h->zero_page : nullptr;
+        a.wpk = c.packed[PK_MAIN].p;
+        a.zero = h ? h->zero_page.p : nullptr;
         a.dbg = debug_buffer();
         a.nchunks = c.nchunks;
         a.nchunks_real = c.nchunks_real;
@@ -916,12 +903,12 @@ struct Runner {
             tile_list(a, th, tw, t);
             const int n = (int)(t.size() / 2);
             t.resize(t.size() + 2 * (size_t)pad, 0u);
-            void* d = nullptr;
-            if (check(hipMalloc(&d, t.size() * 4), "tile table")) return;
-            if (check(hipMemcpy(d, t.data(), t.size() * 4, hipMemcpyHostToDevice), "tile table upload")) { (void)hipFree(d); return; }
-            it = h->tile_tabs.emplace(key, std::make_pair(d, n)).first;
+            DevBuf d;
+            if (check(d.alloc(t.size() * 4), "tile table")) return;
+            if (check(hipMemcpy(d.p, t.data(), t.size() * 4, hipMemcpyHostToDevice), "tile table upload")) return;
+            it = h->tile_tabs.emplace(key, std::make_pair(std::move(d), n)).first;
         }
-        a.tile_tab = it->second.first;
+        a.tile_tab = it->second.first.p;
         a.grid = it->second.second;
     }
 
@@ -963,7 +950,7 @@ struct Runner {
         if (fused) {
             a.in1 = xin;
             a.p1 = pad16(c.cout) * dtype_size(dtype) / 16;
-            a.wmix = mixf->packed;
+            a.wmix = mixf->packed[PK_MAIN].p;
             a.mix_pieces = mixf->nchunks * mixf->nt;
             {   // room for the 8 compute waves' x fragments next to the gate weights in ring slots 1-2?
                 const int a_slot = (ch.mode == MODE_C3W16 ? 2 * 640 : 2 * 672) * 16;
@@ -979,12 +966,11 @@ struct Runner {
         const double sz = dtype_size(dtype);
         const double px = (double)B * H * W;
         pick_order(a, c, px * c.cp0 * sz, knobs);
-        if (ch.s16) {
-            const bool t = ch.launcher == L_CONV3T;
+        if (ch.layout != PK_MAIN) {
             a.s16 = 1;
-            a.wpk16 = t ? c.packed16t : c.packed16;
-            a.nchunks16 = t ? c.nchunks16t : c.nchunks16;
-            if (fused) a.wmix16 = t ? mixf->packed16t : (ch.launcher == L_CONV3R ? mixf->packed16r : mixf->packed16);
+            a.wpk16 = c.packed[ch.layout].p;
+            a.nchunks16 = pack_shape(c, ch.layout).nchunks;
+            if (fused) a.wmix16 = mixf->packed[ch.gate].p;
         }
         if (ch.tile_list) tile_table(a, ch.th, ch.tw, ch.persist);
         if (rc) return;
@@ -1016,12 +1002,13 @@ struct Runner {
         a.p_out = a.cp_out * sz / 16;
         a.mix_scale = 1.0f / (1.0f + std::exp(-alpha));
         a.inv_mix_scale = inv_sigmoid(alpha);
-        if (ch.s16) {  // 192-channel N tiles, x / z straight into MFMA operands (mix16_kernel / mix16b_kernel)
-            a.ntiles = c.cout / 192;
-            a.wpk16 = ch.launcher == L_MIX16B ? c.packed16r : c.packed16;
-            a.nchunks16 = c.nchunks16;
+        if (ch.layout != PK_MAIN) {  // 192-channel N tiles, x / z straight into MFMA operands (mix16_kernel / mix16b_kernel)
+            const PackShape sh = pack_shape(c, ch.layout);
+            a.ntiles = sh.ntiles;
+            a.wpk16 = c.packed[ch.layout].p;
+            a.nchunks16 = sh.nchunks;
         }
-        pick_order(a, c, (double)npix * (c.cp0 + pad16(c.c1)) * sz, knobs, ch.s16 ? 32 : 64);
+        pick_order(a, c, (double)npix * (c.cp0 + pad16(c.c1)) * sz, knobs, ch.layout != PK_MAIN ? 32 : 64);
         launch(ch, a, c.nt, prof_begin(1, a, c, 2.0 * (double)npix * c.cin * c.cout, (double)npix * 3.0 * c.cout * sz));
     }
 
@@ -1074,7 +1061,7 @@ static int forward_micro(mz_handle* h, const char* x, char* out_sr, float* out_q
 
     // stem (model.py:158): NCHW image -> NHWC features
     char* cur = ws + p.R[0][0];
-    if (hipError_t e = launch_stem(h->dtype, x, h->stem_w4, cur, nb, H, W, pad16(h->ch[0]), s, io_u8); e != hipSuccess)
+    if (hipError_t e = launch_stem(h->dtype, x, (const float*)h->stem_w4.p, cur, nb, H, W, pad16(h->ch[0]), s, io_u8); e != hipSuccess)
         return fail(MZ_ERR_HIP, "stem launch: %s", hipGetErrorString(e));
 
     // encoder (model.py:461-484)
@@ -1101,7 +1088,7 @@ static int forward_micro(mz_handle* h, const char* x, char* out_sr, float* out_q
         const int F = h->cfg.num_deg_features;
         run.conv3(h->qa_conv, feat[3], ws + p.QA, nb, p.hs[3], p.ws[3], EPI_STORE, 0, 0, 0);
         if (run.rc) return run.rc;
-        if (hipError_t e = launch_qa_reduce(h->dtype, ws + p.QA, h->qa_bias, out_qa, nb, p.hs[3] * p.ws[3], pad16(F), F, s);
+        if (hipError_t e = launch_qa_reduce(h->dtype, ws + p.QA, (const float*)h->qa_bias.p, out_qa, nb, p.hs[3] * p.ws[3], pad16(F), F, s);
             e != hipSuccess)
             return fail(MZ_ERR_HIP, "qa reduce launch: %s", hipGetErrorString(e));
     }
@@ -1202,12 +1189,13 @@ extern "C" int mz_forward_u8(mz_handle* h, const uint8_t* x, uint8_t* out_sr, fl
 // ------------------------------------------------------------------------------------------------
 extern "C" int mz_padded_channels(int c) { return pad16(c); }
 
-struct TempBuf {
-    void* p = nullptr;
-    ~TempBuf() {
-        if (p) (void)hipFree(p);
-    }
-};
+// The throw-away handle an mz_op_* entry hands to Runner: the zero page and the knobs
+static int op_handle(mz_handle& fake, hipStream_t s) {
+    HIPCHK(fake.zero_page.alloc(4096));
+    HIPCHK(hipMemsetAsync(fake.zero_page.p, 0, 4096, s));
+    fake.knobs = read_knobs();
+    return MZ_OK;
+}
 
 extern "C" int mz_op_conv(int dtype, int kind, const void* in0, const void* in1, const float* w_dev_f32, float alpha,
                           void* out, int B, int H, int W, int cin, int cout, int Hout, int Wout, int silu,
@@ -1223,19 +1211,10 @@ extern "C" int mz_op_conv(int dtype, int kind, const void* in0, const void* in1,
         case 3: plan_conv(c, dtype, MODE_GEMM1, cout, 2 * cout, 1, 1, OUT_PLAIN, SRC_CONCAT, cout, cout); break;
         default: return fail(MZ_ERR_INVALID_ARGUMENT, "bad op kind %d", kind);
     }
-    TempBuf zero, packed, packed16, packed16r, packed16t;
-    HIPCHK(hipMalloc(&zero.p, 4096));
-    HIPCHK(hipMemsetAsync(zero.p, 0, 4096, s));
-    rc = pack_conv(c, dtype, w_dev_f32, s);
-    packed.p = c.packed;
-    packed16.p = c.packed16;
-    packed16r.p = c.packed16r;   // kind 3, C = 192: the second packing of the gate weights (mix16b_kernel)
-    packed16t.p = c.packed16t;   // kind 0, one N tile of 33..48 channels: conv3t_kernel's packing
-    if (rc) return rc;
-    // a throw-away handle carries the zero page and the knobs for Runner
     mz_handle fake;
-    fake.zero_page = zero.p;
-    fake.knobs = read_knobs();
+    rc = op_handle(fake, s);
+    if (!rc) rc = pack_conv(c, dtype, w_dev_f32, s);
+    if (rc) return rc;
     Runner run{&fake, s, dtype};
     switch (kind) {
         case 0: run.conv3(c, in0, out, B, H, W, EPI_STORE, silu, 0, 0); break;
@@ -1249,7 +1228,6 @@ extern "C" int mz_op_conv(int dtype, int kind, const void* in0, const void* in1,
         case 2: run.crush(c, in0, out, B, H, W); break;
         case 3: run.mix(c, alpha, in0, in1, out, B, H, W); break;
     }
-    fake.zero_page = nullptr;
     HIPCHK(hipStreamSynchronize(s));
     return run.rc;
 }
@@ -1266,22 +1244,13 @@ extern "C" int mz_op_conv_mix(int dtype, const void* hid, const void* x, const f
     BlockW b;
     plan_block(b, dtype, cout, cin);
     if (!b.fused) return fail(MZ_ERR_INVALID_ARGUMENT, "the fused conv2 + mix needs all output channels in one N tile (cout <= 96)");
-    ConvW &c2 = b.conv2, &f = b.mixf;
-    TempBuf zero, p0, p1, p2, p3, p4, p5, p6;
-    HIPCHK(hipMalloc(&zero.p, 4096));
-    HIPCHK(hipMemsetAsync(zero.p, 0, 4096, s));
-    rc = pack_conv(c2, dtype, w2_dev_f32, s);
-    p0.p = c2.packed; p1.p = c2.packed16; p5.p = c2.packed16t;
-    if (rc) return rc;
-    rc = pack_conv(f, dtype, wmix_dev_f32, s);
-    p2.p = f.packed; p3.p = f.packed16; p4.p = f.packed16r; p6.p = f.packed16t;
-    if (rc) return rc;
     mz_handle fake;
-    fake.zero_page = zero.p;
-    fake.knobs = read_knobs();
+    rc = op_handle(fake, s);
+    if (!rc) rc = pack_conv(b.conv2, dtype, w2_dev_f32, s);
+    if (!rc) rc = pack_conv(b.mixf, dtype, wmix_dev_f32, s);
+    if (rc) return rc;
     Runner run{&fake, s, dtype};
-    run.conv3(c2, hid, out, B, H, W, EPI_FUSEDMIX, 0, 0, 0, nullptr, 0, 0, nullptr, &f, x, alpha);
-    fake.zero_page = nullptr;
+    run.conv3(b.conv2, hid, out, B, H, W, EPI_FUSEDMIX, 0, 0, 0, nullptr, 0, 0, nullptr, &b.mixf, x, alpha);
     HIPCHK(hipStreamSynchronize(s));
     return run.rc;
 }
@@ -1299,30 +1268,23 @@ extern "C" int mz_op_conv_film(int dtype, const void* in0, const float* w_dev_f3
     hipStream_t s = (hipStream_t)hip_stream;
     ConvW c;
     plan_conv(c, dtype, MODE_CONV3, cout, cin, 3, 3, OUT_PLAIN, SRC_PLAIN, 0, 0);
-    TempBuf zero, packed, packed16, packed16t, gpad, bpad;
-    HIPCHK(hipMalloc(&zero.p, 4096));
-    HIPCHK(hipMemsetAsync(zero.p, 0, 4096, s));
-    rc = pack_conv(c, dtype, w_dev_f32, s);
-    packed.p = c.packed;
-    packed16.p = c.packed16;
-    packed16t.p = c.packed16t;
+    mz_handle fake;
+    rc = op_handle(fake, s);
+    if (!rc) rc = pack_conv(c, dtype, w_dev_f32, s);
     if (rc) return rc;
     // gamma / beta [B][cout] -> [B][padded cout], pad channels zero
     const int cp = pad16(cout);
-    HIPCHK(hipMalloc(&gpad.p, sizeof(float) * (size_t)B * cp));
-    HIPCHK(hipMalloc(&bpad.p, sizeof(float) * (size_t)B * cp));
+    DevBuf gpad, bpad;
+    HIPCHK(gpad.alloc(sizeof(float) * (size_t)B * cp));
+    HIPCHK(bpad.alloc(sizeof(float) * (size_t)B * cp));
     HIPCHK(hipMemsetAsync(gpad.p, 0, sizeof(float) * (size_t)B * cp, s));
     HIPCHK(hipMemsetAsync(bpad.p, 0, sizeof(float) * (size_t)B * cp, s));
     HIPCHK(hipMemcpy2DAsync(gpad.p, sizeof(float) * cp, gamma_dev_f32, sizeof(float) * cout, sizeof(float) * cout, B, hipMemcpyDeviceToDevice, s));
     HIPCHK(hipMemcpy2DAsync(bpad.p, sizeof(float) * cp, beta_dev_f32, sizeof(float) * cout, sizeof(float) * cout, B, hipMemcpyDeviceToDevice, s));
-    mz_handle fake;
-    fake.zero_page = zero.p;
-    fake.knobs = read_knobs();
     Runner run{&fake, s, dtype};
     run.film_gamma = (const float*)gpad.p;
     run.film_beta = (const float*)bpad.p;
     run.conv3(c, in0, out, B, H, W, EPI_STORE, silu, 0, 0);
-    fake.zero_page = nullptr;
     HIPCHK(hipStreamSynchronize(s));
     return run.rc;
 }
@@ -1333,8 +1295,8 @@ extern "C" int mz_op_stem(int dtype, const void* x, const float* w_dev_f32, cons
     if (rc) return rc;
     hipStream_t s = (hipStream_t)hip_stream;
     const int cp = pad16(cout);
-    TempBuf w4;
-    HIPCHK(hipMalloc(&w4.p, sizeof(float) * 4 * cp));
+    DevBuf w4;
+    HIPCHK(w4.alloc(sizeof(float) * 4 * cp));
     HIPCHK(hipMemsetAsync(w4.p, 0, sizeof(float) * 4 * cp, s));
     HIPCHK(launch_pack_stem(w_dev_f32, b_dev_f32, (float*)w4.p, cout, cp, s));
     HIPCHK(launch_stem(dtype, x, (const float*)w4.p, out, B, H, W, cp, s));
@@ -1349,19 +1311,12 @@ extern "C" int mz_op_final(int dtype, const void* feat, const void* img, const f
     hipStream_t s = (hipStream_t)hip_stream;
     ConvW c;
     plan_conv(c, dtype, MODE_CONV3, 12, cin, 3, 3, OUT_FINAL, SRC_PLAIN, 0, 0);
-    TempBuf zero, packed, packed16;
-    HIPCHK(hipMalloc(&zero.p, 4096));
-    HIPCHK(hipMemsetAsync(zero.p, 0, 4096, s));
-    rc = pack_conv(c, dtype, w_dev_f32, s);
-    packed.p = c.packed;
-    packed16.p = c.packed16;
-    if (rc) return rc;
     mz_handle fake;
-    fake.zero_page = zero.p;
-    fake.knobs = read_knobs();
+    rc = op_handle(fake, s);
+    if (!rc) rc = pack_conv(c, dtype, w_dev_f32, s);
+    if (rc) return rc;
     Runner run{&fake, s, dtype};
     run.conv3(c, feat, out, B, H, W, EPI_FINAL, 0, 2 * H, 2 * W, img, R, clamp);
-    fake.zero_page = nullptr;
     HIPCHK(hipStreamSynchronize(s));
     return run.rc;
 }
@@ -1389,56 +1344,82 @@ extern "C" int mz_debug_tile_list(int B, int tiles_y, int tiles_x, int ntiles, i
     for (int i = 0; i < n && i < cap; ++i) { out[2 * i] = t[2 * i]; out[2 * i + 1] = t[2 * i + 1]; }
     return n;
 }
-// Host-only (no GPU): the kernel family Runner::conv3 / Runner::mix would launch for one layer (ops: include/mewzoom_hip.h), with
-// ConvW planned as the model and the mz_op_* entries plan it and the knobs read from the environment as the mz_op_* entries read them.
-extern "C" const char* mz_debug_select(int dtype, int op, int cin, int cout, int B, int H, int W, int cus) {
-    if ((dtype != MZ_F32 && dtype != MZ_BF16 && dtype != MZ_F16) || cin < 1 || cout < 1 || B < 1 || H < 1 || W < 1 || cus < 0) {
-        fail(MZ_ERR_INVALID_ARGUMENT, "bad arguments");
-        return nullptr;
-    }
-    const Knobs k = read_knobs();
-    ConvW c;
-    BlockW b;
-    KernelChoice ch;
+// The layer that op (mz_debug_select's, include/mewzoom_hip.h; 8: the fused gate of a block's conv2) names, planned as the model and
+// the mz_op_* entries plan it, inside b.  nullptr (mz_last_error() says why) for a bad op, a mix whose cin is not 2 cout, or the gate of
+// a block that does not fuse.
+static const ConvW* plan_debug_layer(BlockW& b, int dtype, int op, int cin, int cout) {
     switch (op) {
-        case 0: case 1: case 4:  // conv1 + SiLU, plain 3x3, QA head
-            plan_conv(c, dtype, MODE_CONV3, cout, cin, 3, 3, OUT_PLAIN, SRC_PLAIN, 0, 0);
-            ch = choose_conv3(k, dtype, c, nullptr, EPI_STORE, op == 0, false, B, H, W, 0, 0, cus);
-            break;
+        case 0: case 1: case 4: case 5:  // conv1 + SiLU, plain 3x3, QA head, FiLM conv
+            plan_conv(b.conv1, dtype, MODE_CONV3, cout, cin, 3, 3, OUT_PLAIN, SRC_PLAIN, 0, 0);
+            return &b.conv1;
         case 2:  // SubpixelConv2d: 3x3 + PixelShuffle(2) into 2H x 2W
-            plan_conv(c, dtype, MODE_CONV3, cout, cin, 3, 3, OUT_D2S, SRC_PLAIN, 0, 0);
-            ch = choose_conv3(k, dtype, c, nullptr, EPI_D2S, 0, false, B, H, W, 2 * H, 2 * W, cus);
-            break;
+            plan_conv(b.conv1, dtype, MODE_CONV3, cout, cin, 3, 3, OUT_D2S, SRC_PLAIN, 0, 0);
+            return &b.conv1;
         case 3:  // image head
-            plan_conv(c, dtype, MODE_CONV3, cout, cin, 3, 3, OUT_FINAL, SRC_PLAIN, 0, 0);
-            ch = choose_conv3(k, dtype, c, nullptr, EPI_FINAL, 0, false, B, H, W, 2 * H, 2 * W, cus);
-            break;
-        case 5:  // FiLM conv (mz_op_conv_film)
-            if (dtype != DT_BF16 && dtype != DT_F16) {
-                fail(MZ_ERR_INVALID_ARGUMENT, "the FiLM epilogue is implemented for bf16 / fp16");
-                return nullptr;
-            }
-            plan_conv(c, dtype, MODE_CONV3, cout, cin, 3, 3, OUT_PLAIN, SRC_PLAIN, 0, 0);
-            ch = choose_conv3(k, dtype, c, nullptr, EPI_STORE, 0, true, B, H, W, 0, 0, cus);
-            break;
-        case 6:  // a block's conv2 (cin = the hidden channels), as forward runs it: with the mix fused, or alone
+            plan_conv(b.conv1, dtype, MODE_CONV3, cout, cin, 3, 3, OUT_FINAL, SRC_PLAIN, 0, 0);
+            return &b.conv1;
+        case 6: case 8:  // a block's conv2 (cin = the hidden channels), its fused gate
             plan_block(b, dtype, cout, cin);
-            ch = fuse_mix(k, b) ? choose_conv3(k, dtype, b.conv2, &b.mixf, EPI_FUSEDMIX, 0, false, B, H, W, 0, 0, cus)
-                                : choose_conv3(k, dtype, b.conv2, nullptr, EPI_STORE, 0, false, B, H, W, 0, 0, cus);
-            break;
+            if (op == 6) return &b.conv2;
+            if (b.fused) return &b.mixf;
+            fail(MZ_ERR_INVALID_ARGUMENT, "the block does not fuse conv2 and the mix");
+            return nullptr;
         case 7:  // unfused AdaptiveResidualMix of cout channels (cin = 2 cout)
             if (cin != 2 * cout) {
                 fail(MZ_ERR_INVALID_ARGUMENT, "a mix has cin = 2 cout");
                 return nullptr;
             }
-            plan_conv(c, dtype, MODE_GEMM1, cout, cin, 1, 1, OUT_PLAIN, SRC_CONCAT, cout, cout);
-            ch = choose_mix(k, dtype, c, B, H, W, cus);
-            break;
-        default:
-            fail(MZ_ERR_INVALID_ARGUMENT, "bad op %d", op);
-            return nullptr;
+            plan_conv(b.mix, dtype, MODE_GEMM1, cout, cin, 1, 1, OUT_PLAIN, SRC_CONCAT, cout, cout);
+            return &b.mix;
     }
-    return ch.name;
+    fail(MZ_ERR_INVALID_ARGUMENT, "bad op %d", op);
+    return nullptr;
+}
+
+// Host-only (no GPU): the kernel family Runner::conv3 / Runner::mix would launch for one layer, with the knobs read from the environment
+// as the mz_op_* entries read them.
+extern "C" const char* mz_debug_select(int dtype, int op, int cin, int cout, int B, int H, int W, int cus) {
+    if ((dtype != MZ_F32 && dtype != MZ_BF16 && dtype != MZ_F16) || cin < 1 || cout < 1 || B < 1 || H < 1 || W < 1 || cus < 0) {
+        fail(MZ_ERR_INVALID_ARGUMENT, "bad arguments");
+        return nullptr;
+    }
+    if (op == 5 && dtype != DT_BF16 && dtype != DT_F16) {
+        fail(MZ_ERR_INVALID_ARGUMENT, "the FiLM epilogue is implemented for bf16 / fp16");
+        return nullptr;
+    }
+    if (op == 8) {  // the gate is no launch of its own
+        fail(MZ_ERR_INVALID_ARGUMENT, "bad op %d", op);
+        return nullptr;
+    }
+    const Knobs k = read_knobs();
+    BlockW b;
+    const ConvW* c = plan_debug_layer(b, dtype, op, cin, cout);
+    if (!c) return nullptr;
+    if (op == 7) return choose_mix(k, dtype, *c, B, H, W, cus).name;
+    const int epi = op == 2 ? EPI_D2S : op == 3 ? EPI_FINAL : op == 6 && fuse_mix(k, b) ? EPI_FUSEDMIX : EPI_STORE;
+    const int up = op == 2 || op == 3 ? 2 : 0;  // D2S / FINAL: into 2H x 2W
+    return choose_conv3(k, dtype, *c, epi == EPI_FUSEDMIX ? &b.mixf : nullptr, epi, op == 0, op == 5, B, H, W, up * H, up * W, cus).name;
+}
+
+// Host-only (no GPU): packing `layout` of one layer (mz_debug_select's ops; 8 = the fused gate of a block's conv2), as pack_kernel writes
+// it: the OIHW source index of each packed element, -1 for padding.  Writes at most cap of them to out.
+extern "C" long long mz_debug_pack(int dtype, int op, int cin, int cout, int layout, long long* out, long long cap) {
+    if ((dtype != MZ_F32 && dtype != MZ_BF16 && dtype != MZ_F16) || cin < 1 || cout < 1 || layout < 0 || layout >= PK_COUNT || cap < 0 ||
+        (cap > 0 && !out)) {
+        fail(MZ_ERR_INVALID_ARGUMENT, "bad arguments");
+        return -1;
+    }
+    BlockW b;
+    const ConvW* c = plan_debug_layer(b, dtype, op, cin, cout);
+    if (!c) return -1;
+    if (!c->has(layout)) {
+        fail(MZ_ERR_INVALID_ARGUMENT, "the layer has no packing %d", layout);
+        return -1;
+    }
+    const PackArgs p = pack_args(*c, layout, dtype, nullptr, nullptr);
+    const long long n = (long long)(packed_bytes(p.taps, p.frags, p.ntiles, p.nchunks) / dtype_size(dtype));
+    for (long long i = 0; i < n && i < cap; ++i) out[i] = dtype == DT_F32 ? pack_source<4>(p, i) : pack_source<2>(p, i);
+    return n;
 }
 extern "C" const char* mz_version(void) { return "mewzoom_hip 0.1 (gfx950)"; }
 

@@ -92,7 +92,7 @@ int gemm1_chunks_per_stage();
 hipError_t launch_conv(int dtype, int mode, int nt, const ConvArgs& a, hipStream_t s);
 // AdaptiveResidualMix for C = k * 192 on the 16x16x32 MFMA (16-bit types): a.wpk16 / a.nchunks16 = K steps over [x ; z]
 hipError_t launch_mix16(int dtype, const ConvArgs& a, hipStream_t s);
-// C = 192 without the second read of x and z: a.wpk16 = gate weights packed with PackArgs::frag16 = 3 (accumulator rows in B-operand
+// C = 192 without the second read of x and z: a.wpk16 = gate weights packed as PK_MIX16B (accumulator rows in B-operand
 // order); the gate matrix stays in LDS, every wave walks its own 32-pixel units
 hipError_t launch_mix16b(int dtype, const ConvArgs& a, hipStream_t s, int workgroups);  // persistent: at most `workgroups` (one per CU)
 hipError_t init_kernels();  // raises the dynamic-LDS limits (per device)
@@ -101,31 +101,41 @@ hipError_t init_kernels();  // raises the dynamic-LDS limits (per device)
 // and the loader + epilogue role from tile to tile.  >= 3 chunks of 32 channels (odd counts included; a.ragged_planes != 0: exactly
 // two, the second with a.ragged_planes real planes -- Cin = 48 --, EPI_STORE + SiLU only); EPI_STORE / EPI_D2S
 // (32-bit store offsets: 12 planes of the output, resp. one whole D2S target image, must stay below 4 GiB); EPI_FUSEDMIX: >= 6
-// chunks, a.wmix16 = gate weights packed with PackArgs::frag16 = 2, a.in1 / a.p1 = the block input.
+// chunks, a.wmix16 = gate weights packed as PK_GATE16R, a.in1 / a.p1 = the block input.
 hipError_t launch_conv3r(int dtype, const ConvArgs& a, hipStream_t s);
 // conv3t_kernel (mz_conv3t.h): conv3r's role-alternating structure for ONE N tile of <= 48 channels (three 16-channel fragments x twelve
-// pixel fragments per wave, 12 x 64 pixel tiles).  a.wpk16 = weights packed with PackArgs::nfr = 3; a.nchunks16 = 3 or >= 6; EPI_STORE
-// (plain / SiLU) or EPI_FUSEDMIX (a.wmix16 = gate weights packed with PackArgs::frag16 = 4, a.in1 / a.p1 = the block input).
+// pixel fragments per wave, 12 x 64 pixel tiles).  a.wpk16 = weights packed as PK_CONV16T; a.nchunks16 = 3 or >= 6; EPI_STORE
+// (plain / SiLU) or EPI_FUSEDMIX (a.wmix16 = gate weights packed as PK_GATE16T, a.in1 / a.p1 = the block input).
 hipError_t launch_conv3t(int dtype, const ConvArgs& a, hipStream_t s);
 
 // ---- weight packing ---------------------------------------------------------------------------
 enum OutMap : int { OUT_PLAIN = 0, OUT_D2S = 1, OUT_FINAL = 2 };
+// The packings of one layer's weights (mz_pack.h maps each element to its OIHW source; mz_host.cpp plans which layers have which).
+// PK_MAIN counts 32-channel fragments of the 32x32 MFMA and K chunks of chunk_channels(); every other layout holds fragments of the
+// 16x16x32 MFMA (16 channels x 32 K, 16-bit types) and counts K chunks of 32 channels.  Packed in this order.
+enum PackLayout : int {
+    PK_MAIN = 0,  // every layer: conv3w / conv3p / conv_kernel (3x3, crush, mix); a fused gate (SRC_MIXF) for conv3w
+    PK_CONV16,    // 3x3 (SRC_PLAIN): conv3s, conv3r
+    PK_MIX16,     // the [C, 2C] gate of a mix (SRC_CONCAT), C = k * 192: mix16_kernel, 12 fragments per 192-channel N tile
+    PK_GATE16,    // a fused gate (SRC_MIXF): conv3s; x channels in natural order, then z in accumulator-row order
+    PK_MIX16B,    // PK_MIX16 for C = 192 in mix16b_kernel's row and K-step order (accumulator rows in B-operand order, own channels first)
+    PK_GATE16R,   // PK_GATE16 with the x half in accumulator-row order as well: conv3r's fused variant
+    PK_CONV16T,   // 3x3, three 16-channel fragments per tap: conv3t
+    PK_GATE16T,   // conv3t's fused gate: K step s = fragments 2 s, 2 s + 1 of [x0 x1 x2 z0 z1 z2]
+    PK_COUNT
+};
 struct PackArgs {
     const float* w;    // [cout][cin][kh][kw] float32
     void* dst;
     int dtype;
+    int layout;        // PackLayout
     int cout, cin, kh, kw;
     int taps;          // packed taps (9 for conv3, 1 for GEMM1)
-    int nt, ntiles, nchunks;
+    int frags, ntiles, nchunks;  // fragments per tap and N tile, N tiles, K chunks
     int out_map;       // OutMap
     int cq, cq_p;      // D2S: real / padded channels per output pixel
     int in_map;        // SrcKind
-    int frag16;        // 1: fragments of the 16x16x32 MFMA (16 channels x 32 K; 16-bit types); nchunks counts 32-channel chunks.  2 (SRC_MIXF): ... with
-                       // the x half of the gate weights in accumulator-row order as well (conv3r_kernel's fused variant)
-                       // 3 (SRC_CONCAT, nt = 6): mix16b_kernel's row and K-step order
-                       // 4 (SRC_MIXF, nfr = 3, nchunks = 3): conv3t_kernel's gate: K step s = fragments 2 s, 2 s + 1 of [x0 x1 x2 z0 z1 z2]
-    int c0, cp0, c1;   // CONCAT: real/padded channels of in0, real channels of in1;  PLAIN/CRUSH: c0 = cin, cp0 = padded cin
-    int nfr;           // frag16 packings: 16-channel fragments per tap and N tile; 0 = 2 * nt (conv3t_kernel: 3)
+    int c0, cp0, c1;   // CONCAT / MIXF: real/padded channels of in0, real channels of in1;  PLAIN/CRUSH: c0 = cin, cp0 = padded cin
 };
 size_t packed_bytes(int taps, int nt, int ntiles, int nchunks);
 size_t conv16_lds_bytes(int mode, int nt, bool fuse);

@@ -24,6 +24,7 @@
 // Both images are lane-linear, which is what global_load_lds (LDS-DMA) requires, and every
 // ds_read_b128 of a fragment covers contiguous 512-byte runs per half-wave: bank-conflict free.
 #include "mz_device.h"
+#include "mz_pack.h"
 
 namespace mz {
 
@@ -1147,7 +1148,7 @@ __device__ __forceinline__ void gate_halves(f32x4 (&beta)[2 * NT], const u32x4 (
 
 // FUSE: conv2 + AdaptiveResidualMix (model.py:826-839) in one pass, as in conv3w_kernel<.., FUSE> but on the 16x16
 // accumulator layout: after the K loop the wave packs z into MFMA B operands (two 16-channel accumulator fragments =
-// one 32-wide K step; the gate weights were packed in that order, SRC_MIXF + frag16), two extra barriers let the
+// one 32-wide K step; the gate weights were packed in that order, PK_GATE16), two extra barriers let the
 // weight loader drop the 4 NT^2 KB of gate weights into the second weight slot (+ the LDS behind it) once every wave
 // has left the K loop, x arrives as plain 16-byte loads (the plane-major layout IS the B-operand layout), and the
 // blend x + sigmoid(alpha) sigmoid(beta) (z - x) runs in the accumulator registers before the common store.
@@ -1669,7 +1670,7 @@ hipError_t launch_mix16(int dtype, const ConvArgs& a, hipStream_t s) {
 // mix16_kernel blends in accumulator layout and therefore fetches x and z a second time (8-byte loads, L2 hit rate 0.38 at
 // C = 192: counted traffic 2.79 GB against 1.79 GB algorithmic -- DESIGN 5.3), and its workgroup -- the only one its CU has room
 // for -- alternates between a read-only K loop and a write-only epilogue.  Here
-//   * the gate weights are packed (PackArgs::frag16 = 3) so that accumulator row 4 g + j of channel fragment 2 m + h is channel
+//   * the gate weights are packed (PK_MIX16B) so that accumulator row 4 g + j of channel fragment 2 m + h is channel
 //     32 m + 8 g + 4 h + j: lane (g, c) then owns, as accumulators, exactly the eight channels of pixel c that it loaded as the B
 //     operand of K step m -- x, z and beta of one 16-byte plane entry sit in ONE lane: the 24 B operands of a unit (96 registers)
 //     are kept until the blend, no second read, no v_permlane16_swap, one 16-byte store per entry;
@@ -2146,118 +2147,10 @@ hipError_t init_kernels() {
 // weight packing: OIHW float32 -> [ntile][kchunk][tap][nt][lane][16 bytes] in the compute dtype
 // ================================================================================================
 template <class TT> __global__ void pack_kernel(const PackArgs a, long long total) {
-    constexpr int SZ = TT::SZ;
-    constexpr int CK = TT::CK;
-    constexpr int EPL = 16 / SZ;  // elements per lane
     const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= total) return;
-    long long t = idx;
-    const int e = (int)(t % EPL); t /= EPL;
-    const int lane = (int)(t % 64); t /= 64;
-    const int nfr = a.frag16 ? (a.nfr ? a.nfr : 2 * a.nt) : a.nt;  // fragments per tap: 16-channel (16x16x32 MFMA) or 32-channel ones
-    const int nt = (int)(t % nfr); t /= nfr;
-    const int tap = (int)(t % a.taps); t /= a.taps;
-    const int kc = (int)(t % a.nchunks); t /= a.nchunks;
-    const int nb = (int)t;
-    int n = a.frag16 ? (nb * nfr + nt) * 16 + (lane & 15) : (nb * a.nt + nt) * 32 + (lane & 31);
-    if (a.frag16 == 3) {
-        // mix16b_kernel: accumulator rows in B-OPERAND order.  Row r = 4 g + j of fragment 2 m + h stands for channel
-        // 32 m + 8 g + 4 h + j of the N tile, so that lane (g, c) of the accumulators owns exactly the eight channels whose x and z it
-        // loaded as the B operand of K step m: the blend needs no second read of x and z, and its result is a whole 16-byte entry
-        const int r = lane & 15;
-        n = nb * (nfr * 16) + 32 * (nt >> 1) + 8 * (r >> 2) + 4 * (nt & 1) + (r & 3);
-    }
-    const int hh = lane >> 5;
-    const int kin = a.frag16 ? (lane >> 4) * 8 + e : hh * (CK / 2) + e;  // channel within the chunk
-    const int ckk = a.frag16 ? 32 : CK;                                  // channels per chunk
-
-    // output channel
-    int o = -1;
-    if (a.out_map == OUT_PLAIN) {
-        o = n < a.cout ? n : -1;
-    } else if (a.out_map == OUT_D2S) {
-        const int ij = n / a.cq_p, c = n - ij * a.cq_p;
-        o = (ij < 4 && c < a.cq) ? c * 4 + ij : -1;  // PixelShuffle(2): in-channel = c*4 + 2i + j
-    } else {
-        const int ij = n >> 2, c = n & 3;
-        o = (n < 16 && c < 3) ? c * 4 + ij : -1;
-    }
-    // input channel and filter tap
-    int ci = -1, ty = 0, tx = 0;
-    if (a.in_map == SRC_PLAIN) {
-        const int k = kc * ckk + kin;
-        ci = k < a.c0 ? k : -1;
-        ty = tap / a.kw;
-        tx = tap - ty * a.kw;
-    } else if (a.in_map == SRC_CONCAT) {
-        int ks = kc;
-        if (a.frag16 == 3) {
-            // ... and the K steps of an N tile start with its OWN x and z channels (six steps each, kept in registers for the blend);
-            // the rest follows in natural order (mix16b_step() in the kernel is the same map)
-            const int hs = a.nchunks >> 1, t6 = 6 * nb;
-            if (kc < 6) ks = t6 + kc;
-            else if (kc < 12) ks = hs + t6 + (kc - 6);
-            else {
-                ks = kc - 12;
-                if (ks >= t6) ks += 6;
-                if (ks >= hs + t6) ks += 6;
-            }
-        }
-        const int k = ks * ckk + kin;
-        if (k < a.cp0) ci = k < a.c0 ? k : -1;
-        else ci = (k - a.cp0) < a.c1 ? a.c0 + (k - a.cp0) : -1;
-    } else if (a.in_map == SRC_MIXF && a.frag16 == 4) {
-        // conv3t_kernel's gate (C <= 48: three 16-channel fragments of x, three of z): K step kc = fragments 2 kc and 2 kc + 1 of
-        // [x0 x1 x2 z0 z1 z2], the K elements of lane group g in accumulator-row order: e < 4 -> the first fragment's channels 4 g + e,
-        // e >= 4 -> the second's
-        const int g = lane >> 4;
-        const int fr = 2 * kc + (e < 4 ? 0 : 1);
-        const int ch = 16 * (fr % 3) + 4 * g + (e & 3);
-        if (fr < 3) ci = ch < a.c0 ? ch : -1;
-        else ci = ch < a.c1 ? a.c0 + ch : -1;
-    } else if (a.in_map == SRC_MIXF && a.frag16) {
-        // fused gate for the 16x16x32 kernel: K-steps [0, ncx) = x channels in natural order (32 per step); then one
-        // K-step per PAIR of 16-channel accumulator fragments of z, K elements in the order the accumulator quads of
-        // lane group g = lane >> 4 supply them: e < 4 -> fragment 2m, channel 4g + e; e >= 4 -> fragment 2m + 1
-        const int ncx = (a.cp0 + 31) / 32;
-        if (kc < ncx && a.frag16 == 2) {
-            // conv3r_kernel's fused variant: the x half in accumulator-row order too (x is fetched in accumulator layout, so
-            // that a pair of its channel fragments is a B operand as it stands)
-            const int g = lane >> 4;
-            const int xch = 32 * kc + (e < 4 ? 4 * g + e : 16 + 4 * g + (e - 4));
-            ci = xch < a.c0 ? xch : -1;
-        } else if (kc < ncx) {
-            const int k = kc * 32 + kin;
-            ci = k < a.c0 ? k : -1;
-        } else {
-            const int m = kc - ncx, g = lane >> 4;
-            const int zch = 32 * m + (e < 4 ? 4 * g + e : 16 + 4 * g + (e - 4));
-            ci = zch < a.c1 ? a.c0 + zch : -1;
-        }
-    } else if (a.in_map == SRC_MIXF) {
-        // fused AdaptiveResidualMix gate: chunks [0, ncx) = x channels in natural order; then one chunk per
-        // (32-row accumulator tile, fragment g) of z, K-elements in ACCUMULATOR ROW order (ZFrag<TT>::make)
-        const int ncx = a.cp0 / CK;
-        if (kc < ncx) {
-            const int k = kc * CK + kin;
-            ci = k < a.c0 ? k : -1;
-        } else {
-            constexpr int ZG = SZ == 2 ? 2 : 4;
-            const int gz = kc - ncx, ntz = gz / ZG, g = gz - ntz * ZG;
-            const int zrow = 32 * ntz + (SZ == 2 ? 16 * g + 8 * (e >> 2) + 4 * hh + (e & 3) : 8 * g + 4 * hh + e);
-            ci = zrow < a.c1 ? a.c0 + zrow : -1;
-        }
-    } else {  // CRUSH: K axis = [tap][padded channel]
-        const int cpt = a.cp0 / CK;  // chunks per tap
-        const int st = kc / cpt;
-        const int k = (kc - st * cpt) * CK + kin;
-        ci = (st < 4 && k < a.c0) ? k : -1;  // st >= 4: K padding
-        ty = st >> 1;
-        tx = st & 1;
-    }
-    float v = 0.0f;
-    if (o >= 0 && ci >= 0) v = a.w[(((long long)o * a.cin + ci) * a.kh + ty) * a.kw + tx];
-    st1<TT>((char*)a.dst + idx * SZ, v);
+    const long long src = pack_source<TT::SZ>(a, idx);  // mz_pack.h
+    st1<TT>((char*)a.dst + idx * TT::SZ, src >= 0 ? a.w[src] : 0.0f);
 }
 
 size_t packed_bytes(int taps, int nt, int ntiles, int nchunks) {
@@ -2266,7 +2159,7 @@ size_t packed_bytes(int taps, int nt, int ntiles, int nchunks) {
 
 hipError_t launch_pack(const PackArgs& a, hipStream_t s) {
     const int sz = dtype_size(a.dtype);
-    const long long total = (long long)packed_bytes(a.taps, a.frag16 ? (a.nfr ? a.nfr : 2 * a.nt) : a.nt, a.ntiles, a.nchunks) / sz;
+    const long long total = (long long)packed_bytes(a.taps, a.frags, a.ntiles, a.nchunks) / sz;
     const int blocks = (int)((total + 255) / 256);
     switch (a.dtype) {
         case DT_F32: hipLaunchKernelGGL(pack_kernel<TF32>, dim3(blocks), dim3(256), 0, s, a, total); break;
