@@ -54,10 +54,12 @@ def resource_usage(src: str):
 def test_hot_kernels_use_no_scratch():
     from concurrent.futures import ThreadPoolExecutor
 
-    sources = ["mz_kernels.hip", "mz_conv3r.hip", "mz_conv3t.hip"]
+    sources = ["mz_conv3r.hip", "mz_conv32.hip", "mz_conv3s.hip", "mz_mix16.hip", "mz_conv3t.hip"]  # every unit with a HOT kernel
+    others = ["mz_kernels.hip"]  # no hot kernel: compiled for the hazard scan below, as before
     with ThreadPoolExecutor(max_workers=4) as ex:  # four hipcc processes side by side: ~2 minutes in total
-        usages = dict(zip(sources, ex.map(resource_usage, sources)))
-    for src, usage in usages.items():
+        usages = dict(zip(sources + others, ex.map(resource_usage, sources + others)))
+    for src in sources:
+        usage = usages[src]
         hot = {k: v for k, v in usage.items() if any(h in k for h in HOT) and ("TBF16" in k or "TF16" in k) and not any(e.search(k) for e in EXEMPT)}
         assert hot, f"no hot kernel found in {src}: {list(usage)[:5]}"
         bad = {k: v for k, v in hot.items() if v.get("ScratchSize", 0) != 0 or v.get("VGPRs Spill", 0) != 0}

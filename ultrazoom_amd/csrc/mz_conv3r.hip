@@ -11,16 +11,7 @@ namespace mz {
 
 template <class TT, int NSEG, int EPI, bool SILU = false, int GEO = 0, bool RAG = false> static hipError_t r_launch(const ConvArgs& a, hipStream_t s) {
     constexpr size_t lds = r3::Seg<NSEG>::lds_bytes(EPI == EPI_FUSEDMIX);
-    static bool ready[16] = {};  // per device ordinal: the dynamic-LDS limit of this instantiation has been raised
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return hipErrorInvalidDevice;
-    if (!ready[dev]) {
-        hipError_t e = hipFuncSetAttribute((const void*)conv3r_kernel<TT, NSEG, EPI, SILU, GEO, RAG>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-        ready[dev] = true;
-    }
-    hipLaunchKernelGGL((conv3r_kernel<TT, NSEG, EPI, SILU, GEO, RAG>), dim3(a.persist), dim3(512), lds, s, a);
-    return hipGetLastError();
+    return launch_lds<conv3r_kernel<TT, NSEG, EPI, SILU, GEO, RAG>>(a.persist, 512, lds, a, s);
 }
 template <class TT> static hipError_t r_epi(const ConvArgs& a, hipStream_t s) {
     if (a.ragged_planes) {  // two chunks, the second with a.ragged_planes real planes (Cin = 48): conv1 + SiLU on 8 x 48 tiles

@@ -5,16 +5,7 @@ namespace mz {
 
 template <class TT, int EPI, bool SILU = false> static hipError_t t_launch(const ConvArgs& a, hipStream_t s) {
     constexpr size_t lds = t3::lds_bytes(EPI == EPI_FUSEDMIX);
-    static bool ready[16] = {};  // per device ordinal: the dynamic-LDS limit of this instantiation has been raised
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return hipErrorInvalidDevice;
-    if (!ready[dev]) {
-        hipError_t e = hipFuncSetAttribute((const void*)conv3t_kernel<TT, EPI, SILU>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-        ready[dev] = true;
-    }
-    hipLaunchKernelGGL((conv3t_kernel<TT, EPI, SILU>), dim3(a.persist), dim3(512), lds, s, a);
-    return hipGetLastError();
+    return launch_lds<conv3t_kernel<TT, EPI, SILU>>(a.persist, 512, lds, a, s);
 }
 template <class TT> static hipError_t t_epi(const ConvArgs& a, hipStream_t s) {
     switch (a.epi) {

@@ -1,6 +1,7 @@
-// Device-side building blocks shared by the kernel translation units (mz_kernels.hip, mz_conv3r.hip, mz_conv3t.hip): element types,
+// Device-side building blocks shared by the kernel translation units (mz_conv32.hip, mz_<family>.hip, mz_kernels.hip): element types,
 // conversions, MFMA wrappers, LDS-DMA / LDS fragment-read primitives, the XCD-aware tile walk.
 #pragma once
+#include <type_traits>
 #include "mz_kernels.h"
 
 namespace mz {
@@ -77,6 +78,20 @@ __device__ __forceinline__ uint32_t pack_f16(float a, float b) {
     typedef float f32x2_ __attribute__((ext_vector_type(2)));
     typedef _Float16 f16x2_ __attribute__((ext_vector_type(2)));
     return __builtin_bit_cast(uint32_t, __builtin_convertvector(f32x2_{a, b}, f16x2_));
+}
+// two 16-bit values of one 32-bit word <-> float (the 16x16x32 kernels' fused gates, the mix kernels' blends)
+template <class TT> __device__ __forceinline__ void unpack2(uint32_t v, float& lo, float& hi) {
+    if constexpr (TT::IS_BF16) {
+        lo = __builtin_bit_cast(float, v << 16);
+        hi = __builtin_bit_cast(float, v & 0xffff0000u);
+    } else {
+        lo = (float)__builtin_bit_cast(_Float16, (uint16_t)(v & 0xffff));
+        hi = (float)__builtin_bit_cast(_Float16, (uint16_t)(v >> 16));
+    }
+}
+template <class TT> __device__ __forceinline__ uint32_t pack2(float lo, float hi) {
+    if constexpr (TT::IS_BF16) return pack_bf16(lo, hi);
+    else return pack_f16(lo, hi);
 }
 
 // 4 consecutive channels <-> memory
@@ -228,6 +243,14 @@ template <int NT> __device__ __forceinline__ void wait_frags(Frags<NT>& f) {
                      : "+v"(f.x0), "+v"(f.x1), "+v"(f.w[0]), "+v"(f.w[1]), "+v"(f.w[2]), "+v"(f.w[3])::"memory");
 }
 
+// The 16x16x32 kernels' counted wait for a pair of weight fragments (conv3s_kernel, mix16_kernel, mix16b_kernel).
+// LDS reads return in order, so lgkmcnt(N) = "everything but the N youngest reads has landed" (no scalar load is in
+// flight inside the K loop: its straight-line code uses no kernel argument).  The registers named "+v" are the
+// ones the following MFMAs may use; the N youngest stay untouched until a later wait.
+template <int N> __device__ __forceinline__ void wait_w16(u32x4& w0, u32x4& w1) {
+    asm volatile("s_waitcnt lgkmcnt(%2)" : "+v"(w0), "+v"(w1) : "n"(N) : "memory");
+}
+
 // ================================================================================================
 // workgroup -> (pixel tile, N tile).  Consecutive logical ids land on one XCD (bijective remap of the round-robin
 // dispatch), and within an XCD's contiguous id range tiles are walked in gm x gn groups: the ~32 workgroups that are
@@ -247,6 +270,21 @@ __device__ __forceinline__ int fdiv(int x, int d, float inv) {
 
 // logical id -> tile (the group walk)
 __device__ __forceinline__ bool tile_of(const ConvArgs& a, int L, int& mtile, int& ntile) {
+    const int gsz = a.gm * a.gn;
+    const int group = fdiv(L, gsz, a.inv_gsz), within = L - group * gsz;
+    const int gi_n = fdiv(group, a.groups_m, a.inv_groups_m), gi_m = group - gi_n * a.groups_m;
+    const int mi = fdiv(within, a.gn, a.inv_gn), ni = within - mi * a.gn;
+    mtile = gi_m * a.gm + mi;
+    ntile = gi_n * a.gn + ni;
+    return mtile < a.mtiles && ntile < a.ntiles;
+}
+
+// this workgroup's tile of a per-tile launch (one workgroup per id of the group walk)
+__device__ __forceinline__ bool map_tile(const ConvArgs& a, int& mtile, int& ntile) {
+    const int nblk = gridDim.x;
+    const int bid = blockIdx.x;
+    const int q = nblk >> 3, rem = nblk & 7, xcd = bid & 7, pos = bid >> 3;
+    const int L = (xcd < rem ? xcd * (q + 1) : rem * (q + 1) + (xcd - rem) * q) + pos;
     const int gsz = a.gm * a.gn;
     const int group = fdiv(L, gsz, a.inv_gsz), within = L - group * gsz;
     const int gi_n = fdiv(group, a.groups_m, a.inv_groups_m), gi_m = group - gi_n * a.groups_m;
@@ -376,6 +414,46 @@ __device__ __forceinline__ void tile_rc(const ConvArgs& a, int trem, int& tyi, i
     const int qx = rows == 4 ? rem >> 2 : (rows == 3 ? (int)(((unsigned)rem * 43691u) >> 17) : (rows == 2 ? rem >> 1 : rem));
     txi = __builtin_amdgcn_readfirstlane(qx);
     tyi = 4 * br + rem - txi * rows;
+}
+
+// ---- host side of a launch, shared by the launchers (mz_<family>.hip) -----------------------------------------------------------
+// KERNEL<<<grid, block, lds>>>(a).  The first launch of an instantiation on a device raises its dynamic-LDS limit to `lds`
+// (hipFuncSetAttribute applies to the CURRENT device); `lds` is a constant of the instantiation.
+template <auto KERNEL> hipError_t launch_lds(int grid, int block, size_t lds, const ConvArgs& a, hipStream_t s) {
+    static bool ready[kMaxDevices] = {};  // per device ordinal
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDevices) return hipErrorInvalidDevice;
+    if (!ready[dev]) {
+        hipError_t e = hipFuncSetAttribute((const void*)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return e;
+        ready[dev] = true;
+    }
+    hipLaunchKernelGGL(KERNEL, dim3(grid), dim3(block), lds, s, a);
+    return hipGetLastError();
+}
+// Runtime (dtype, nt in 1..MAXNT, mode in {MA, MB}) -> f(TT{}, NT, MODE) with NT and MODE as std::integral_constant; anything else is
+// hipErrorInvalidValue.
+template <int MAXNT, int MA, int MB, class F> hipError_t dispatch(int dtype, int nt, int mode, F f) {
+    auto by_mode = [&](auto tt, auto n) {
+        if (mode == MA) return f(tt, n, std::integral_constant<int, MA>{});
+        if (mode == MB) return f(tt, n, std::integral_constant<int, MB>{});
+        return hipErrorInvalidValue;
+    };
+    auto by_nt = [&](auto tt) {
+        switch (nt) {
+            case 1: return by_mode(tt, std::integral_constant<int, 1>{});
+            case 2: return by_mode(tt, std::integral_constant<int, 2>{});
+            case 3: return by_mode(tt, std::integral_constant<int, 3>{});
+            case 4: if constexpr (MAXNT >= 4) return by_mode(tt, std::integral_constant<int, 4>{});
+        }
+        return hipErrorInvalidValue;
+    };
+    switch (dtype) {
+        case DT_F32: return by_nt(TF32{});
+        case DT_BF16: return by_nt(TBF16{});
+        case DT_F16: return by_nt(TF16{});
+    }
+    return hipErrorInvalidValue;
 }
 
 }  // namespace mz

@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "../../include/mewzoom_hip.h"
+#include "mz_geo.h"
 #include "mz_pack.h"
 
 using namespace mz;
@@ -40,8 +41,7 @@ static int fail(int code, const char* fmt, ...) {
         if (e_ != hipSuccess) return fail(MZ_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
     } while (0)
 
-// Per-device state: the raised dynamic-LDS limits (hipFuncSetAttribute applies to the CURRENT device) and the CU count.
-static constexpr int kMaxDevices = 64;
+// Per-device state: the CU count (kMaxDevices: mz_kernels.h; the launchers raise their kernels' dynamic-LDS limits themselves)
 static int g_dev_ready[kMaxDevices];  // 0 unknown, 1 ok
 static int g_dev_cus[kMaxDevices];
 
@@ -50,8 +50,6 @@ static int ensure_device_ready() {
     if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return fail(MZ_ERR_NO_DEVICE, "no HIP device visible");
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDevices) return fail(MZ_ERR_NO_DEVICE, "bad current device");
     if (g_dev_ready[dev] == 1) return MZ_OK;
-    hipError_t e = init_kernels();
-    if (e != hipSuccess) return fail(MZ_ERR_HIP, "kernel init failed: %s", hipGetErrorString(e));
     int cus = 0;
     if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 0;
     g_dev_cus[dev] = cus / 8 * 8;
@@ -679,13 +677,13 @@ static void pick_order(ConvArgs& a, const ConvW& c, double act_bytes, const Knob
 // whether a buffer happens to be allocated), the knobs, the shape and the CU count only -- no HIP call: mz_debug_select() runs them
 // without a GPU, and tests/test_select_cpu.py pins their table.
 // ------------------------------------------------------------------------------------------------
-enum Launcher { L_CONV, L_CONV3R, L_CONV3T, L_MIX16, L_MIX16B };
-
 struct KernelChoice {
-    const char* name = nullptr;  // what mz_debug_last_kernel() reports; nullptr = the launch is refused (mz_last_error() says why)
-    int launcher = L_CONV;
-    int mode = MODE_GEMM1;       // launch_conv's ConvMode; 3x3: that of the 512 / 256-pixel kernels even where conv3r / conv3t run
-                                 // (it also sizes the fused mix's x ring, ConvArgs::x_via_lds)
+    bool ok = false;             // false = the launch is refused (mz_last_error() says why)
+    int kernel = K_CONV256;      // Kernel (mz_kernels.h): the family Runner::launch launches
+    int mode = MODE_GEMM1;       // ConvMode of the 256 / 512-pixel kernels; 3x3: theirs even where conv3r / conv3t run (it also sizes the
+                                 // fused mix's x ring, ConvArgs::x_via_lds)
+    bool fused = false;          // 3x3: conv2 + AdaptiveResidualMix in one launch (EPI_FUSEDMIX)
+    bool mix = false;            // an unfused AdaptiveResidualMix (choose_mix)
     int th = 0, tw = 0;          // 3x3: pixel tile
     int geo = 0;                 // conv3r_kernel: 1 = 8 x 40 tiles
     int ragged_planes = 0;       // conv3r_kernel's ragged variant (Cin = 48)
@@ -694,6 +692,25 @@ struct KernelChoice {
     bool tile_list = false;      // walks a tile table (conv3r / conv3t, Runner::tile_table)
     int persist = 0;             // persistent workgroups at most; 0 = one workgroup per tile
 };
+
+// What mz_debug_last_kernel() and mz_debug_select() report for a choice: the family that is launched and its variant.
+static const char* kernel_name(const KernelChoice& ch) {
+    if (!ch.ok) return nullptr;
+    switch (ch.kernel) {
+        case K_CONV256: return ch.mix ? "conv_kernel_mix" : "conv_kernel";
+        // A fused layer that qualifies for a persistent launch but not for the 16x16x32 kernels (MZ_NO_S16=1, or K padding beyond
+        // MZ_KPAD_PCT) runs conv3w_kernel<.., FUSE> -- conv3p has no fused variant -- and has always been REPORTED as "conv3p": rows of
+        // tests/test_select_cpu.py pin that string.  Renaming it to "conv3w_fused" changes those rows and is a change of its own.
+        case K_CONV3W: return ch.fused ? (ch.persist > 0 ? "conv3p" : "conv3w_fused") : "conv3w";
+        case K_CONV3P: return "conv3p";
+        case K_CONV3S: return ch.fused ? "conv3s_fused" : "conv3s";
+        case K_CONV3R: return ch.fused ? "conv3r_fused" : ch.ragged_planes ? "conv3r_ragged" : ch.geo ? "conv3r_8x40" : "conv3r";
+        case K_CONV3T: return ch.fused ? "conv3t_fused" : "conv3t";
+        case K_MIX16: return "mix16";
+        case K_MIX16B: return "mix16b";
+    }
+    return nullptr;
+}
 
 // workgroups of a persistent launch: one per CU, a multiple of 8 (one equal share per XCD).  Knobs::persist overrides: 0 = one
 // workgroup per tile everywhere (A/B timing); n = force n (tests use 8 / 16 so that small images walk several tiles per workgroup).
@@ -709,6 +726,7 @@ static bool fuse_mix(const Knobs& k, const BlockW& b) { return b.fused && k.wide
 static KernelChoice choose_conv3(const Knobs& k, int dtype, const ConvW& c, const ConvW* mixf, int epi, int silu, bool film,
                                  int B, int H, int W, int Hout, int Wout, int cus) {
     KernelChoice ch;
+    const bool fused = epi == EPI_FUSEDMIX;
     const int wgs = persistent_workgroups(k, cus);
     const double px = (double)H * W;  // the offset guards hold inside one image
     // tile shape: the 512-pixel kernels (NT <= 3) in the shape that wastes fewer padded pixels, else 8 x 32
@@ -733,15 +751,13 @@ static KernelChoice choose_conv3(const Knobs& k, int dtype, const ConvW& c, cons
     const bool halo_fits = offsets_fit(4, px);  // 32-bit halo offsets span four planes
     const int p0 = c.cp0 * dtype_size(dtype) / 16;
     // conv3r / conv3t walk a tile list whose entries hold image, N tile and pixel coordinates in 16 bits each
-    auto listed = [&](const char* name, int launcher, int lth, int ltw, int layout, int gate) {
-        ch.name = name; ch.launcher = launcher; ch.th = lth; ch.tw = ltw;
+    auto listed = [&](int kernel, int lth, int ltw, int layout, int gate) {
+        ch.kernel = kernel; ch.fused = fused; ch.th = lth; ch.tw = ltw;
         ch.layout = layout; ch.gate = gate;
         ch.tile_list = true;
         ch.persist = wgs;
-        if (B >= 65536 || c.ntiles >= 65536 || (H + lth - 1) / lth * lth >= 65536 || (W + ltw - 1) / ltw * ltw >= 65536) {
-            fail(MZ_ERR_INVALID_ARGUMENT, "tile table: image, batch or N-tile index beyond 16 bits");
-            ch.name = nullptr;
-        }
+        ch.ok = B < 65536 && c.ntiles < 65536 && (H + lth - 1) / lth * lth < 65536 && (W + ltw - 1) / ltw * ltw < 65536;
+        if (!ch.ok) fail(MZ_ERR_INVALID_ARGUMENT, "tile table: image, batch or N-tile index beyond 16 bits");
         return ch;
     };
 
@@ -752,7 +768,7 @@ static KernelChoice choose_conv3(const Knobs& k, int dtype, const ConvW& c, cons
     const bool t_fuse = epi == EPI_FUSEDMIX && k.fuse16 && mixf && mixf->has(PK_GATE16T);
     if (k.t && s16 && !film && c.has(PK_CONV16T) && c.ntiles == 1 && (c.nchunks32 == 3 || c.nchunks32 >= 6) &&
         (epi == EPI_STORE || t_fuse) && halo_fits && offsets_fit(6, px))
-        return listed(t_fuse ? "conv3t_fused" : "conv3t", L_CONV3T, 12, 64, PK_CONV16T, t_fuse ? PK_GATE16T : PK_MAIN);
+        return listed(K_CONV3T, 12, 64, PK_CONV16T, t_fuse ? PK_GATE16T : PK_MAIN);
 
     // conv3r_kernel's ragged variant: conv1 + SiLU with Cin = 48 (two 32-channel chunks, the second with two real planes) into 96-channel
     // N tiles.  The kernel it replaces (conv3p_kernel: 32x32x16 MFMA, exact 16-channel chunks) sums in another order, so the choice
@@ -760,7 +776,7 @@ static KernelChoice choose_conv3(const Knobs& k, int dtype, const ConvW& c, cons
     if (k.r && k.r2 && s16 && !film && c.nt == 3 && c.has(PK_CONV16) && epi == EPI_STORE && silu && c.nchunks32 == 2 && c.cp0 == 48 &&
         halo_fits && offsets_fit(12, px)) {
         ch.ragged_planes = (c.cp0 - 32) / 8;
-        return listed("conv3r_ragged", L_CONV3R, 8, 48, PK_CONV16, PK_MAIN);
+        return listed(K_CONV3R, 8, 48, PK_CONV16, PK_MAIN);
     }
 
     // conv3r_kernel's fused variant (conv2 + AdaptiveResidualMix, C = 96): six or more chunks (one pixel fragment's gate GEMM and blend
@@ -770,7 +786,7 @@ static KernelChoice choose_conv3(const Knobs& k, int dtype, const ConvW& c, cons
     // (ultrazoom_amd/tiling.py) breaks.
     if (k.r && k.fuse16 && epi == EPI_FUSEDMIX && s16 && c.nt == 3 && c.ntiles == 1 && c.has(PK_CONV16) && mixf && mixf->has(PK_GATE16R) &&
         mixf->nchunks32 == c.nt && c.nchunks32 >= 6 && p0 % 4 == 0 && k_fits && halo_fits && offsets_fit(12, px))
-        return listed("conv3r_fused", L_CONV3R, 8, 48, PK_CONV16, PK_GATE16R);
+        return listed(K_CONV3R, 8, 48, PK_CONV16, PK_GATE16R);
 
     // conv3r_kernel: 96-channel N tiles, any chunk count >= 3 of four whole planes (its halo loads carry the plane in the scalar offset,
     // which the hardware's range check does not cover); its stores carry 32-bit offsets inside 12 output planes / one D2S target image.
@@ -786,13 +802,13 @@ static KernelChoice choose_conv3(const Knobs& k, int dtype, const ConvW& c, cons
         const int geo = pad40 < pad48 ? 1 : 0;
         if ((geo ? pad40 : pad48) <= pads) {
             ch.geo = geo;
-            return listed(geo ? "conv3r_8x40" : "conv3r", L_CONV3R, 8, geo ? 40 : 48, PK_CONV16, PK_MAIN);
+            return listed(K_CONV3R, 8, geo ? 40 : 48, PK_CONV16, PK_MAIN);
         }
     }
 
     // the 512-pixel kernels (per tile: conv3w; persistent: conv3p, or conv3s on the 16x16x32 MFMA) and the 256-pixel conv_kernel
     ch.th = th; ch.tw = tw;
-    const bool fused = epi == EPI_FUSEDMIX;
+    ch.fused = fused;
     const bool fuse16 = fused && mixf && mixf->has(PK_GATE16) && k.fuse16 &&
                         mixf->nchunks32 == c.nt;  // x K-steps == z K-steps (always so for C <= 96)
     if (mode != MODE_CONV3 && (epi == EPI_STORE || epi == EPI_D2S || fuse16) && wgs > 0) {
@@ -816,27 +832,27 @@ static KernelChoice choose_conv3(const Knobs& k, int dtype, const ConvW& c, cons
                                       "N tile, input channels within 12.5 %% of a multiple of 32");
         return ch;
     }
-    ch.launcher = L_CONV;
-    ch.name = mode == MODE_CONV3 ? "conv_kernel"
-              : ch.persist > 0  ? (ch.layout != PK_MAIN ? (fused ? "conv3s_fused" : "conv3s") : "conv3p")
-                                : (fused ? "conv3w_fused" : "conv3w");
+    // conv3p has no fused variant: a fused layer off the 16x16x32 kernels stays on the per-tile kernel (kernel_name() has the history)
+    ch.kernel = mode == MODE_CONV3 ? K_CONV256 : ch.persist == 0 || (fused && ch.layout == PK_MAIN) ? K_CONV3W : ch.layout != PK_MAIN ? K_CONV3S : K_CONV3P;
+    ch.ok = true;
     return ch;
 }
 
 // AdaptiveResidualMix of C channels (c: the [C, 2C] gate weights, SRC_CONCAT) over B x H x W pixels
 static KernelChoice choose_mix(const Knobs& k, int dtype, const ConvW& c, int B, int H, int W, int cus) {
     KernelChoice ch;
+    ch.ok = ch.mix = true;
     ch.mode = MODE_GEMM1;
     // mix16_kernel: C = k * 192 (192-channel N tiles, x / z straight into MFMA operands), 32-bit buffer offsets inside each tensor;
     // mix16b_kernel (C = 192) is persistent, also under MZ_NO_PERSIST=1: it has no per-tile form
     const bool mix16 = c.has(PK_MIX16) && offsets_fit(c.cp0 * dtype_size(dtype) / 16.0, (double)B * H * W);
     const int wgs = k.persist > 0 ? k.persist : cus;
     if (mix16 && k.mix16b && c.has(PK_MIX16B) && wgs > 0) {
-        ch.name = "mix16b"; ch.launcher = L_MIX16B; ch.layout = PK_MIX16B; ch.persist = wgs;
+        ch.kernel = K_MIX16B; ch.layout = PK_MIX16B; ch.persist = wgs;
     } else if (mix16) {
-        ch.name = "mix16"; ch.launcher = L_MIX16; ch.layout = PK_MIX16;
+        ch.kernel = K_MIX16; ch.layout = PK_MIX16;
     } else {
-        ch.name = "conv_kernel_mix"; ch.launcher = L_CONV;
+        ch.kernel = K_CONV256;
     }
     return ch;
 }
@@ -884,7 +900,6 @@ struct Runner {
         a.nchunks = c.nchunks;
         a.nchunks_real = c.nchunks_real;
         a.ntiles = c.ntiles;
-        a.use_glds = 1;  // read by no kernel today; kept so that the argument block stays as it was
     }
 
     // conv3r_kernel / conv3t_kernel: the launch's tiles in walk order as a table in HBM (ConvArgs::tile_tab), so that the kernels'
@@ -912,15 +927,22 @@ struct Runner {
         a.grid = it->second.second;
     }
 
-    void launch(const KernelChoice& ch, const ConvArgs& a, int nt, ProfRec* r) {
-        g_last_kernel = ch.name;
-        switch (ch.launcher) {
-            case L_CONV3T: check(launch_conv3t(dtype, a, s), ch.name); break;
-            case L_CONV3R: check(launch_conv3r(dtype, a, s), ch.name); break;
-            case L_MIX16: check(launch_mix16(dtype, a, s), ch.name); break;
-            case L_MIX16B: check(launch_mix16b(dtype, a, s, ch.persist), ch.name); break;
-            default: check(launch_conv(dtype, ch.mode, nt, a, s), ch.name); break;
+    hipError_t launch_kernel(const KernelChoice& ch, const ConvArgs& a, int nt) {
+        switch (ch.kernel) {
+            case K_CONV256: return launch_conv256(dtype, ch.mode, nt, a, s);
+            case K_CONV3W: return launch_conv3w(dtype, ch.mode, nt, a, s);
+            case K_CONV3P: return launch_conv3p(dtype, ch.mode, nt, a, s);
+            case K_CONV3S: return launch_conv3s(dtype, ch.mode, nt, a, s);
+            case K_CONV3R: return launch_conv3r(dtype, a, s);
+            case K_CONV3T: return launch_conv3t(dtype, a, s);
+            case K_MIX16: return launch_mix16(dtype, a, s);
+            case K_MIX16B: return launch_mix16b(dtype, a, s, ch.persist);
         }
+        return hipErrorInvalidValue;
+    }
+    void launch(const KernelChoice& ch, const ConvArgs& a, int nt, ProfRec* r, const char* what = nullptr) {
+        if (!what) what = g_last_kernel = kernel_name(ch);  // `what` given: a launch that is neither a 3x3 convolution nor a mix
+        check(launch_kernel(ch, a, nt), what);
         prof_end(r);
     }
 
@@ -930,7 +952,7 @@ struct Runner {
                const ConvW* mixf = nullptr, const void* xin = nullptr, float alpha = 0.f) {
         if (rc) return;
         const KernelChoice ch = choose_conv3(knobs, dtype, c, mixf, epi, silu, film_gamma != nullptr, B, H, W, Hout, Wout, cus);
-        if (!ch.name) { rc = MZ_ERR_INVALID_ARGUMENT; return; }
+        if (!ch.ok) { rc = MZ_ERR_INVALID_ARGUMENT; return; }
         ConvArgs a;
         base_args(a, c);
         if (zero_override) a.zero = zero_override;
@@ -953,8 +975,7 @@ struct Runner {
             a.wmix = mixf->packed[PK_MAIN].p;
             a.mix_pieces = mixf->nchunks * mixf->nt;
             {   // room for the 8 compute waves' x fragments next to the gate weights in ring slots 1-2?
-                const int a_slot = (ch.mode == MODE_C3W16 ? 2 * 640 : 2 * 672) * 16;
-                const int slot = a_slot + 9 * c.nt * 1024;
+                const int slot = ch.mode == MODE_C3W16 ? stage_bytes<MODE_C3W16>(c.nt) : stage_bytes<MODE_C3W8>(c.nt);
                 const int ncx = a.p1 / 2;
                 a.x_via_lds = (a.mix_pieces * 1024 + 8 * ncx * 1024 <= 2 * slot) ? 1 : 0;
             }
@@ -967,7 +988,6 @@ struct Runner {
         const double px = (double)B * H * W;
         pick_order(a, c, px * c.cp0 * sz, knobs);
         if (ch.layout != PK_MAIN) {
-            a.s16 = 1;
             a.wpk16 = c.packed[ch.layout].p;
             a.nchunks16 = pack_shape(c, ch.layout).nchunks;
             if (fused) a.wmix16 = mixf->packed[ch.gate].p;
@@ -1031,8 +1051,9 @@ struct Runner {
         const double sz = dtype_size(dtype);
         pick_order(a, c, (double)B * H * W * c.cp0 * sz, knobs, 64);
         ProfRec* r = prof_begin(2, a, c, 2.0 * (double)npix * 4.0 * c.cin * c.cout, ((double)B * H * W * c.cin + (double)npix * c.cout) * sz);
-        check(launch_conv(dtype, MODE_GEMM1, c.nt, a, s), "crush launch");
-        prof_end(r);
+        KernelChoice ch;  // conv_kernel's 1x1 mode is the only kernel that gathers the 2x2 patches
+        ch.ok = true; ch.kernel = K_CONV256; ch.mode = MODE_GEMM1;
+        launch(ch, a, c.nt, r, "crush launch");
     }
 };
 
@@ -1395,10 +1416,10 @@ extern "C" const char* mz_debug_select(int dtype, int op, int cin, int cout, int
     BlockW b;
     const ConvW* c = plan_debug_layer(b, dtype, op, cin, cout);
     if (!c) return nullptr;
-    if (op == 7) return choose_mix(k, dtype, *c, B, H, W, cus).name;
+    if (op == 7) return kernel_name(choose_mix(k, dtype, *c, B, H, W, cus));
     const int epi = op == 2 ? EPI_D2S : op == 3 ? EPI_FINAL : op == 6 && fuse_mix(k, b) ? EPI_FUSEDMIX : EPI_STORE;
     const int up = op == 2 || op == 3 ? 2 : 0;  // D2S / FINAL: into 2H x 2W
-    return choose_conv3(k, dtype, *c, epi == EPI_FUSEDMIX ? &b.mixf : nullptr, epi, op == 0, op == 5, B, H, W, up * H, up * W, cus).name;
+    return kernel_name(choose_conv3(k, dtype, *c, epi == EPI_FUSEDMIX ? &b.mixf : nullptr, epi, op == 0, op == 5, B, H, W, up * H, up * W, cus));
 }
 
 // Host-only (no GPU): packing `layout` of one layer (mz_debug_select's ops; 8 = the fused gate of a block's conv2), as pack_kernel writes

@@ -1,4 +1,4 @@
-// Internal interface between the host runtime (mz_host.cpp) and the gfx950 kernels (mz_kernels.hip).
+// Internal interface between the host runtime (mz_host.cpp) and the gfx950 kernels (one family per header mz_<family>.h, launchers in the .hip units).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -69,8 +69,8 @@ struct ConvArgs {
     int Hi, Wi;        // FINAL: img size
     int clamp;
     int io_u8;         // EPI_FINAL: img and out are uint8 images (scaled by 1/255 on read, x255 + 0.5 on write)
-    int persist;       // > 0: launch the persistent wide 3x3 kernel with this many workgroups (a multiple of 8)
-    int s16;           // persistent launches of 16-bit types: use the 16x16x32-MFMA kernel (needs wpk16)
+    int persist;       // the persistent kernels: workgroups launched (a multiple of 8)
+    int s16;           // read by no kernel and no launcher: kept, like use_glds below, so that every field keeps its kernel-argument offset
     const void* wpk16; // weights packed for it: [ntile][32-channel chunk][tap][2*nt][64 lanes][16 B]
     int nchunks16;     // 32-channel chunks
     const void* tile_tab;  // conv3r / conv3t: the launch's tiles in walk order, uint2 {y0 | x0 << 16, image | N tile << 16} each, padded with
@@ -81,21 +81,58 @@ struct ConvArgs {
     const void* wmix16; // EPI_FUSEDMIX on the 16x16x32 kernel: gate weights packed [2*nt K-steps][2*nt][64 lanes][16 B]
     const float* film_gamma;  // EPI_STORE on conv3s_kernel only: per-image per-channel affine gamma * y + beta ahead of the SiLU
     const float* film_beta;   //   (float [B][cp_out], pad channels zero); nullptr = off.  No reference counterpart.
-    int use_glds;      // stage through global_load_lds (1) or through registers (0)
+    int use_glds;      // read by no kernel and no launcher
     unsigned long long* dbg;  // -DMZ_DIAG builds (mz_diag.h): cycle counters of one workgroup of conv3r_kernel
 };
 
-size_t conv_lds_bytes(int mode, int nt);
 // picks NT (32*NT output channels per workgroup) for a logical padded N
-int choose_nt(int n_padded);
-int gemm1_chunks_per_stage();
-hipError_t launch_conv(int dtype, int mode, int nt, const ConvArgs& a, hipStream_t s);
+inline int choose_nt(int n_padded) {
+    // smallest padded N wins; ties prefer 3, 2, 4, 1 (4 needs 94 KiB of LDS: one workgroup per CU)
+    const int order[4] = {3, 2, 4, 1};
+    int best = 1, best_n = 1 << 30;
+    for (int i = 0; i < 4; ++i) {
+        const int bn = 32 * order[i];
+        const int padded = (n_padded + bn - 1) / bn * bn;
+        if (padded < best_n) {
+            best_n = padded;
+            best = order[i];
+        }
+    }
+    return best;
+}
+
+// ---- launchers: one per kernel family, next to the family's instantiations (mz_conv32.hip for the three 32x32-MFMA families, else mz_<family>.hip).  The host chooses the family (mz_host.cpp:
+// choose_conv3 / choose_mix -> KernelChoice::kernel) and Runner::launch switches over it; a launcher launches ITS family and answers
+// hipErrorInvalidValue to arguments that do not fit it.  The first launch of an instantiation on a device raises its dynamic-LDS limit
+// (launch_lds(), mz_device.h).
+enum Kernel : int {
+    K_CONV256,  // conv_kernel: the image head, mixes for C <= 96, PixelCrush
+    K_CONV3W,   // conv3w_kernel: 512-pixel tiles, one workgroup per tile
+    K_CONV3P,   // conv3p_kernel: the same, persistent
+    K_CONV3S,   // conv3s_kernel: persistent, 16x16x32 MFMA
+    K_CONV3R,   // conv3r_kernel: 96-channel N tiles, role-alternating waves
+    K_CONV3T,   // conv3t_kernel: one N tile of <= 48 channels
+    K_MIX16,    // mix16_kernel
+    K_MIX16B,   // mix16b_kernel
+};
+constexpr int kMaxDevices = 64;  // device ordinals with per-device state (the raised LDS limits, the host's CU counts)
+// a launch that walks tiles in gm x gn groups: a non-empty grid whose ids fdiv() can divide (dividends below 2^24)
+inline bool walk_ok(const ConvArgs& a) {
+    return a.mtiles > 0 && a.ntiles > 0 && a.gm > 0 && a.gn > 0 && a.grid > 0 && a.grid < (1 << 24);
+}
+// conv_kernel<TT, NT, mode>, mode = MODE_CONV3 / MODE_GEMM1, nt = 1..4: a.grid workgroups of 256 threads
+hipError_t launch_conv256(int dtype, int mode, int nt, const ConvArgs& a, hipStream_t s);
+// The 512-pixel kernels, mode = MODE_C3W16 / MODE_C3W8, nt = 1..3.  conv3w: a.grid workgroups, one per tile, any epilogue.  conv3p and
+// conv3s: a.persist workgroups, EPI_STORE / EPI_D2S; conv3s also EPI_FUSEDMIX, 16-bit types only, a.wpk16 / a.nchunks16 = PK_CONV16
+// (32-channel chunks), a.wmix16 = PK_GATE16.
+hipError_t launch_conv3w(int dtype, int mode, int nt, const ConvArgs& a, hipStream_t s);
+hipError_t launch_conv3p(int dtype, int mode, int nt, const ConvArgs& a, hipStream_t s);
+hipError_t launch_conv3s(int dtype, int mode, int nt, const ConvArgs& a, hipStream_t s);
 // AdaptiveResidualMix for C = k * 192 on the 16x16x32 MFMA (16-bit types): a.wpk16 / a.nchunks16 = K steps over [x ; z]
 hipError_t launch_mix16(int dtype, const ConvArgs& a, hipStream_t s);
 // C = 192 without the second read of x and z: a.wpk16 = gate weights packed as PK_MIX16B (accumulator rows in B-operand
 // order); the gate matrix stays in LDS, every wave walks its own 32-pixel units
 hipError_t launch_mix16b(int dtype, const ConvArgs& a, hipStream_t s, int workgroups);  // persistent: at most `workgroups` (one per CU)
-hipError_t init_kernels();  // raises the dynamic-LDS limits (per device)
 // conv3r_kernel (mz_conv3r.h): 3x3 convolution, 16-bit types, 96-channel N tiles (NT = 3), 8 x 48 / 8 x 40 pixel tiles, a.persist workgroups of
 // 512 threads; a.wpk16 / a.nchunks16 as for conv3s_kernel.  The two waves of every SIMD alternate between the compute
 // and the loader + epilogue role from tile to tile.  >= 3 chunks of 32 channels (odd counts included; a.ragged_planes != 0: exactly
@@ -137,8 +174,7 @@ struct PackArgs {
     int in_map;        // SrcKind
     int c0, cp0, c1;   // CONCAT / MIXF: real/padded channels of in0, real channels of in1;  PLAIN/CRUSH: c0 = cin, cp0 = padded cin
 };
-size_t packed_bytes(int taps, int nt, int ntiles, int nchunks);
-size_t conv16_lds_bytes(int mode, int nt, bool fuse);
+inline size_t packed_bytes(int taps, int nt, int ntiles, int nchunks) { return (size_t)ntiles * nchunks * taps * nt * 1024; }
 hipError_t launch_pack(const PackArgs& a, hipStream_t s);
 
 // ---- small kernels ----------------------------------------------------------------------------
