@@ -44,10 +44,12 @@
 // 36 KB of AdaptiveResidualMix gate weights resident there for the whole launch.
 //
 // LDS map: [halo 0 | halo 1] 2 x 32 KB + 3 weight slots (+ fused: 36 KB gate weights).
+//
+// conv3t_kernel (mz_conv3t.h) has the same structure around three channel fragments; the device helpers both use are in mz_relay.h.
 #pragma once
-#include <type_traits>
 #include "mz_device.h"
 #include "mz_diag.h"
+#include "mz_relay.h"
 
 namespace mz {
 namespace r3 {
@@ -153,15 +155,9 @@ __device__ __forceinline__ void group_mfmas(f32x4 (&acc)[Geo<GEO>::NPF][NF], Fra
         // its MFMAs in K order), but the chip is power-limited in this loop and holds a higher clock: deep layers -2 %, whole forward
         // -1 % against the channel-major raster order (tools/microbench/mb_order.hip).
         constexpr int pf = (n & 1) ? NPF - 1 - M / 2 : M / 2, k = ((M / 2) & 1) ? 1 - (M & 1) : (M & 1);
-        if constexpr (ZERO_C) {  // a tile's first tap WRITES the accumulators (C = 0): nobody has to clear 144 registers per tile
-            const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
-            if constexpr (TT::IS_BF16)
-                acc[pf][2 * n + k] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, f.w[GC % 3][k]), __builtin_bit_cast(bf16x8_t, f.x[xp][pf]), zero, 0, 0, 0);
-            else
-                acc[pf][2 * n + k] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8_t, f.w[GC % 3][k]), __builtin_bit_cast(f16x8_t, f.x[xp][pf]), zero, 0, 0, 0);
-        } else {
-            mma16<TT>(acc[pf][2 * n + k], f.w[GC % 3][k], f.x[xp][pf]);
-        }
+        // (a tile's first tap WRITES the accumulators (C = 0): nobody has to clear 144 registers per tile)
+        if constexpr (ZERO_C) mma16_first<TT>(acc[pf][2 * n + k], f.w[GC % 3][k], f.x[xp][pf]);
+        else mma16<TT>(acc[pf][2 * n + k], f.w[GC % 3][k], f.x[xp][pf]);
         __builtin_amdgcn_sched_barrier(0);
         if constexpr (M < 2) {
             f.w[T % 3][M] = lds_read128<(2 * t_idx + M) * 1024>(t_here ? bs.b_cur : bs.b_nxt);
@@ -234,73 +230,6 @@ __device__ __forceinline__ void gate_halves(f32x4 (&beta)[NF], const u32x4 (&xf)
         gate_halves<TT, H + 1>(beta, xf, zf, wb, wa, addr);
     }
 }
-template <class TT> __device__ __forceinline__ void unpack2r(uint32_t v, float& lo, float& hi) {
-    if constexpr (TT::IS_BF16) {
-        lo = __builtin_bit_cast(float, v << 16);
-        hi = __builtin_bit_cast(float, v & 0xffff0000u);
-    } else {
-        lo = (float)__builtin_bit_cast(_Float16, (uint16_t)(v & 0xffff));
-        hi = (float)__builtin_bit_cast(_Float16, (uint16_t)(v >> 16));
-    }
-}
-template <class TT> __device__ __forceinline__ uint32_t pack2r(float lo, float hi) {
-    if constexpr (TT::IS_BF16) return pack_bf16(lo, hi);
-    else return pack_f16(lo, hi);
-}
-
-template <int V> using ic = std::integral_constant<int, V>;
-
-// lane index, recomputed where it is needed (v_mbcnt): no register holds it across the K loop, whose 253 registers are all taken,
-// and nothing derived from it can be hoisted out of the tile loop (and spilled)
-__device__ __forceinline__ int lane_now() {
-    int l;
-    asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
-    return l;
-}
-
-// v * sigmoid(v) of TWO values: v_mul, v_exp, v_add, v_rcp, v_mul each, as ONE inline-asm block with the two chains
-// interleaved.  Inline asm because hipcc's SLP vectoriser pairs the multiplies and adds into v_pk_* (7 x slower beside the
-// partner's MFMA stream); one block because hipcc's hazard recogniser does not look inside inline asm: a VALU instruction that
-// reads the result of a transcendental one needs ONE wait state, which the other chain's instruction provides (no s_nop).
-// The same operations in the same order as silu2() / sigmoidf_(): identical bits.
-// OUT of place (the inputs stay untouched: accumulator elements need no copy into scratch registers first; the results double as
-// the chains' temporaries)
-__device__ __forceinline__ void silu_pair_to(float& ra, float& rb, const float a, const float b) {
-    asm("v_mul_f32 %0, 0xbfb8aa3b, %2\n\t"
-        "v_mul_f32 %1, 0xbfb8aa3b, %3\n\t"
-        "v_exp_f32 %0, %0\n\t"
-        "v_exp_f32 %1, %1\n\t"
-        "v_add_f32 %0, 1.0, %0\n\t"
-        "v_add_f32 %1, 1.0, %1\n\t"
-        "v_rcp_f32 %0, %0\n\t"
-        "v_rcp_f32 %1, %1\n\t"
-        "v_mul_f32 %0, %2, %0\n\t"
-        "v_mul_f32 %1, %3, %1"
-        : "=&v"(ra), "=&v"(rb)
-        : "v"(a), "v"(b));
-}
-
-// x + sigmoid(alpha) sigmoid(beta) (z - x) of TWO values, out of place: blend_()'s operations in blend_()'s order
-// (mz_device.h: v_mul, v_exp, v_fma, v_rcp, v_sub, v_fma; identical bits), as one inline-asm block of two interleaved chains for the
-// same reasons as silu_pair_to() -- left to hipcc, the SLP vectoriser pairs the adds and fmas into v_pk_add_f32 / v_pk_fma_f32.
-__device__ __forceinline__ void blend_pair_to(float& o0, float& o1, const float b0, const float b1, const float x0, const float x1,
-                                              const float z0, const float z1, const float inv_s) {
-    float d0, d1;
-    asm("v_mul_f32 %0, 0xbfb8aa3b, %4\n\t"
-        "v_mul_f32 %1, 0xbfb8aa3b, %5\n\t"
-        "v_exp_f32 %0, %0\n\t"
-        "v_exp_f32 %1, %1\n\t"
-        "v_fma_f32 %0, %0, %10, %10\n\t"
-        "v_fma_f32 %1, %1, %10, %10\n\t"
-        "v_rcp_f32 %0, %0\n\t"
-        "v_rcp_f32 %1, %1\n\t"
-        "v_sub_f32 %2, %8, %6\n\t"
-        "v_sub_f32 %3, %9, %7\n\t"
-        "v_fma_f32 %0, %0, %2, %6\n\t"
-        "v_fma_f32 %1, %1, %3, %7"
-        : "=&v"(o0), "=&v"(o1), "=&v"(d0), "=&v"(d1)
-        : "v"(b0), "v"(b1), "v"(x0), "v"(x1), "v"(z0), "v"(z1), "s"(inv_s));
-}
 
 }  // namespace r3
 
@@ -313,6 +242,7 @@ __device__ __forceinline__ void blend_pair_to(float& o0, float& o1, const float 
 template <class TT, int NSEG, int EPI, bool SILU, int GEO = 0, bool RAG = false>
 __global__ __launch_bounds__(512) void conv3r_kernel(const ConvArgs a) {
     using namespace r3;
+    using namespace relay;
     using S = Seg<NSEG>;
     using GG = Geo<GEO>;
     constexpr int NPF = GG::NPF, TW = GG::TW, ROWW = GG::ROWW, NPIX = GG::NPIX;
@@ -331,8 +261,8 @@ __global__ __launch_bounds__(512) void conv3r_kernel(const ConvArgs a) {
     // ---- tile walk: the host lists the launch's tiles in walk order (mz_host.cpp: tile_table(); a.grid entries of eight bytes, the
     // group walk of mz_device.h with the padding ids dropped).  XCD x owns the x-th eighth of the list, its workgroups stride through it.
     // Tile coordinates come out of the table with ONE scalar load per tile, requested two tiles ahead at the start of a helper phase:
-    // the divisions of tile_of_s() / tile_rc_s() (three chains of ~50 scalar instructions per phase, at ~5 cycles each in the role
-    // that is the critical path of the short tiles) are gone from the kernel. ----
+    // the divisions of the group walk (three chains of ~50 scalar instructions per phase, at ~5 cycles each in the role that is the
+    // critical path of the short tiles) are gone from the kernel.  (twin: conv3t_kernel, mz_conv3t.h) ----
     const int xcd = blockIdx.x & 7, pos = blockIdx.x >> 3, step = gridDim.x >> 3;
     const int q = a.grid >> 3, rem = a.grid & 7;
     const int cnt = q + (xcd < rem ? 1 : 0);
@@ -383,7 +313,7 @@ __global__ __launch_bounds__(512) void conv3r_kernel(const ConvArgs a) {
     // may see the per-lane offset only, so all four planes of every chunk must exist: Cin % 32 == 0 (the host guards).
     uint32_t hoff[2];
     const char* img_l = nullptr;
-    auto set_load_tile = [&](const TileE e) __attribute__((always_inline)) {
+    auto set_load_tile = [&](const TileE e) __attribute__((always_inline)) {  // (twin: conv3t_kernel, with its own constants)
         int b, y0, x0;
         tile_origin(e, b, y0, x0);
         img_l = (const char*)a.in0 + (long long)b * a.p0 * plane_in;
@@ -483,7 +413,7 @@ __global__ __launch_bounds__(512) void conv3r_kernel(const ConvArgs a) {
 #pragma unroll
             for (int n = 0; n < NT; ++n) eoff[n] = (uint32_t)(4 * n + lane_cu) * (uint32_t)plane_o;  // planes that do not exist fall out of range
             if constexpr (FUSE) {
-                // x in ACCUMULATOR layout: channels 16 nf + 4 g .. + 3 of the lane's pixel = 8 bytes (g & 1) of plane 2 nf + (g >> 1)
+                // (twin: conv3t_kernel's epi_setup) x in ACCUMULATOR layout: channels 16 nf + 4 g .. + 3 of the lane's pixel = 8 bytes (g & 1) of plane 2 nf + (g >> 1)
                 const unsigned long long xb = (unsigned long long)(uintptr_t)((const char*)a.in1 + (long long)d_b * a.p1 * plane_o);
                 xrsrc[0] = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)xb);
                 xrsrc[1] = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)((xb >> 32) & 0xffffu));
@@ -530,12 +460,7 @@ __global__ __launch_bounds__(512) void conv3r_kernel(const ConvArgs a) {
             pa[h] = pack_pair<TT>(f32x2{a0, a1});
             pb[h] = pack_pair<TT>(f32x2{b0, b1});
         }
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            const auto sw = __builtin_amdgcn_permlane16_swap(pa[h], pb[h], false, false);
-            o[h] = sw[0];
-            o[2 + h] = sw[1];
-        }
+        o = swap_packed(pa, pb);
     };
     auto epi_store = [&](auto e_tag, const u32x4& o) __attribute__((always_inline)) {
         constexpr int E = decltype(e_tag)::value;
@@ -572,7 +497,7 @@ __global__ __launch_bounds__(512) void conv3r_kernel(const ConvArgs a) {
 #pragma unroll
         for (int nf = 0; nf < NF; ++nf) {
             const uint32_t o = inside ? off + (uint32_t)(2 * nf) * (uint32_t)plane_o : 0xffffffffu;  // planes >= p1 fall out of range: zeros
-            // Inline asm (as conv3t_kernel): hipcc's waitcnt pass must not see these loads.  It cannot count the conditionally issued DMA
+            // Inline asm (twin: conv3t_kernel's fuse_x / x_landed): hipcc's waitcnt pass must not see these loads.  It cannot count the conditionally issued DMA
             // pieces that follow them and waited with vmcnt(0) in front of the gate step -- for the NEXT pixel fragment's loads, issued a
             // few hundred cycles earlier, whose lines come out of HBM.  The request is a whole chunk older than its use: the closing
             // vmcnt(0) of the gate step it precedes covers it; x_landed() marks the spot from which the values may be used.
@@ -618,11 +543,7 @@ __global__ __launch_bounds__(512) void conv3r_kernel(const ConvArgs a) {
         u32x4 wa[NT], wb[NT];
         gate_reads<0, 0>(wa, mix_lane);
         gate_halves<TT, 0>(acc[pf], xb, f_zb, wa, wb, mix_lane);
-        // MFMA result -> VALU read is a software hazard (8 passes: 11 wait states) that hipcc does not see into inline asm for: the blend
-        // (blend_pair_to) reads beta from inline-asm chains.  In the tile loop a whole step lies between gate and blend; in the final
-        // epilogue they follow each other directly (conv3t_kernel met the stale read there).
-        asm volatile("s_nop 7\n\ts_nop 4" ::: "memory");
-        __builtin_amdgcn_sched_barrier(0);
+        gate_settle();  // (beta is read by inline-asm chains next: in the final epilogue directly)
     };
     auto entry_whole = [&](auto e_tag) __attribute__((always_inline)) {
         if constexpr (decltype(e_tag)::value < NE) {
@@ -632,12 +553,6 @@ __global__ __launch_bounds__(512) void conv3r_kernel(const ConvArgs a) {
         }
     };
 
-    auto zero_acc = [&]() __attribute__((always_inline)) {
-#pragma unroll
-        for (int pf = 0; pf < NPF; ++pf)
-#pragma unroll
-            for (int nf = 0; nf < NF; ++nf) acc[pf][nf] = f32x4{0.f, 0.f, 0.f, 0.f};
-    };
     // fragment stream of a tile's first groups: tap 0 of chunk 0 and the weight pairs of groups 0 and 1
     auto prime = [&](int wslot, int aslot) __attribute__((always_inline)) {
         const int lane_ = lane_now();
@@ -750,7 +665,7 @@ __global__ __launch_bounds__(512) void conv3r_kernel(const ConvArgs a) {
             if constexpr (last) {
                 // the epilogue is complete: clear the accumulators and prime the fragment stream for the next tile.  Unconditional
                 // on every path into the compute role, so that the fragment registers are DEAD throughout the loader role.
-                if constexpr (FUSE) zero_acc();  // (with the tile's first tap writing the accumulators instead, hipcc spills in this variant)
+                if constexpr (FUSE) zero_acc(acc);  // (with the tile's first tap writing the accumulators instead, hipcc spills in this variant)
                 prime(next3(hs), us ^ 1);
             } else {
                 if (k + 2 == nchunks && okB) {  // the next step requests tB's first halo image
@@ -940,7 +855,7 @@ __global__ __launch_bounds__(512) void conv3r_kernel(const ConvArgs a) {
         }
     };
 
-    // ------------------------------------------------------------------------------------------------
+    // ---- the role driver (twin: conv3t_kernel) ------------------------------------------------------
     if (team == 1) {
         // prologue: chunk 0 of the first tile (halo image + the first two weight segments), published by B_0
         eA = tile_at(a_pos);
@@ -971,7 +886,7 @@ __global__ __launch_bounds__(512) void conv3r_kernel(const ConvArgs a) {
         }
         wait_vmcnt<0>();
         __builtin_amdgcn_s_barrier();  // B_0
-        if constexpr (FUSE) zero_acc();
+        if constexpr (FUSE) zero_acc(acc);
         loader_phase(ic<0>{});
         advance();
         if (a_pos >= cnt) { RS_DUMP(); return; }
@@ -982,7 +897,7 @@ __global__ __launch_bounds__(512) void conv3r_kernel(const ConvArgs a) {
         eB = tile_at(a_pos + 2 * step);
         asm volatile("" ::"s"(eD.yx), "s"(eD.bn), "s"(eA.yx), "s"(eA.bn), "s"(eB.yx), "s"(eB.bn));
         __builtin_amdgcn_s_barrier();  // B_0
-        if constexpr (FUSE) zero_acc();
+        if constexpr (FUSE) zero_acc(acc);
         prime(0, 0);
     }
     for (;;) {

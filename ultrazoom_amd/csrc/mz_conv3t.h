@@ -2,8 +2,9 @@
 // level-1 block of the 48-channel models (BASELINE configs[0] / [1]: conv2 96 -> 48 + AdaptiveResidualMix, reference
 // model.py:746-748, 773-778, 826-839), which conv3s_kernel<NT = 2> computed with N padded 48 -> 64 and its epilogue exposed.
 //
-// The structure is conv3r_kernel's (mz_conv3r.h: two teams of four waves that alternate between the compute role and the
-// loader + epilogue role from tile to tile), re-shaped around THREE channel fragments:
+// The structure is conv3r_kernel's (two teams of four waves that alternate between the compute role and the loader + epilogue role
+// from tile to tile: described at the head of mz_conv3r.h; the helpers both kernels use are in mz_relay.h), re-shaped around THREE
+// channel fragments:
 //   * wave tile 12 pixel fragments x 3 channel fragments = 36 accumulators (144 registers, as conv3r's 6 x 6): 192 pixels x 48
 //     channels per wave; workgroup tile 12 rows x 64 columns (wave w: rows 3 w .. 3 w + 2); 1080, 540, 2160 are multiples of 12 and
 //     1920, 960, 3840 of 64: no padded pixel on the 16:9 sizes.
@@ -28,13 +29,12 @@
 // Requirements (the host guards): one N tile (Cout <= 48), Cin a multiple of 32 with three or >= six chunks, 32-bit offsets inside
 // four input planes / six output planes.
 #pragma once
-#include "mz_conv3r.h"
+#include "mz_device.h"
+#include "mz_diag.h"
+#include "mz_relay.h"
 
 namespace mz {
 namespace t3 {
-
-using r3::ic;
-using r3::lane_now;
 
 constexpr int FPR = 4;                      // pixel fragments per tile row
 constexpr int RPW = 3;                      // tile rows per wave
@@ -93,15 +93,9 @@ __device__ __forceinline__ void group_mfmas(f32x4 (&acc)[NPF][NF], Frag& f, cons
         constexpr int t = GC / 2, h = GC % 2, xp = GC & 1, xq = xp ^ 1;
         constexpr int j = M / NF, i = M % NF;
         constexpr int pl = h ? GPF - 1 - j : j, pf = GPF * h + pl, nf = (j & 1) ? NF - 1 - i : i;
-        if constexpr (ZERO_C) {  // a tile's first tap WRITES the accumulators (C = 0): nobody clears 144 registers per tile
-            const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
-            if constexpr (TT::IS_BF16)
-                acc[pf][nf] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, f.w[t % 3][nf]), __builtin_bit_cast(bf16x8_t, f.x[xp][pl]), zero, 0, 0, 0);
-            else
-                acc[pf][nf] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8_t, f.w[t % 3][nf]), __builtin_bit_cast(f16x8_t, f.x[xp][pl]), zero, 0, 0, 0);
-        } else {
-            mma16<TT>(acc[pf][nf], f.w[t % 3][nf], f.x[xp][pl]);
-        }
+        // (a tile's first tap WRITES the accumulators (C = 0): nobody clears 144 registers per tile)
+        if constexpr (ZERO_C) mma16_first<TT>(acc[pf][nf], f.w[t % 3][nf], f.x[xp][pl]);
+        else mma16<TT>(acc[pf][nf], f.w[t % 3][nf], f.x[xp][pl]);
         __builtin_amdgcn_sched_barrier(0);
         if constexpr (M < GPF) {
             if constexpr (h == 0) f.x[xq][M] = lds_read128<a_off<t, GPF + M>()>(a_cur);
@@ -158,6 +152,7 @@ template <bool SHORT> constexpr int plain_count(int k, int sg) { return SHORT ? 
 template <class TT, int EPI, bool SILU>
 __global__ __launch_bounds__(512) void conv3t_kernel(const ConvArgs a) {
     using namespace t3;
+    using namespace relay;
     constexpr bool FUSE = EPI == EPI_FUSEDMIX;
     static_assert(EPI == EPI_STORE || EPI == EPI_FUSEDMIX, "plain / SiLU store or the fused mix");
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -166,7 +161,7 @@ __global__ __launch_bounds__(512) void conv3t_kernel(const ConvArgs a) {
     const int nchunks = a.nchunks16;       // 32-channel chunks: 3, or >= 6 (the host guards)
     const uint32_t lds_base = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)smem;
 
-    // ---- tile walk (as conv3r_kernel: the host's tile list, an XCD's contiguous range of it strided by the workgroups of that XCD;
+    // ---- tile walk (twin: conv3r_kernel, mz_conv3r.h: the host's tile list, an XCD's contiguous range of it strided by the workgroups of that XCD;
     // a tile's coordinates are one scalar load, requested two tiles ahead at the start of a helper phase) ----
     const int xcd = blockIdx.x & 7, pos = blockIdx.x >> 3, step = gridDim.x >> 3;
     const int q = a.grid >> 3, rem = a.grid & 7;
@@ -209,7 +204,7 @@ __global__ __launch_bounds__(512) void conv3t_kernel(const ConvArgs a) {
     // not see scalar offsets), so a tile costs four per-lane offsets.
     uint32_t hoff[4];
     const char* img_l = nullptr;
-    auto set_load_tile = [&](const TileE e) __attribute__((always_inline)) {
+    auto set_load_tile = [&](const TileE e) __attribute__((always_inline)) {  // (twin: conv3r_kernel, with its own constants)
         int b, y0, x0;
         tile_origin(e, b, y0, x0);
         img_l = (const char*)a.in0 + (long long)b * a.p0 * plane_in;
@@ -283,7 +278,7 @@ __global__ __launch_bounds__(512) void conv3t_kernel(const ConvArgs a) {
         eoff1 = (uint32_t)(2 * (g & 1) + (g >> 1)) * (uint32_t)plane_o;           // fragments 0, 1: plane 2 (g & 1) + (g >> 1) (entry16(), mz_device.h)
         eoff2 = (uint32_t)(4 + (g >> 1)) * (uint32_t)plane_o + (uint32_t)(g & 1) * 256u;  // fragment 2: plane 4 + (g >> 1), 16 pixels on for odd lane rows
         if constexpr (FUSE) {
-            // x in ACCUMULATOR layout: channels 16 nf + 4 g .. + 3 of the lane's pixel = 8 bytes (g & 1) of plane 2 nf + (g >> 1)
+            // (twin: conv3r_kernel's epi_setup) x in ACCUMULATOR layout: channels 16 nf + 4 g .. + 3 of the lane's pixel = 8 bytes (g & 1) of plane 2 nf + (g >> 1)
             const unsigned long long xb = (unsigned long long)(uintptr_t)((const char*)a.in1 + (long long)d_b * a.p1 * plane_o);
             xrsrc[0] = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)xb);
             xrsrc[1] = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)((xb >> 32) & 0xffffu));
@@ -309,7 +304,7 @@ __global__ __launch_bounds__(512) void conv3t_kernel(const ConvArgs a) {
 #pragma unroll
         for (int nf = 0; nf < NF; ++nf) {
             const uint32_t o = inside ? off + (uint32_t)(2 * nf) * (uint32_t)plane_o : 0xffffffffu;  // planes >= p1 fall out of range: zeros
-            // Inline asm: hipcc's waitcnt pass must not see these loads.  It would wait for them in front of their first use with what it
+            // Inline asm (twin: conv3r_kernel's fuse_x / x_landed): hipcc's waitcnt pass must not see these loads.  It would wait for them in front of their first use with what it
             // can count -- which is vmcnt(0) once conditional DMA pieces lie in between, i.e. for the halo image a step's closing wait
             // deliberately leaves in flight.  The request is older than that step's DMA, so the closing wait of the step it is issued in
             // covers it; x_landed() marks the spot from which the values may be used.
@@ -329,7 +324,7 @@ __global__ __launch_bounds__(512) void conv3t_kernel(const ConvArgs a) {
         }
     };
     // values of an entry, packed: out of place (accumulator elements are read where they lie), activation / blend as inline-asm pairs
-    // of scalar-f32 chains (r3::silu_pair_to / blend_pair_to: no packed-f32 arithmetic beside the partner's MFMA stream)
+    // of scalar-f32 chains (silu_pair_to() / blend_pair_to(), mz_relay.h: no packed-f32 arithmetic beside the partner's MFMA stream)
     auto packed_frag = [&](auto pf_tag, auto nf_tag, uint32_t (&o)[2]) __attribute__((always_inline)) {
         constexpr int pf = decltype(pf_tag)::value, nf = decltype(nf_tag)::value;
 #pragma unroll
@@ -337,22 +332,16 @@ __global__ __launch_bounds__(512) void conv3t_kernel(const ConvArgs a) {
             float v0 = acc[pf][nf][2 * h], v1 = acc[pf][nf][2 * h + 1];
             if constexpr (FUSE) {
                 float x0, x1, z0, z1;
-                r3::unpack2r<TT>(f_x[pf & 3][nf][h], x0, x1);
-                r3::unpack2r<TT>(f_z[nf][h], z0, z1);
-                r3::blend_pair_to(v0, v1, acc[pf][nf][2 * h], acc[pf][nf][2 * h + 1], x0, x1, z0, z1, a.inv_mix_scale);
+                unpack2r<TT>(f_x[pf & 3][nf][h], x0, x1);
+                unpack2r<TT>(f_z[nf][h], z0, z1);
+                blend_pair_to(v0, v1, acc[pf][nf][2 * h], acc[pf][nf][2 * h + 1], x0, x1, z0, z1, a.inv_mix_scale);
             }
-            if constexpr (!FUSE && SILU) r3::silu_pair_to(v0, v1, acc[pf][nf][2 * h], acc[pf][nf][2 * h + 1]);
+            if constexpr (!FUSE && SILU) silu_pair_to(v0, v1, acc[pf][nf][2 * h], acc[pf][nf][2 * h + 1]);
             o[h] = pack_pair<TT>(f32x2{v0, v1});
         }
     };
     auto store_entry = [&](const uint32_t (&pa)[2], const uint32_t (&pb)[2], uint32_t off) __attribute__((always_inline)) {
-        u32x4 o;
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            const auto sw = __builtin_amdgcn_permlane16_swap(pa[h], pb[h], false, false);
-            o[h] = sw[0];
-            o[2 + h] = sw[1];
-        }
+        const u32x4 o = swap_packed(pa, pb);
         __builtin_amdgcn_raw_buffer_store_b128(o, orsrc, (int)off, 0, 0);
     };
     // entry of channel fragments 0, 1 of pixel fragment pf
@@ -414,13 +403,8 @@ __global__ __launch_bounds__(512) void conv3t_kernel(const ConvArgs a) {
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int nf = 0; nf < NF; ++nf) {
-                if constexpr (S == 0) {  // K step 0 WRITES beta (C = 0)
-                    const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
-                    if constexpr (TT::IS_BF16) acc[pf][nf] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, wv[nf]), __builtin_bit_cast(bf16x8_t, b), zero, 0, 0, 0);
-                    else acc[pf][nf] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8_t, wv[nf]), __builtin_bit_cast(f16x8_t, b), zero, 0, 0, 0);
-                } else {
-                    mma16<TT>(acc[pf][nf], wv[nf], b);
-                }
+                if constexpr (S == 0) mma16_first<TT>(acc[pf][nf], wv[nf], b);  // (K step 0 WRITES beta)
+                else mma16<TT>(acc[pf][nf], wv[nf], b);
             }
             __builtin_amdgcn_sched_barrier(0);
         };
@@ -431,11 +415,7 @@ __global__ __launch_bounds__(512) void conv3t_kernel(const ConvArgs a) {
         gate_mfmas(ic<1>{}, wb, b1);
         asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(wc[0]), "+v"(wc[1]), "+v"(wc[2])::"memory");
         gate_mfmas(ic<2>{}, wc, b2);
-        // MFMA result -> VALU read is a SOFTWARE hazard on this chip (8 passes: 11 wait states), and hipcc's hazard recogniser does not
-        // look inside inline asm: the blend below reads beta from inline-asm chains (r3::blend_pair_to).  Without these wait states the
-        // first pair of a unit now and then blended with a stale beta (intermittent, under the partner's MFMA stream only).
-        asm volatile("s_nop 7\n\ts_nop 4" ::: "memory");
-        __builtin_amdgcn_sched_barrier(0);
+        gate_settle();  // (the blend below reads beta from inline-asm chains)
         entry01(pf_tag);
         if constexpr ((pf & 1) == 0) {
             packed_frag(pf_tag, ic<2>{}, held);
@@ -515,7 +495,8 @@ __global__ __launch_bounds__(512) void conv3t_kernel(const ConvArgs a) {
         if constexpr (sg == 2) {
             if constexpr (last) {
                 // the epilogue is complete: the fragment stream of the next tile.  Plain variants: its first tap WRITES the accumulators; the
-                // fused variant clears them here (with the first-tap form hipcc spills 218 registers around the tile loop, as in conv3r)
+                // fused variant clears them here (with the first-tap form hipcc spills 218 registers around the tile loop, as in conv3r;
+                // inline loops: relay::zero_acc() in their place reorders this kernel's register moves)
                 if constexpr (FUSE) {
 #pragma unroll
                     for (int pf = 0; pf < NPF; ++pf)
@@ -645,7 +626,7 @@ __global__ __launch_bounds__(512) void conv3t_kernel(const ConvArgs a) {
         }
     };
 
-    // ------------------------------------------------------------------------------------------------
+    // ---- the role driver (twin: conv3r_kernel) ------------------------------------------------------
     if (team == 1) {
         // prologue: chunk 0 of the first tile (halo image + its first two weight segments), published by B_0
         eA = tile_at(a_pos);

@@ -904,7 +904,7 @@ struct Runner {
 
     // conv3r_kernel / conv3t_kernel: the launch's tiles in walk order as a table in HBM (ConvArgs::tile_tab), so that the kernels'
     // helper role -- the critical path of their short tiles -- reads a tile's coordinates with one scalar load instead of running
-    // the divisions of the group walk (tile_of_s / tile_rc_s, mz_device.h) three times per phase.  The order IS that walk's: ids
+    // the divisions of the group walk (tile_of / tile_rc, mz_device.h) three times per phase.  The order IS that walk's: ids
     // 0 .. grid - 1 in gm x gn groups, the tiles of an image in block rows of four tile rows (blk4), padding ids dropped.  Needs
     // pick_order() done; sets a.tile_tab and a.grid (= tiles listed), padded for up to wgs workgroups.  One table per geometry, kept
     // with the handle.

@@ -57,7 +57,7 @@ struct ConvArgs {
     float inv_gsz, inv_groups_m, inv_gn, inv_tpi, inv_tiles_x;  // 1.0f / divisor for fdiv() (all dividends < 2^24)
     int blk4;          // conv3s, the tile lists of conv3r / conv3t: tiles of an image are walked in block rows of four tile rows (tile_rc(), mz_device.h)
     float inv_bsz;     // 1.0f / (4 * tiles_x)
-    // conv3r_kernel: the same divisors as floor(2^32 / d) for sdiv() (scalar-unit division, mz_device.h)
+    // the same divisors as floor(2^32 / d), for division on the scalar unit (unused since the relay kernels read the host's tile table)
     uint32_t mg_gsz, mg_groups_m, mg_gn, mg_tpi, mg_tiles_x, mg_bsz;
     int epi;
     int silu;
@@ -133,14 +133,14 @@ hipError_t launch_mix16(int dtype, const ConvArgs& a, hipStream_t s);
 // C = 192 without the second read of x and z: a.wpk16 = gate weights packed as PK_MIX16B (accumulator rows in B-operand
 // order); the gate matrix stays in LDS, every wave walks its own 32-pixel units
 hipError_t launch_mix16b(int dtype, const ConvArgs& a, hipStream_t s, int workgroups);  // persistent: at most `workgroups` (one per CU)
-// conv3r_kernel (mz_conv3r.h): 3x3 convolution, 16-bit types, 96-channel N tiles (NT = 3), 8 x 48 / 8 x 40 pixel tiles, a.persist workgroups of
+// conv3r_kernel (mz_conv3r.h; helpers shared with conv3t_kernel: mz_relay.h): 3x3 convolution, 16-bit types, 96-channel N tiles (NT = 3), 8 x 48 / 8 x 40 pixel tiles, a.persist workgroups of
 // 512 threads; a.wpk16 / a.nchunks16 as for conv3s_kernel.  The two waves of every SIMD alternate between the compute
 // and the loader + epilogue role from tile to tile.  >= 3 chunks of 32 channels (odd counts included; a.ragged_planes != 0: exactly
 // two, the second with a.ragged_planes real planes -- Cin = 48 --, EPI_STORE + SiLU only); EPI_STORE / EPI_D2S
 // (32-bit store offsets: 12 planes of the output, resp. one whole D2S target image, must stay below 4 GiB); EPI_FUSEDMIX: >= 6
 // chunks, a.wmix16 = gate weights packed as PK_GATE16R, a.in1 / a.p1 = the block input.
 hipError_t launch_conv3r(int dtype, const ConvArgs& a, hipStream_t s);
-// conv3t_kernel (mz_conv3t.h): conv3r's role-alternating structure for ONE N tile of <= 48 channels (three 16-channel fragments x twelve
+// conv3t_kernel (mz_conv3t.h, mz_relay.h): conv3r's role-alternating structure for ONE N tile of <= 48 channels (three 16-channel fragments x twelve
 // pixel fragments per wave, 12 x 64 pixel tiles).  a.wpk16 = weights packed as PK_CONV16T; a.nchunks16 = 3 or >= 6; EPI_STORE
 // (plain / SiLU) or EPI_FUSEDMIX (a.wmix16 = gate weights packed as PK_GATE16T, a.in1 / a.p1 = the block input).
 hipError_t launch_conv3t(int dtype, const ConvArgs& a, hipStream_t s);
