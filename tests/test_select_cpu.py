@@ -1,5 +1,7 @@
 """Which kernel every 3x3 convolution and mix of the model gets (mz_host.cpp: choose_conv3 / choose_mix), read without a GPU through
-mz_debug_select().  The expected names are those mz_debug_last_kernel() reported for these layers when the selection was spread over the
+mz_debug_select().  That entry only maps its op code to a layer role; the role functions (conv1_call, conv2_call, d2s_call, ..) then
+describe the call, a Conv3Call, exactly as they do for mz_forward and the mz_op_* entries, so a row here exercises the code the model
+runs.  The expected names are those mz_debug_last_kernel() reported for these layers when the selection was spread over the
 launch code; a row that changes is a change of the kernel that runs, and belongs in a pull request that says so."""
 
 import ctypes

@@ -212,7 +212,6 @@ struct Slot {
 struct ProfRec {
     hipEvent_t a, b;
     double flops, bytes;
-    int is_conv3;
     int kind, B, H, W, cin, cout, nt, ntiles, mtiles, n_fast;  // kind: 0 conv3, 1 mix, 2 crush
 };
 
@@ -638,6 +637,12 @@ static void tile_list(const ConvArgs& a, int th, int tw, std::vector<uint32_t>& 
     }
 }
 
+// The walk of a launch in groups of a.gm pixel tiles x a.gn N tiles (a.mtiles, a.ntiles set): whole groups, padding ids included
+static void set_walk(ConvArgs& a) {
+    a.groups_m = (a.mtiles + a.gm - 1) / a.gm;
+    a.grid = (int)((long long)a.groups_m * ((a.ntiles + a.gn - 1) / a.gn) * a.gm * a.gn);
+}
+
 // Tile groups of gm pixel tiles x gn N tiles (gm * gn ~ the workgroups resident on one XCD): inside a group both operands are shared
 // through the XCD's L2; per group the activations are re-read ntiles/gn times and the weights mtiles/gm times in total.  Picks the shape
 // with the least total re-read traffic and sets the walk of a (a.mtiles, a.ntiles, a.tiles_x, a.tiles_y set): a.grid and its divisors.
@@ -656,9 +661,7 @@ static void pick_order(ConvArgs& a, const ConvW& c, double act_bytes, const Knob
         if (traffic < best) { best = traffic; best_gm = gm; best_gn = gn; }
     }
     a.gm = best_gm; a.gn = best_gn;
-    const long long groups = (long long)((a.mtiles + a.gm - 1) / a.gm) * ((a.ntiles + a.gn - 1) / a.gn);
-    a.grid = (int)(groups * a.gm * a.gn);
-    a.groups_m = (a.mtiles + a.gm - 1) / a.gm;
+    set_walk(a);
     a.inv_gsz = 1.0f / (float)(a.gm * a.gn);
     a.inv_groups_m = 1.0f / (float)a.groups_m;
     a.inv_gn = 1.0f / (float)a.gn;
@@ -666,10 +669,6 @@ static void pick_order(ConvArgs& a, const ConvW& c, double act_bytes, const Knob
     a.inv_tiles_x = a.tiles_x > 0 ? 1.0f / (float)a.tiles_x : 1.0f;
     a.inv_bsz = a.tiles_x > 0 ? 1.0f / (float)(4 * a.tiles_x) : 1.0f;
     a.blk4 = k.blk4 && a.tiles_x > 0 && 4 * a.tiles_x < 65536 ? 1 : 0;  // the tile walk inside an image: conv3s_kernel, and the tile lists of conv3r / conv3t
-    auto magic = [](long long d) { return d <= 1 ? 0xffffffffu : (uint32_t)(4294967296ULL / (unsigned long long)d); };
-    a.mg_gsz = magic((long long)a.gm * a.gn); a.mg_groups_m = magic(a.groups_m); a.mg_gn = magic(a.gn);
-    a.mg_tpi = magic(a.tiles_x > 0 ? (long long)a.tiles_x * a.tiles_y : 1); a.mg_tiles_x = magic(a.tiles_x > 0 ? a.tiles_x : 1);
-    a.mg_bsz = magic(a.tiles_x > 0 ? 4LL * a.tiles_x : 1);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -722,10 +721,71 @@ static bool offsets_fit(double planes, double pixels) { return planes * pixels *
 // conv2 + AdaptiveResidualMix of a block in one launch: all output channels in one workgroup (BlockW::fused), on the 512-pixel kernels
 static bool fuse_mix(const Knobs& k, const BlockW& b) { return b.fused && k.wide && k.fuse; }
 
-// conv3x3, pad 1: epi STORE / D2S (into Hout x Wout) / FINAL / FUSEDMIX (mixf = the block's gate weights); film = FiLM epilogue
-static KernelChoice choose_conv3(const Knobs& k, int dtype, const ConvW& c, const ConvW* mixf, int epi, int silu, bool film,
-                                 int B, int H, int W, int Hout, int Wout, int cus) {
+// One 3x3 layer call (conv3x3, pad 1): choose_conv3 reads the fields down to Wout, Runner::conv3 all of them.  The role functions below
+// are the ONE place that says what a conv1, a block's conv2, a sub-pixel conv, .. is -- for mz_forward, the mz_op_* entries and
+// mz_debug_select (which names no buffers) alike.
+struct Conv3Call {
+    const ConvW* c = nullptr;
+    const ConvW* mixf = nullptr;  // EPI_FUSEDMIX: the block's gate weights
+    int epi = EPI_STORE, silu = 0;
+    bool film = false;            // FiLM epilogue: gamma[b, c] * y + beta[b, c] ahead of the SiLU
+    int B = 0, H = 0, W = 0, Hout = 0, Wout = 0;  // D2S / FINAL: into Hout x Wout
+    const void* in = nullptr;
+    void* out = nullptr;
+    const void* xin = nullptr;    // EPI_FUSEDMIX: the block input and the mix's alpha
+    float alpha = 0.f;
+    const void* img = nullptr;    // EPI_FINAL: the low-resolution image, the total upscale ratio, clamp to [0, 1]
+    int R = 0, clamp = 0;
+    const float *gamma = nullptr, *beta = nullptr;  // film: float [B][padded cout] each
+};
+// a plain 3x3 convolution: a block's unfused conv2 (model.py:746-748), the quality head's (:1010)
+static Conv3Call plain_call(const ConvW& c, const void* in, void* out, int B, int H, int W) {
+    Conv3Call k;
+    k.c = &c; k.in = in; k.out = out; k.B = B; k.H = H; k.W = W;
+    return k;
+}
+// conv1 of a block + SiLU (model.py:742-744)
+static Conv3Call conv1_call(const ConvW& c, const void* in, void* out, int B, int H, int W) {
+    Conv3Call k = plain_call(c, in, out, B, H, W);
+    k.silu = 1;
+    return k;
+}
+// SubpixelConv2d: 3x3 + PixelShuffle(2) into Hout x Wout (model.py:900-911)
+static Conv3Call d2s_call(const ConvW& c, const void* in, void* out, int B, int H, int W, int Hout, int Wout) {
+    Conv3Call k = plain_call(c, in, out, B, H, W);
+    k.epi = EPI_D2S; k.Hout = Hout; k.Wout = Wout;
+    return k;
+}
+// the image head: 3x3 to 12 channels + PixelShuffle(2) + bicubic skip + add (+ clamp) into 2H x 2W (model.py:926-930, 156, 162, 177);
+// the caller names img, R and clamp
+static Conv3Call head_call(const ConvW& c, const void* in, void* out, int B, int H, int W) {
+    Conv3Call k = plain_call(c, in, out, B, H, W);
+    k.epi = EPI_FINAL; k.Hout = 2 * H; k.Wout = 2 * W;
+    return k;
+}
+// 3x3 + FiLM + optional SiLU (mz_op_conv_film); the caller names gamma and beta
+static Conv3Call film_call(const ConvW& c, const void* in, void* out, int B, int H, int W, int silu) {
+    Conv3Call k = plain_call(c, in, out, B, H, W);
+    k.film = true; k.silu = silu;
+    return k;
+}
+// conv2 of a block + AdaptiveResidualMix with the block input xin in one launch (model.py:746-748, 826-839)
+static Conv3Call fused_call(const BlockW& b, const void* in, const void* xin, void* out, int B, int H, int W) {
+    Conv3Call k = plain_call(b.conv2, in, out, B, H, W);
+    k.epi = EPI_FUSEDMIX; k.mixf = &b.mixf; k.xin = xin; k.alpha = b.alpha;
+    return k;
+}
+// conv2 of a block as mz_forward runs it: fused with the mix (mixf set), or plain and the caller runs the mix.  Where the output goes
+// depends on which: the caller names out
+static Conv3Call conv2_call(const Knobs& knobs, const BlockW& b, const void* in, const void* xin, int B, int H, int W) {
+    return fuse_mix(knobs, b) ? fused_call(b, in, xin, nullptr, B, H, W) : plain_call(b.conv2, in, nullptr, B, H, W);
+}
+
+static KernelChoice choose_conv3(const Knobs& k, int dtype, const Conv3Call& call, int cus) {
     KernelChoice ch;
+    const ConvW& c = *call.c;
+    const ConvW* mixf = call.mixf;
+    const int epi = call.epi, B = call.B, H = call.H, W = call.W;
     const bool fused = epi == EPI_FUSEDMIX;
     const int wgs = persistent_workgroups(k, cus);
     const double px = (double)H * W;  // the offset guards hold inside one image
@@ -766,14 +826,14 @@ static KernelChoice choose_conv3(const Knobs& k, int dtype, const ConvW& c, cons
     // counts only (never on H or W): its fused variant sums the gate in another order than conv3s_kernel<.., FUSE> -- equal to <= 1 ulp,
     // not bit for bit --, and a tile of upscale_tiled() must run the kernel the whole image runs.
     const bool t_fuse = epi == EPI_FUSEDMIX && k.fuse16 && mixf && mixf->has(PK_GATE16T);
-    if (k.t && s16 && !film && c.has(PK_CONV16T) && c.ntiles == 1 && (c.nchunks32 == 3 || c.nchunks32 >= 6) &&
+    if (k.t && s16 && !call.film && c.has(PK_CONV16T) && c.ntiles == 1 && (c.nchunks32 == 3 || c.nchunks32 >= 6) &&
         (epi == EPI_STORE || t_fuse) && halo_fits && offsets_fit(6, px))
         return listed(K_CONV3T, 12, 64, PK_CONV16T, t_fuse ? PK_GATE16T : PK_MAIN);
 
     // conv3r_kernel's ragged variant: conv1 + SiLU with Cin = 48 (two 32-channel chunks, the second with two real planes) into 96-channel
     // N tiles.  The kernel it replaces (conv3p_kernel: 32x32x16 MFMA, exact 16-channel chunks) sums in another order, so the choice
     // depends on channel counts, dtype and knobs only -- never on H or W.
-    if (k.r && k.r2 && s16 && !film && c.nt == 3 && c.has(PK_CONV16) && epi == EPI_STORE && silu && c.nchunks32 == 2 && c.cp0 == 48 &&
+    if (k.r && k.r2 && s16 && !call.film && c.nt == 3 && c.has(PK_CONV16) && epi == EPI_STORE && call.silu && c.nchunks32 == 2 && c.cp0 == 48 &&
         halo_fits && offsets_fit(12, px)) {
         ch.ragged_planes = (c.cp0 - 32) / 8;
         return listed(K_CONV3R, 8, 48, PK_CONV16, PK_MAIN);
@@ -793,9 +853,9 @@ static KernelChoice choose_conv3(const Knobs& k, int dtype, const ConvW& c, cons
     // Its tiles are 8 x 48, or 8 x 40 (five pixel fragments per wave: widths like 120 that 48 does not divide) where those pad fewer
     // pixels, and it runs where they pad no more than the better of the 8 x 64 / 16 x 32 tiles.  (The plain variants accumulate in the
     // same order as conv3s_kernel whatever the tile shape: bit-identical, so this choice may follow H and W.)
-    if (k.r && s16 && !film && c.nt == 3 && c.has(PK_CONV16) && (epi == EPI_STORE || epi == EPI_D2S) && k_fits && halo_fits &&
+    if (k.r && s16 && !call.film && c.nt == 3 && c.has(PK_CONV16) && (epi == EPI_STORE || epi == EPI_D2S) && k_fits && halo_fits &&
         c.nchunks32 >= 3 && p0 % 4 == 0 &&
-        (epi == EPI_D2S ? offsets_fit(c.cq_p * dtype_size(dtype) / 16, (double)Hout * Wout) : offsets_fit(12, px))) {
+        (epi == EPI_D2S ? offsets_fit(c.cq_p * dtype_size(dtype) / 16, (double)call.Hout * call.Wout) : offsets_fit(12, px))) {
         const long long rows8 = (long long)((H + 7) / 8 * 8);
         const long long pad48 = rows8 * ((W + 47) / 48 * 48), pad40 = rows8 * ((W + 39) / 40 * 40);
         const long long pads = (long long)((H + th - 1) / th) * th * ((W + tw - 1) / tw) * tw;
@@ -827,7 +887,7 @@ static KernelChoice choose_conv3(const Knobs& k, int dtype, const ConvW& c, cons
             ch.persist = wgs;
         }
     }
-    if (film && ch.layout == PK_MAIN) {
+    if (call.film && ch.layout == PK_MAIN) {
         fail(MZ_ERR_INVALID_ARGUMENT, "the FiLM epilogue exists on the 16x16x32 kernel only: bf16 / fp16, at most 96 output channels per "
                                       "N tile, input channels within 12.5 %% of a multiple of 32");
         return ch;
@@ -864,25 +924,24 @@ struct Runner {
     int rc = MZ_OK;
     const Knobs knobs = h->knobs;
     int io_u8 = 0;                                        // images at both ends are uint8 (mz_forward_u8)
-    const float* film_gamma = nullptr;                    // mz_op_conv_film: per-image per-channel affine on the next conv3 call
-    const float* film_beta = nullptr;
     int cus = current_cus();
 
     // the profiling record of one launch (kind: 0 conv3, 1 mix, 2 crush); nullptr unless the handle profiles
     ProfRec* prof_begin(int kind, const ConvArgs& a, const ConvW& c, double flops, double bytes) {
-        if (!h || !h->prof) return nullptr;
+        if (!h->prof) return nullptr;
         if (h->recs_used == h->recs.size()) {
             ProfRec n;
             if (hipEventCreate(&n.a) != hipSuccess || hipEventCreate(&n.b) != hipSuccess) return nullptr;
             h->recs.push_back(n);
         }
         ProfRec* r = &h->recs[h->recs_used++];
-        r->flops = flops; r->bytes = bytes; r->is_conv3 = kind == 0;
+        r->flops = flops; r->bytes = bytes;
         r->kind = kind; r->B = a.B; r->H = a.H; r->W = a.W; r->cin = c.cin; r->cout = c.cout; r->nt = c.nt; r->ntiles = a.ntiles;
         r->mtiles = a.mtiles; r->n_fast = a.gm * 1000 + a.gn;
         (void)hipEventRecord(r->a, s);
         return r;
     }
+
     void prof_end(ProfRec* r) {
         if (r) (void)hipEventRecord(r->b, s);
     }
@@ -892,14 +951,21 @@ struct Runner {
         return rc;
     }
 
-    void base_args(ConvArgs& a, const ConvW& c) {
+    // what every launch says alike: the layer's main packing and chunk counts, its first input over B x H x W pixels, its output of
+    // cp_out channels per pixel
+    void base_args(ConvArgs& a, const ConvW& c, const void* in0, void* out, int B, int H, int W, int cp_out) {
         memset(&a, 0, sizeof(a));
         a.wpk = c.packed[PK_MAIN].p;
-        a.zero = h ? h->zero_page.p : nullptr;
+        a.zero = h->zero_page.p;
         a.dbg = debug_buffer();
         a.nchunks = c.nchunks;
         a.nchunks_real = c.nchunks_real;
         a.ntiles = c.ntiles;
+        a.in0 = in0; a.out = out;
+        a.B = B; a.H = H; a.W = W; a.Ho = H; a.Wo = W;
+        a.p0 = c.cp0 * dtype_size(dtype) / 16;
+        a.cp_out = cp_out;
+        a.p_out = a.cp_out * dtype_size(dtype) / 16;
     }
 
     // conv3r_kernel / conv3t_kernel: the launch's tiles in walk order as a table in HBM (ConvArgs::tile_tab), so that the kernels'
@@ -946,41 +1012,35 @@ struct Runner {
         prof_end(r);
     }
 
-    // conv3x3, pad 1 (model.py:742-748, 900-909, 1010). epi: STORE / D2S / FINAL / FUSEDMIX
-    void conv3(const ConvW& c, const void* in, void* out, int B, int H, int W, int epi, int silu, int Hout, int Wout,
-               const void* img = nullptr, int R = 0, int clamp = 0, const void* zero_override = nullptr,
-               const ConvW* mixf = nullptr, const void* xin = nullptr, float alpha = 0.f) {
+    // conv3x3, pad 1 (model.py:742-748, 900-909, 1010)
+    void conv3(const Conv3Call& k) {
         if (rc) return;
-        const KernelChoice ch = choose_conv3(knobs, dtype, c, mixf, epi, silu, film_gamma != nullptr, B, H, W, Hout, Wout, cus);
+        const KernelChoice ch = choose_conv3(knobs, dtype, k, cus);
         if (!ch.ok) { rc = MZ_ERR_INVALID_ARGUMENT; return; }
+        const ConvW& c = *k.c;
+        const int B = k.B, H = k.H, W = k.W;
         ConvArgs a;
-        base_args(a, c);
-        if (zero_override) a.zero = zero_override;
-        a.in0 = in; a.out = out;
-        a.B = B; a.H = H; a.W = W; a.Ho = H; a.Wo = W;
-        a.p0 = c.cp0 * dtype_size(dtype) / 16;
+        base_args(a, c, k.in, k.out, B, H, W, k.epi == EPI_D2S ? c.cq_p : pad16(c.cout));
         a.src = SRC_PLAIN;
         a.tiles_x = (W + ch.tw - 1) / ch.tw; a.tiles_y = (H + ch.th - 1) / ch.th;
         a.mtiles = B * a.tiles_x * a.tiles_y;
-        a.epi = epi; a.silu = silu;
-        a.cp_out = epi == EPI_D2S ? c.cq_p : pad16(c.cout);
-        a.p_out = a.cp_out * dtype_size(dtype) / 16;
-        a.Hout = Hout; a.Wout = Wout;
-        a.img = img; a.R = R; a.clamp = clamp;
-        if (epi == EPI_FINAL) { a.Hi = Hout / R; a.Wi = Wout / R; a.io_u8 = io_u8; }
-        const bool fused = epi == EPI_FUSEDMIX;
+        a.epi = k.epi; a.silu = k.silu;
+        a.Hout = k.Hout; a.Wout = k.Wout;
+        a.img = k.img; a.R = k.R; a.clamp = k.clamp;
+        if (k.epi == EPI_FINAL) { a.Hi = k.Hout / k.R; a.Wi = k.Wout / k.R; a.io_u8 = io_u8; }
+        const bool fused = ch.fused;
         if (fused) {
-            a.in1 = xin;
+            a.in1 = k.xin;
             a.p1 = pad16(c.cout) * dtype_size(dtype) / 16;
-            a.wmix = mixf->packed[PK_MAIN].p;
-            a.mix_pieces = mixf->nchunks * mixf->nt;
+            a.wmix = k.mixf->packed[PK_MAIN].p;
+            a.mix_pieces = k.mixf->nchunks * k.mixf->nt;
             {   // room for the 8 compute waves' x fragments next to the gate weights in ring slots 1-2?
                 const int slot = ch.mode == MODE_C3W16 ? stage_bytes<MODE_C3W16>(c.nt) : stage_bytes<MODE_C3W8>(c.nt);
                 const int ncx = a.p1 / 2;
                 a.x_via_lds = (a.mix_pieces * 1024 + 8 * ncx * 1024 <= 2 * slot) ? 1 : 0;
             }
-            a.mix_scale = 1.0f / (1.0f + std::exp(-alpha));
-            a.inv_mix_scale = inv_sigmoid(alpha);
+            a.mix_scale = 1.0f / (1.0f + std::exp(-k.alpha));
+            a.inv_mix_scale = inv_sigmoid(k.alpha);
         }
         a.geo = ch.geo;
         a.ragged_planes = ch.ragged_planes;
@@ -990,12 +1050,12 @@ struct Runner {
         if (ch.layout != PK_MAIN) {
             a.wpk16 = c.packed[ch.layout].p;
             a.nchunks16 = pack_shape(c, ch.layout).nchunks;
-            if (fused) a.wmix16 = mixf->packed[ch.gate].p;
+            if (fused) a.wmix16 = k.mixf->packed[ch.gate].p;
         }
         if (ch.tile_list) tile_table(a, ch.th, ch.tw, ch.persist);
         if (rc) return;
         a.persist = std::min((a.grid + 7) / 8 * 8, ch.persist);
-        a.film_gamma = film_gamma; a.film_beta = film_beta;
+        a.film_gamma = k.gamma; a.film_beta = k.beta;
         // algorithmic flops and bytes: input once, output once, weights once; a fused conv2 + mix also runs the gate GEMM and reads the
         // block input x once
         const double flops = 2.0 * px * 9.0 * c.cin * c.cout + (fused ? 2.0 * px * 2.0 * c.cout * c.cout : 0.0);
@@ -1008,18 +1068,14 @@ struct Runner {
         if (rc) return;
         const KernelChoice ch = choose_mix(knobs, dtype, c, B, H, W, cus);
         ConvArgs a;
-        base_args(a, c);
-        a.in0 = x; a.in1 = z; a.out = out;
-        a.B = B; a.H = H; a.W = W; a.Ho = H; a.Wo = W;
+        base_args(a, c, x, out, B, H, W, pad16(c.cout));
         const int sz = dtype_size(dtype);
-        a.p0 = c.cp0 * sz / 16; a.p1 = pad16(c.c1) * sz / 16;
+        a.in1 = z; a.p1 = pad16(c.c1) * sz / 16;
         a.nchunks0 = c.cp0 / chunk_channels(dtype);
         a.src = SRC_CONCAT;
         const long long npix = (long long)B * H * W;
         a.mtiles = (int)((npix + 255) / 256);
         a.epi = EPI_MIX;
-        a.cp_out = pad16(c.cout);
-        a.p_out = a.cp_out * sz / 16;
         a.mix_scale = 1.0f / (1.0f + std::exp(-alpha));
         a.inv_mix_scale = inv_sigmoid(alpha);
         if (ch.layout != PK_MAIN) {  // 192-channel N tiles, x / z straight into MFMA operands (mix16_kernel / mix16b_kernel)
@@ -1033,21 +1089,16 @@ struct Runner {
     }
 
     // PixelCrush (model.py:857-863, 881-882): conv 2x2 stride 2, floors odd sizes
-    void crush(const ConvW& c, const void* in, void* out, int B, int H, int W, const void* zero_override = nullptr) {
+    void crush(const ConvW& c, const void* in, void* out, int B, int H, int W) {
         if (rc) return;
         ConvArgs a;
-        base_args(a, c);
-        if (zero_override) a.zero = zero_override;
-        a.in0 = in; a.out = out;
-        a.B = B; a.H = H; a.W = W; a.Ho = H / 2; a.Wo = W / 2;
-        a.p0 = c.cp0 * dtype_size(dtype) / 16;
+        base_args(a, c, in, out, B, H, W, pad16(c.cout));
+        a.Ho = H / 2; a.Wo = W / 2;
         a.nchunks0 = c.cp0 / chunk_channels(dtype);
         a.src = SRC_CRUSH;
         const long long npix = (long long)B * a.Ho * a.Wo;
         a.mtiles = (int)((npix + 255) / 256);
         a.epi = EPI_STORE;
-        a.cp_out = pad16(c.cout);
-        a.p_out = a.cp_out * dtype_size(dtype) / 16;
         const double sz = dtype_size(dtype);
         pick_order(a, c, (double)B * H * W * c.cp0 * sz, knobs, 64);
         ProfRec* r = prof_begin(2, a, c, 2.0 * (double)npix * 4.0 * c.cin * c.cout, ((double)B * H * W * c.cin + (double)npix * c.cout) * sz);
@@ -1070,14 +1121,12 @@ static int forward_micro(mz_handle* h, const char* x, char* out_sr, float* out_q
 
     auto block = [&](const BlockW& b, const void* xin, void* hid, void* z, void* yout, int hh, int ww) {
         // EncoderBlock / DecoderBlock (model.py:507-511): conv1 -> SiLU -> conv2 -> adaptive mix with the input
-        run.conv3(b.conv1, xin, hid, nb, hh, ww, EPI_STORE, 1, 0, 0);
-        if (fuse_mix(run.knobs, b)) {
-            // conv2 + AdaptiveResidualMix in one launch (all output channels live in one workgroup)
-            run.conv3(b.conv2, hid, yout, nb, hh, ww, EPI_FUSEDMIX, 0, 0, 0, nullptr, 0, 0, nullptr, &b.mixf, xin, b.alpha);
-        } else {
-            run.conv3(b.conv2, hid, z, nb, hh, ww, EPI_STORE, 0, 0, 0);
-            run.mix(b.mix, b.alpha, xin, z, yout, nb, hh, ww);
-        }
+        run.conv3(conv1_call(b.conv1, xin, hid, nb, hh, ww));
+        // conv2 + AdaptiveResidualMix in one launch (all output channels live in one workgroup), or in two
+        Conv3Call c2 = conv2_call(run.knobs, b, hid, xin, nb, hh, ww);
+        c2.out = c2.mixf ? yout : z;
+        run.conv3(c2);
+        if (!c2.mixf) run.mix(b.mix, b.alpha, xin, z, yout, nb, hh, ww);
     };
 
     // stem (model.py:158): NCHW image -> NHWC features
@@ -1107,7 +1156,7 @@ static int forward_micro(mz_handle* h, const char* x, char* out_sr, float* out_q
     // quality head (model.py:482, 1026-1032); upscale() discards it (model.py:175)
     if (out_qa) {
         const int F = h->cfg.num_deg_features;
-        run.conv3(h->qa_conv, feat[3], ws + p.QA, nb, p.hs[3], p.ws[3], EPI_STORE, 0, 0, 0);
+        run.conv3(plain_call(h->qa_conv, feat[3], ws + p.QA, nb, p.hs[3], p.ws[3]));
         if (run.rc) return run.rc;
         if (hipError_t e = launch_qa_reduce(h->dtype, ws + p.QA, (const float*)h->qa_bias.p, out_qa, nb, p.hs[3] * p.ws[3], pad16(F), F, s);
             e != hipSuccess)
@@ -1123,7 +1172,7 @@ static int forward_micro(mz_handle* h, const char* x, char* out_sr, float* out_q
             // SubpixelConv2d (model.py:926-930) + crop_feature_maps zero pad (model.py:650-689) + skip mix (:701)
             const ConvW& up = h->up[d - 1];
             char* u = ws + p.U[l];
-            run.conv3(up, cur, u, nb, p.hs[l + 1], p.ws[l + 1], EPI_D2S, 0, p.hs[l], p.ws[l]);
+            run.conv3(d2s_call(up, cur, u, nb, p.hs[l + 1], p.ws[l + 1], p.hs[l], p.ws[l]));
             if (run.rc) return run.rc;
             if (hipError_t e = launch_zero_border(h->dtype, u, nb, p.hs[l], p.ws[l], up.cq_p, 2 * p.hs[l + 1], 2 * p.ws[l + 1], s);
                 e != hipSuccess)
@@ -1158,10 +1207,12 @@ static int forward_micro(mz_handle* h, const char* x, char* out_sr, float* out_q
         block(*h->head_blocks[i], cur, hid, z, y, hh, ww);
         const bool last = i == h->nhead - 1;
         if (last) {
-            run.conv3(*h->head_up[i], y, out_sr, nb, hh, ww, EPI_FINAL, 0, 2 * hh, 2 * ww, x, r, clamp);
+            Conv3Call head = head_call(*h->head_up[i], y, out_sr, nb, hh, ww);
+            head.img = x; head.R = r; head.clamp = clamp;
+            run.conv3(head);
         } else {
             char* nxt = ws + p.HR[i + 1][0];
-            run.conv3(*h->head_up[i], y, nxt, nb, hh, ww, EPI_D2S, 0, 2 * hh, 2 * ww);
+            run.conv3(d2s_call(*h->head_up[i], y, nxt, nb, hh, ww, 2 * hh, 2 * ww));
             cur = nxt;
             hh *= 2; ww *= 2;
         }
@@ -1210,20 +1261,30 @@ extern "C" int mz_forward_u8(mz_handle* h, const uint8_t* x, uint8_t* out_sr, fl
 // ------------------------------------------------------------------------------------------------
 extern "C" int mz_padded_channels(int c) { return pad16(c); }
 
-// The throw-away handle an mz_op_* entry hands to Runner: the zero page and the knobs
+// What an mz_op_* entry runs its layer on, built after the entry's own argument checks: a throw-away handle -- the zero page, the knobs
+// read now -- and a Runner on it.  rc says whether making the handle, then pack() of a layer's weights, worked; an entry returns it
+// where it is set, before it touches run (which exists either way).  finish() waits for the stream and gives the entry's return code.
 static int op_handle(mz_handle& fake, hipStream_t s) {
     HIPCHK(fake.zero_page.alloc(4096));
     HIPCHK(hipMemsetAsync(fake.zero_page.p, 0, 4096, s));
     fake.knobs = read_knobs();
     return MZ_OK;
 }
+struct OpRun {
+    mz_handle fake;
+    int rc;
+    Runner run;
+    OpRun(int dtype, void* hip_stream) : rc(op_handle(fake, (hipStream_t)hip_stream)), run{&fake, (hipStream_t)hip_stream, dtype} {}
+    int pack(ConvW& c, const float* w_dev_f32) { return rc = rc ? rc : pack_conv(c, run.dtype, w_dev_f32, run.s); }
+    // the entry's return code: a failed wait for the stream is reported ahead of the Runner's own code
+    int finish() { HIPCHK(hipStreamSynchronize(run.s)); return run.rc; }
+};
 
 extern "C" int mz_op_conv(int dtype, int kind, const void* in0, const void* in1, const float* w_dev_f32, float alpha,
                           void* out, int B, int H, int W, int cin, int cout, int Hout, int Wout, int silu,
                           void* hip_stream) {
     int rc = ensure_device_ready();
     if (rc) return rc;
-    hipStream_t s = (hipStream_t)hip_stream;
     ConvW c;
     switch (kind) {
         case 0: plan_conv(c, dtype, MODE_CONV3, cout, cin, 3, 3, OUT_PLAIN, SRC_PLAIN, 0, 0); break;
@@ -1232,25 +1293,22 @@ extern "C" int mz_op_conv(int dtype, int kind, const void* in0, const void* in1,
         case 3: plan_conv(c, dtype, MODE_GEMM1, cout, 2 * cout, 1, 1, OUT_PLAIN, SRC_CONCAT, cout, cout); break;
         default: return fail(MZ_ERR_INVALID_ARGUMENT, "bad op kind %d", kind);
     }
-    mz_handle fake;
-    rc = op_handle(fake, s);
-    if (!rc) rc = pack_conv(c, dtype, w_dev_f32, s);
-    if (rc) return rc;
-    Runner run{&fake, s, dtype};
+    OpRun op(dtype, hip_stream);
+    if (op.pack(c, w_dev_f32)) return op.rc;
+    Runner& run = op.run;
     switch (kind) {
-        case 0: run.conv3(c, in0, out, B, H, W, EPI_STORE, silu, 0, 0); break;
+        case 0: run.conv3(silu ? conv1_call(c, in0, out, B, H, W) : plain_call(c, in0, out, B, H, W)); break;
         case 1:
-            run.conv3(c, in0, out, B, H, W, EPI_D2S, 0, Hout, Wout);
+            run.conv3(d2s_call(c, in0, out, B, H, W, Hout, Wout));
             if (!run.rc) {
-                hipError_t e = launch_zero_border(dtype, out, B, Hout, Wout, c.cq_p, 2 * H, 2 * W, s);
+                hipError_t e = launch_zero_border(dtype, out, B, Hout, Wout, c.cq_p, 2 * H, 2 * W, run.s);
                 if (e != hipSuccess) run.rc = fail(MZ_ERR_HIP, "zero border: %s", hipGetErrorString(e));
             }
             break;
         case 2: run.crush(c, in0, out, B, H, W); break;
         case 3: run.mix(c, alpha, in0, in1, out, B, H, W); break;
     }
-    HIPCHK(hipStreamSynchronize(s));
-    return run.rc;
+    return op.finish();
 }
 
 // conv2 of a block + AdaptiveResidualMix with the block input in ONE launch (model.py:773-778 second half, 826-839): the fused
@@ -1261,19 +1319,14 @@ extern "C" int mz_op_conv_mix(int dtype, const void* hid, const void* x, const f
     int rc = ensure_device_ready();
     if (rc) return rc;
     if (!hid || !x || !w2_dev_f32 || !wmix_dev_f32 || !out) return fail(MZ_ERR_INVALID_ARGUMENT, "null argument");
-    hipStream_t s = (hipStream_t)hip_stream;
     BlockW b;
     plan_block(b, dtype, cout, cin);
     if (!b.fused) return fail(MZ_ERR_INVALID_ARGUMENT, "the fused conv2 + mix needs all output channels in one N tile (cout <= 96)");
-    mz_handle fake;
-    rc = op_handle(fake, s);
-    if (!rc) rc = pack_conv(b.conv2, dtype, w2_dev_f32, s);
-    if (!rc) rc = pack_conv(b.mixf, dtype, wmix_dev_f32, s);
-    if (rc) return rc;
-    Runner run{&fake, s, dtype};
-    run.conv3(b.conv2, hid, out, B, H, W, EPI_FUSEDMIX, 0, 0, 0, nullptr, 0, 0, nullptr, &b.mixf, x, alpha);
-    HIPCHK(hipStreamSynchronize(s));
-    return run.rc;
+    b.alpha = alpha;  // (nobody set this block's skip.alpha)
+    OpRun op(dtype, hip_stream);
+    if (op.pack(b.conv2, w2_dev_f32) || op.pack(b.mixf, wmix_dev_f32)) return op.rc;
+    op.run.conv3(fused_call(b, hid, x, out, B, H, W));  // whatever MZ_NO_FUSE / MZ_NO_WIDE say: this entry IS the fused launch
+    return op.finish();
 }
 
 // a17: conv3x3 -> gamma[b, c] * y + beta[b, c] -> optional SiLU, the per-channel modulation of a FiLM /
@@ -1286,28 +1339,23 @@ extern "C" int mz_op_conv_film(int dtype, const void* in0, const float* w_dev_f3
     if (rc) return rc;
     if (!in0 || !w_dev_f32 || !gamma_dev_f32 || !beta_dev_f32 || !out) return fail(MZ_ERR_INVALID_ARGUMENT, "null argument");
     if (dtype != DT_BF16 && dtype != DT_F16) return fail(MZ_ERR_INVALID_ARGUMENT, "the FiLM epilogue is implemented for bf16 / fp16");
-    hipStream_t s = (hipStream_t)hip_stream;
     ConvW c;
     plan_conv(c, dtype, MODE_CONV3, cout, cin, 3, 3, OUT_PLAIN, SRC_PLAIN, 0, 0);
-    mz_handle fake;
-    rc = op_handle(fake, s);
-    if (!rc) rc = pack_conv(c, dtype, w_dev_f32, s);
-    if (rc) return rc;
+    OpRun op(dtype, hip_stream);
+    if (op.pack(c, w_dev_f32)) return op.rc;
     // gamma / beta [B][cout] -> [B][padded cout], pad channels zero
     const int cp = pad16(cout);
     DevBuf gpad, bpad;
     HIPCHK(gpad.alloc(sizeof(float) * (size_t)B * cp));
     HIPCHK(bpad.alloc(sizeof(float) * (size_t)B * cp));
-    HIPCHK(hipMemsetAsync(gpad.p, 0, sizeof(float) * (size_t)B * cp, s));
-    HIPCHK(hipMemsetAsync(bpad.p, 0, sizeof(float) * (size_t)B * cp, s));
-    HIPCHK(hipMemcpy2DAsync(gpad.p, sizeof(float) * cp, gamma_dev_f32, sizeof(float) * cout, sizeof(float) * cout, B, hipMemcpyDeviceToDevice, s));
-    HIPCHK(hipMemcpy2DAsync(bpad.p, sizeof(float) * cp, beta_dev_f32, sizeof(float) * cout, sizeof(float) * cout, B, hipMemcpyDeviceToDevice, s));
-    Runner run{&fake, s, dtype};
-    run.film_gamma = (const float*)gpad.p;
-    run.film_beta = (const float*)bpad.p;
-    run.conv3(c, in0, out, B, H, W, EPI_STORE, silu, 0, 0);
-    HIPCHK(hipStreamSynchronize(s));
-    return run.rc;
+    HIPCHK(hipMemsetAsync(gpad.p, 0, sizeof(float) * (size_t)B * cp, op.run.s));
+    HIPCHK(hipMemsetAsync(bpad.p, 0, sizeof(float) * (size_t)B * cp, op.run.s));
+    HIPCHK(hipMemcpy2DAsync(gpad.p, sizeof(float) * cp, gamma_dev_f32, sizeof(float) * cout, sizeof(float) * cout, B, hipMemcpyDeviceToDevice, op.run.s));
+    HIPCHK(hipMemcpy2DAsync(bpad.p, sizeof(float) * cp, beta_dev_f32, sizeof(float) * cout, sizeof(float) * cout, B, hipMemcpyDeviceToDevice, op.run.s));
+    Conv3Call k = film_call(c, in0, out, B, H, W, silu);
+    k.gamma = (const float*)gpad.p; k.beta = (const float*)bpad.p;
+    op.run.conv3(k);
+    return op.finish();
 }
 
 extern "C" int mz_op_stem(int dtype, const void* x, const float* w_dev_f32, const float* b_dev_f32, void* out, int B,
@@ -1329,17 +1377,14 @@ extern "C" int mz_op_final(int dtype, const void* feat, const void* img, const f
                            int W, int cin, int R, int clamp, void* hip_stream) {
     int rc = ensure_device_ready();
     if (rc) return rc;
-    hipStream_t s = (hipStream_t)hip_stream;
     ConvW c;
     plan_conv(c, dtype, MODE_CONV3, 12, cin, 3, 3, OUT_FINAL, SRC_PLAIN, 0, 0);
-    mz_handle fake;
-    rc = op_handle(fake, s);
-    if (!rc) rc = pack_conv(c, dtype, w_dev_f32, s);
-    if (rc) return rc;
-    Runner run{&fake, s, dtype};
-    run.conv3(c, feat, out, B, H, W, EPI_FINAL, 0, 2 * H, 2 * W, img, R, clamp);
-    HIPCHK(hipStreamSynchronize(s));
-    return run.rc;
+    OpRun op(dtype, hip_stream);
+    if (op.pack(c, w_dev_f32)) return op.rc;
+    Conv3Call k = head_call(c, feat, out, B, H, W);
+    k.img = img; k.R = R; k.clamp = clamp;
+    op.run.conv3(k);
+    return op.finish();
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1357,8 +1402,7 @@ extern "C" int mz_debug_tile_list(int B, int tiles_y, int tiles_x, int ntiles, i
     memset(&a, 0, sizeof(a));
     a.B = B; a.tiles_x = tiles_x; a.tiles_y = tiles_y; a.mtiles = B * tiles_x * tiles_y; a.ntiles = ntiles;
     a.gm = gm < a.mtiles ? gm : a.mtiles; a.gn = gn < ntiles ? gn : ntiles; a.blk4 = blk4 ? 1 : 0;
-    a.groups_m = (a.mtiles + a.gm - 1) / a.gm;
-    a.grid = a.groups_m * ((ntiles + a.gn - 1) / a.gn) * a.gm * a.gn;
+    set_walk(a);
     std::vector<uint32_t> t;
     tile_list(a, th, tw, t);
     const int n = (int)(t.size() / 2);
@@ -1397,8 +1441,8 @@ static const ConvW* plan_debug_layer(BlockW& b, int dtype, int op, int cin, int 
     return nullptr;
 }
 
-// Host-only (no GPU): the kernel family Runner::conv3 / Runner::mix would launch for one layer, with the knobs read from the environment
-// as the mz_op_* entries read them.
+// Host-only (no GPU): the kernel family Runner::conv3 / Runner::mix would launch for one layer -- the same role functions make the call,
+// the same choose_* choose -- with the knobs read from the environment as the mz_op_* entries read them.
 extern "C" const char* mz_debug_select(int dtype, int op, int cin, int cout, int B, int H, int W, int cus) {
     if ((dtype != MZ_F32 && dtype != MZ_BF16 && dtype != MZ_F16) || cin < 1 || cout < 1 || B < 1 || H < 1 || W < 1 || cus < 0) {
         fail(MZ_ERR_INVALID_ARGUMENT, "bad arguments");
@@ -1417,9 +1461,16 @@ extern "C" const char* mz_debug_select(int dtype, int op, int cin, int cout, int
     const ConvW* c = plan_debug_layer(b, dtype, op, cin, cout);
     if (!c) return nullptr;
     if (op == 7) return kernel_name(choose_mix(k, dtype, *c, B, H, W, cus));
-    const int epi = op == 2 ? EPI_D2S : op == 3 ? EPI_FINAL : op == 6 && fuse_mix(k, b) ? EPI_FUSEDMIX : EPI_STORE;
-    const int up = op == 2 || op == 3 ? 2 : 0;  // D2S / FINAL: into 2H x 2W
-    return kernel_name(choose_conv3(k, dtype, *c, epi == EPI_FUSEDMIX ? &b.mixf : nullptr, epi, op == 0, op == 5, B, H, W, up * H, up * W, cus));
+    Conv3Call call;  // no launch: no buffers
+    switch (op) {    // the public op codes -> the layer roles that mz_forward and the mz_op_* entries run
+        case 0: call = conv1_call(*c, nullptr, nullptr, B, H, W); break;
+        case 2: call = d2s_call(*c, nullptr, nullptr, B, H, W, 2 * H, 2 * W); break;
+        case 3: call = head_call(*c, nullptr, nullptr, B, H, W); break;
+        case 5: call = film_call(*c, nullptr, nullptr, B, H, W, 0); break;
+        case 6: call = conv2_call(k, b, nullptr, nullptr, B, H, W); break;
+        default: call = plain_call(*c, nullptr, nullptr, B, H, W); break;  // 1 plain, 4 the quality head's
+    }
+    return kernel_name(choose_conv3(k, dtype, call, cus));
 }
 
 // Host-only (no GPU): packing `layout` of one layer (mz_debug_select's ops; 8 = the fused gate of a block's conv2), as pack_kernel writes
@@ -1502,7 +1553,7 @@ extern "C" int mz_profile_read(mz_handle* h, double* conv_ms, double* conv_flops
         HIPCHK(hipEventSynchronize(r.b));
         float ms = 0.f;
         HIPCHK(hipEventElapsedTime(&ms, r.a, r.b));
-        if (r.is_conv3) { cm += ms; cf += r.flops; cl += 1; cb += r.bytes; }
+        if (r.kind == 0) { cm += ms; cf += r.flops; cl += 1; cb += r.bytes; }
         else om += ms;
     }
     if (conv_ms) *conv_ms = cm;

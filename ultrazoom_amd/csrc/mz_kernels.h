@@ -57,7 +57,8 @@ struct ConvArgs {
     float inv_gsz, inv_groups_m, inv_gn, inv_tpi, inv_tiles_x;  // 1.0f / divisor for fdiv() (all dividends < 2^24)
     int blk4;          // conv3s, the tile lists of conv3r / conv3t: tiles of an image are walked in block rows of four tile rows (tile_rc(), mz_device.h)
     float inv_bsz;     // 1.0f / (4 * tiles_x)
-    // the same divisors as floor(2^32 / d), for division on the scalar unit (unused since the relay kernels read the host's tile table)
+    // read by no kernel since the relay kernels read the host's tile table, and no longer set by the host (zero): kept for the offsets of
+    // the fields behind them, like s16 and use_glds below
     uint32_t mg_gsz, mg_groups_m, mg_gn, mg_tpi, mg_tiles_x, mg_bsz;
     int epi;
     int silu;
