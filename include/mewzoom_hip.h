@@ -111,6 +111,31 @@ int mz_forward(mz_handle* h, const void* x, void* out_sr, float* out_qa, int B, 
 int mz_forward_u8(mz_handle* h, const uint8_t* x, uint8_t* out_sr, float* out_qa, int B, int H, int W,
                   void* workspace, size_t workspace_bytes, int max_images_in_flight, void* hip_stream);
 
+/* Images as VIEWS at both ends: any layout that four element strides describe -- channels-last / interleaved HWC, a crop of a
+ * larger frame, every second image of a batch, BGR (a negative channel stride with `data` at channel 2) -- is read and written in
+ * place, without a copy on either side.  mz_forward and mz_forward_u8 are the dense NCHW special case.
+ *
+ * `data` is the address of element (image 0, channel 0, row 0, column 0) and needs the alignment of ONE element only; strides are
+ * counted in ELEMENTS and may be negative.  The library reads and writes exactly the elements the view names.  Overlap between x
+ * and out, or between elements of out, is the caller's responsibility and is not checked (beyond refusing an output stride of 0). */
+typedef struct mz_image_view {
+    void*   data;        /* element (image 0, channel 0, row 0, column 0) */
+    int64_t stride[4];   /* in ELEMENTS, signed: image, channel, row, column */
+} mz_image_view;
+
+/* x       view of [B,3,H,W]; out: view of the window of [B,3,rH,rW]; out_qa, clamp, workspace, micro-batches as for mz_forward
+ *         (micro-batches advance both views by stride[0]; mz_workspace_bytes is the same as for the dense entries).
+ * window  {y0, x0, h, w} in OUTPUT pixels of the rH x rW result, or NULL for all of it.  out->data is the element that receives
+ *         output pixel (y0, x0); out spans h x w pixels.  The window changes where results are stored, never what is computed: a
+ *         window of a result equals that part of the whole result bit for bit (tiling: the haloed slice as x, the core as window).
+ * elem    0 = the handle's dtype, 1 = uint8 (scaling and rounding exactly as mz_forward_u8; clamp is implied).
+ * Returns MZ_ERR_INVALID_ARGUMENT, before anything touches the GPU, for: a null view or null data; elem outside {0, 1}; a window
+ * that is empty or not inside [0, rH) x [0, rW); an output view whose channel, row or column stride is 0, or whose image stride
+ * is 0 when B > 1. */
+int mz_forward_view(mz_handle* h, const mz_image_view* x, const mz_image_view* out, float* out_qa,
+                    int B, int H, int W, int clamp, int elem, const int32_t window[4],
+                    void* workspace, size_t workspace_bytes, int max_images_in_flight, void* hip_stream);
+
 /* ---- single operators, exported for the parity tests (tests/test_ops_gpu.py) ---------------
  * These run the SAME kernels mz_forward launches, on caller-provided tensors.
  * Activation tensors here are the library's internal layout: plane-major [B][P][H][W][16 bytes], channel count padded

@@ -14,7 +14,7 @@ for cname, sub in (("FETCH_SIZE", "fetch"), ("WRITE_SIZE", "write")):
         for r in csv.DictReader(open(f)):
             # (the 3x3 family: the persistent kernels, and conv_kernel in its CONV3 mode -- template argument MODE = 0: the image head)
             k3 = any(k in r["Kernel_Name"] for k in ("conv3s_kernel", "conv3p_kernel", "conv3w_kernel", "conv3r_kernel", "conv3t_kernel")) or \
-                 ("conv_kernel<" in r["Kernel_Name"] and r["Kernel_Name"].split(">(")[0].endswith(", 0"))
+                 ("conv_kernel<" in r["Kernel_Name"] and r["Kernel_Name"].split(">(")[0].endswith((", 0", ", 0, false", ", 0, true")))
             if not k3 or r["Counter_Name"] != cname: continue
             tot[cname] += float(r["Counter_Value"]); n[cname].add(r["Dispatch_Id"])
 launches = len(n["FETCH_SIZE"]) or 1

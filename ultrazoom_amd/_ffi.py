@@ -36,6 +36,12 @@ class MzConfig(Structure):
     ]
 
 
+class MzImageView(Structure):
+    """mz_image_view: the address of element (image 0, channel 0, row 0, column 0) and four signed element strides."""
+
+    _fields_ = [("data", c_void_p), ("stride", c_int64 * 4)]
+
+
 class MewZoomHipError(RuntimeError):
     def __init__(self, code: int, message: str):
         super().__init__(f"libmewzoom_hip error {code}: {message}")
@@ -57,6 +63,9 @@ def _declare(lib) -> None:
     lib.mz_forward.argtypes = [H, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_int, c_void_p]
     lib.mz_forward_u8.argtypes = [H, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_size_t, c_int, c_void_p]
     lib.mz_forward_u8.restype = c_int
+    lib.mz_forward_view.argtypes = [H, POINTER(MzImageView), POINTER(MzImageView), c_void_p, c_int, c_int, c_int, c_int, c_int,
+                                    POINTER(c_int32), c_void_p, c_size_t, c_int, c_void_p]
+    lib.mz_forward_view.restype = c_int
     lib.mz_padded_channels.argtypes = [c_int]
     lib.mz_op_conv.argtypes = [c_int, c_int, c_void_p, c_void_p, c_void_p, c_float, c_void_p] + [c_int] * 8 + [c_void_p]
     lib.mz_op_conv_film.argtypes = [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p] + [c_int] * 6 + [c_void_p]
@@ -178,6 +187,20 @@ class Handle:
         check(
             lib().mz_forward_u8(
                 self._h, c_void_p(x_ptr), c_void_p(sr_ptr), c_void_p(qa_ptr) if qa_ptr else None, B, H, W,
+                c_void_p(ws_ptr), ws_bytes, max_in_flight, c_void_p(stream),
+            )
+        )
+
+    def forward_view(self, x_ptr, x_strides, out_ptr, out_strides, qa_ptr, B, H, W, clamp, elem, window, ws_ptr, ws_bytes,
+                     max_in_flight, stream) -> None:
+        """mz_forward_view: `x_ptr` / `out_ptr` address element (0, 0, 0, 0) of each view (out: of the window), the strides count
+        elements (image, channel, row, column; signed); `window` = (y0, x0, h, w) in output pixels or None; `elem` 1 = uint8."""
+        xv = MzImageView(c_void_p(x_ptr), (c_int64 * 4)(*[int(v) for v in x_strides]))
+        ov = MzImageView(c_void_p(out_ptr), (c_int64 * 4)(*[int(v) for v in out_strides]))
+        win = (c_int32 * 4)(*[int(v) for v in window]) if window is not None else None
+        check(
+            lib().mz_forward_view(
+                self._h, byref(xv), byref(ov), c_void_p(qa_ptr) if qa_ptr else None, B, H, W, int(clamp), int(elem), win,
                 c_void_p(ws_ptr), ws_bytes, max_in_flight, c_void_p(stream),
             )
         )

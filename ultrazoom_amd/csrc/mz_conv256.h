@@ -15,7 +15,8 @@ static constexpr bool kGlds = false;
 #else
 static constexpr bool kGlds = true;
 #endif
-template <class TT, int NT, int MODE>
+// VIEW (MODE_CONV3, EPI_FINAL): the image head on image views (final_epilogue<.., VIEW>)
+template <class TT, int NT, int MODE, bool VIEW = false>
 __global__ __launch_bounds__(256, 2) void conv_kernel(const ConvArgs a) {
     using G = Geo<MODE>;
     constexpr int SZ = TT::SZ;
@@ -51,6 +52,9 @@ __global__ __launch_bounds__(256, 2) void conv_kernel(const ConvArgs a) {
         const int ty = fdiv(rem, a.tiles_x, a.inv_tiles_x);
         y0 = ty * 8;
         x0 = (rem - ty * a.tiles_x) * 32;
+        if constexpr (VIEW) {
+            if (tile_outside_window(a, y0, x0, 8, 32)) return;  // (whole workgroup, uniform)
+        }
     } else {
         m0 = (long long)mtile * 256;
     }
@@ -183,7 +187,7 @@ __global__ __launch_bounds__(256, 2) void conv_kernel(const ConvArgs a) {
         const int ey[2] = {y0 + 2 * w, y0 + 2 * w + 1};
         const int ex[2] = {x0, x0};
         const long long em[2] = {m0 + 64 * w, m0 + 64 * w + 32};
-        conv_epilogue<TT, NT, MODE == MODE_CONV3>(a, a.epi, a.silu, acc, smem + w * EPW, smem + 4 * EPW + w * kFinalWinBytes, lane, nbase, b, ey, ex, em);
+        conv_epilogue<TT, NT, MODE == MODE_CONV3, VIEW>(a, a.epi, a.silu, acc, smem + w * EPW, smem + 4 * EPW + w * kFinalWinBytes, lane, nbase, b, ey, ex, em);
     }
 }
 

@@ -68,7 +68,8 @@ template <> struct ZFrag<TF16> {
     }
 };
 
-template <class TT, int NT, int MODE, bool FUSE>
+// VIEW (EPI_FINAL, not FUSE): the image head on image views (final_epilogue<.., VIEW>)
+template <class TT, int NT, int MODE, bool FUSE, bool VIEW = false>
 __global__ __launch_bounds__(576, 3) void conv3w_kernel(const ConvArgs a) {
     using G = Geo<MODE>;
     constexpr int SZ = TT::SZ;
@@ -94,6 +95,12 @@ __global__ __launch_bounds__(576, 3) void conv3w_kernel(const ConvArgs a) {
     const int last = nstages - 1;
     const int s0 = (3 - last % 3) % 3;  // slot(st) = (st + s0) % 3, so slot(last) == 0
     char* const mixw = smem + SLOT;     // FUSE: gate weights live in slots 1-2 once those are free
+    if constexpr (VIEW) {  // the tile's origin as the compute waves derive it below, ahead of the loader wave's branch
+        const int vtpi = a.tiles_x * a.tiles_y;
+        const int vrem = mtile - fdiv(mtile, vtpi, a.inv_tpi) * vtpi;
+        const int vty = fdiv(vrem, a.tiles_x, a.inv_tiles_x);
+        if (tile_outside_window(a, vty * G::TH, (vrem - vty * a.tiles_x) * G::TW, G::TH, G::TW)) return;  // (whole workgroup, uniform)
+    }
 
     if (w == 8) {
         // ------------------------- weight loader wave -------------------------
@@ -350,7 +357,7 @@ __global__ __launch_bounds__(576, 3) void conv3w_kernel(const ConvArgs a) {
         __builtin_amdgcn_s_barrier();  // every wave is done with the gate weights: the ring can take epilogue data
         conv_epilogue<TT, NT, true>(a, EPI_STORE, 0, acc, smem + w * EPW, smem + 8 * EPW + w * kFinalWinBytes, lane, nbase, b, ey, ex, em);
     } else {
-        conv_epilogue<TT, NT, true>(a, a.epi, a.silu, acc, smem + w * EPW, smem + 8 * EPW + w * kFinalWinBytes, lane, nbase, b, ey, ex, em);
+        conv_epilogue<TT, NT, true, VIEW>(a, a.epi, a.silu, acc, smem + w * EPW, smem + 8 * EPW + w * kFinalWinBytes, lane, nbase, b, ey, ex, em);
     }
 }
 

@@ -82,7 +82,10 @@ __device__ __forceinline__ void run_items(f32x16 (&acc)[2][NT], Frags<NT>& cur, 
 
 // PixelShuffle(2) + bicubic skip + residual add (+ clamp) -> NCHW image (reference model.py:926-930, 156, 162, 177).
 // U8: both images are uint8 (a compile-time switch: a per-load branch would serialise the 48 taps of every lane).
-template <class TT, int NT, bool U8>
+// VIEW: both images are strided views (ConvArgs::vin / vout, 64-bit element offsets) and only the output pixels inside the window are
+// stored; a lane then stores the three channels of one output pixel back to back, so that a packed HWC row of a wave is one run.
+// The arithmetic is the dense instantiation's, operation by operation: a view changes addresses, never values.
+template <class TT, int NT, bool U8, bool VIEW>
 __device__ __forceinline__ void final_epilogue(const ConvArgs& a, f32x16 (&acc)[2][NT], char* ep, char* win, int lane, int b,
                                                const int (&ey)[2], const int (&ex)[2]) {
     constexpr int SZ = TT::SZ;
@@ -111,7 +114,8 @@ __device__ __forceinline__ void final_epilogue(const ConvArgs& a, f32x16 (&acc)[
         for (int i2 = 0; i2 < 2; ++i2)
 #pragma unroll
             for (int c = 0; c < 3; ++c) zres[i2][c] = *(const float*)(ep + px * ROWF + ((2 * i2 + jj) * 4 + c) * 4);
-        if (y < a.H) {  // (wave-uniform)
+        // (wave-uniform; VIEW: a row pair outside the window's rows stores nothing)
+        if (y < a.H && (!VIEW || (2 * y + 1 >= a.win_y0 && 2 * y < a.win_y0 + a.win_h))) {
             // The bicubic skip reads a 4 x 4 window of the input image per output pixel.  The 64 output columns x 2 output rows of this
             // fragment share ONE window of 4 (R = 4, 8: both rows fall into the same phase half of a source pixel) or 5 (R = 2) image
             // rows x at most 37 columns x 3 channels: the wave loads it once, lane l taking column cbase + l of every row and channel
@@ -139,11 +143,12 @@ __device__ __forceinline__ void final_epilogue(const ConvArgs& a, f32x16 (&acc)[
             uint32_t wv[15];
 #pragma unroll
             for (int c = 0; c < 3; ++c) {
-                const long long ip = ((long long)b * 3 + c) * plane_i;
+                const long long ip = VIEW ? (long long)b * a.vin[0] + (long long)c * a.vin[1] : ((long long)b * 3 + c) * plane_i;
 #pragma unroll
                 for (int i = 0; i < 5; ++i) {
                     if (i == 4 && !five) { wv[c * 5 + i] = 0u; break; }
-                    wv[c * 5 + i] = ld_img_raw<TT, U8>(a.img, ip + (long long)min(max(rbase + i, 0), a.Hi - 1) * a.Wi + wcol);
+                    const long long row = min(max(rbase + i, 0), a.Hi - 1);
+                    wv[c * 5 + i] = ld_img_raw<TT, U8>(a.img, ip + (VIEW ? row * a.vin[2] + (long long)wcol * a.vin[3] : row * a.Wi + wcol));
                 }
             }
 #pragma unroll
@@ -159,6 +164,7 @@ __device__ __forceinline__ void final_epilogue(const ConvArgs& a, f32x16 (&acc)[
                 // window slot of the first tap: slot s holds column clamp(cbase + s), so slots o .. o + 3 are exactly the clamped taps
                 // clamp(kx + fx - 1 + k) of the per-lane version; 0 <= o, o + 3 <= 36 (R = 2)
                 const int o = kx + fx - 1 - cbase;
+                float res[2][3];  // VIEW: this lane's six results, stored pixel by pixel behind the channel loop
 #pragma unroll
                 for (int c = 0; c < 3; ++c) {
                     // the rows' horizontal sums once, shared by both output rows (same operations in the same order as a per-row loop)
@@ -179,13 +185,31 @@ __device__ __forceinline__ void final_epilogue(const ConvArgs& a, f32x16 (&acc)[
                         float v = sres + zres[i2][c];
                         if (a.clamp) v = fminf(fmaxf(v, 0.0f), 1.0f);
                         const int Y = 2 * y + i2;
-                        st_img<TT, U8>(a.out, (((long long)b * 3 + c) * plane_o) + (long long)Y * a.Wout + X, v);
+                        if constexpr (VIEW) res[i2][c] = v;
+                        else st_img<TT, U8>(a.out, (((long long)b * 3 + c) * plane_o) + (long long)Y * a.Wout + X, v);
+                    }
+                }
+                if constexpr (VIEW) {
+                    const int Xw = X - a.win_x0;
+#pragma unroll
+                    for (int i2 = 0; i2 < 2; ++i2) {
+                        const int Yw = 2 * y + i2 - a.win_y0;
+                        if ((unsigned)Yw >= (unsigned)a.win_h || (unsigned)Xw >= (unsigned)a.win_w) continue;
+                        const long long op = (long long)b * a.vout[0] + (long long)Yw * a.vout[2] + (long long)Xw * a.vout[3];
+#pragma unroll
+                        for (int c = 0; c < 3; ++c) st_img<TT, U8>(a.out, op + (long long)c * a.vout[1], res[i2][c]);
                     }
                 }
             }
         }
         __builtin_amdgcn_wave_barrier();
     }
+}
+
+// VIEW: true when none of the 2 th x 2 tw output pixels of the image head's tile at (y0, x0) lies inside the window: the workgroup
+// would store nothing and may return before its K loop (upscale_tiled: the halo of a tile)
+__device__ __forceinline__ bool tile_outside_window(const ConvArgs& a, int y0, int x0, int th, int tw) {
+    return 2 * y0 >= a.win_y0 + a.win_h || 2 * (y0 + th) <= a.win_y0 || 2 * x0 >= a.win_x0 + a.win_w || 2 * (x0 + tw) <= a.win_x0;
 }
 
 // Store epilogues (STORE, D2S, MIX), specialised at compile time; `conv_epilogue` below dispatches.
@@ -283,14 +307,15 @@ __device__ __forceinline__ void store_epilogue(const ConvArgs& a, f32x16 (&acc)[
 // wave's own region `ep`).  Pixel geometry of the wave's two M fragments:
 //   IS_CONV: fragment mf covers pixels (ey[mf], ex[mf] + r) of image b;   else: linear pixels em[mf] + r.
 // ================================================================================================
-template <class TT, int NT, bool IS_CONV>
+// VIEW: EPI_FINAL reads and writes image views (the kernels' VIEW instantiations)
+template <class TT, int NT, bool IS_CONV, bool VIEW = false>
 __device__ __forceinline__ void conv_epilogue(const ConvArgs& a, const int epi, const int silu, f32x16 (&acc)[2][NT], char* ep,
                                               char* win, int lane, int nbase, int b, const int (&ey)[2], const int (&ex)[2],
                                               const long long (&em)[2]) {
     if (epi == EPI_FINAL) {
         if (IS_CONV) {
-            if (a.io_u8) final_epilogue<TT, NT, true>(a, acc, ep, win, lane, b, ey, ex);
-            else final_epilogue<TT, NT, false>(a, acc, ep, win, lane, b, ey, ex);
+            if (a.io_u8) final_epilogue<TT, NT, true, VIEW>(a, acc, ep, win, lane, b, ey, ex);
+            else final_epilogue<TT, NT, false, VIEW>(a, acc, ep, win, lane, b, ey, ex);
         }
         return;
     }

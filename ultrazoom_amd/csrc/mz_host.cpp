@@ -736,6 +736,7 @@ struct Conv3Call {
     float alpha = 0.f;
     const void* img = nullptr;    // EPI_FINAL: the low-resolution image, the total upscale ratio, clamp to [0, 1]
     int R = 0, clamp = 0;
+    const ImageViews* views = nullptr;  // EPI_FINAL: img and out are strided image views, stored inside a window (mz_forward_view)
     const float *gamma = nullptr, *beta = nullptr;  // film: float [B][padded cout] each
 };
 // a plain 3x3 convolution: a block's unfused conv2 (model.py:746-748), the quality head's (:1010)
@@ -1028,6 +1029,11 @@ struct Runner {
         a.Hout = k.Hout; a.Wout = k.Wout;
         a.img = k.img; a.R = k.R; a.clamp = k.clamp;
         if (k.epi == EPI_FINAL) { a.Hi = k.Hout / k.R; a.Wi = k.Wout / k.R; a.io_u8 = io_u8; }
+        if (k.epi == EPI_FINAL && k.views) {  // the kernel chosen above, in its VIEW instantiation
+            a.view = 1;
+            for (int i = 0; i < 4; ++i) { a.vin[i] = k.views->in[i]; a.vout[i] = k.views->out[i]; }
+            a.win_y0 = k.views->y0; a.win_x0 = k.views->x0; a.win_h = k.views->h; a.win_w = k.views->w;
+        }
         const bool fused = ch.fused;
         if (fused) {
             a.in1 = k.xin;
@@ -1111,8 +1117,9 @@ struct Runner {
 // ------------------------------------------------------------------------------------------------
 // forward
 // ------------------------------------------------------------------------------------------------
+// views: x and out_sr are the first elements of image views (out_sr: of the window) instead of dense NCHW tensors
 static int forward_micro(mz_handle* h, const char* x, char* out_sr, float* out_qa, int nb, int H, int W, int clamp,
-                         char* ws, hipStream_t s, int io_u8) {
+                         char* ws, hipStream_t s, int io_u8, const ImageViews* views) {
     Plan p;
     make_plan(h, nb, H, W, p);
     Runner run{h, s, h->dtype};
@@ -1131,7 +1138,8 @@ static int forward_micro(mz_handle* h, const char* x, char* out_sr, float* out_q
 
     // stem (model.py:158): NCHW image -> NHWC features
     char* cur = ws + p.R[0][0];
-    if (hipError_t e = launch_stem(h->dtype, x, (const float*)h->stem_w4.p, cur, nb, H, W, pad16(h->ch[0]), s, io_u8); e != hipSuccess)
+    if (hipError_t e = launch_stem(h->dtype, x, (const float*)h->stem_w4.p, cur, nb, H, W, pad16(h->ch[0]), s, io_u8, views ? views->in : nullptr);
+        e != hipSuccess)
         return fail(MZ_ERR_HIP, "stem launch: %s", hipGetErrorString(e));
 
     // encoder (model.py:461-484)
@@ -1208,7 +1216,7 @@ static int forward_micro(mz_handle* h, const char* x, char* out_sr, float* out_q
         const bool last = i == h->nhead - 1;
         if (last) {
             Conv3Call head = head_call(*h->head_up[i], y, out_sr, nb, hh, ww);
-            head.img = x; head.R = r; head.clamp = clamp;
+            head.img = x; head.R = r; head.clamp = clamp; head.views = views;
             run.conv3(head);
         } else {
             char* nxt = ws + p.HR[i + 1][0];
@@ -1221,7 +1229,8 @@ static int forward_micro(mz_handle* h, const char* x, char* out_sr, float* out_q
 }
 
 static int forward_impl(mz_handle* h, const void* x, void* out_sr, float* out_qa, int B, int H, int W, int clamp,
-                        void* workspace, size_t workspace_bytes, int max_images_in_flight, void* hip_stream, int io_u8) {
+                        void* workspace, size_t workspace_bytes, int max_images_in_flight, void* hip_stream, int io_u8,
+                        const ImageViews* views = nullptr) {
     if (!h || !x || !out_sr || !workspace) return fail(MZ_ERR_INVALID_ARGUMENT, "null argument");
     if (B <= 0 || H < 8 || W < 8) return fail(MZ_ERR_INVALID_ARGUMENT, "need B >= 1 and H, W >= 8 (got %d, %d, %d)", B, H, W);
     int rc = mz_weights_complete(h);
@@ -1233,13 +1242,14 @@ static int forward_impl(mz_handle* h, const void* x, void* out_sr, float* out_qa
         return fail(MZ_ERR_WORKSPACE_TOO_SMALL, "workspace too small: %zu bytes given, %zu needed", workspace_bytes, p.total);
     const size_t sz = io_u8 ? 1 : dtype_size(h->dtype);
     const int r = h->cfg.upscale_ratio;
-    const size_t in_img = (size_t)3 * H * W * sz;
-    const size_t out_img = (size_t)3 * H * r * W * r * sz;
+    // bytes from one image to the next: dense NCHW, or the views' image strides (signed)
+    const long long in_img = views ? views->in[0] * (long long)sz : (long long)((size_t)3 * H * W * sz);
+    const long long out_img = views ? views->out[0] * (long long)sz : (long long)((size_t)3 * H * r * W * r * sz);
     for (int b0 = 0; b0 < B; b0 += nbmax) {
         const int nb = std::min(nbmax, B - b0);
         rc = forward_micro(h, (const char*)x + b0 * in_img, (char*)out_sr + b0 * out_img,
                            out_qa ? out_qa + (size_t)b0 * h->cfg.num_deg_features : nullptr, nb, H, W, clamp,
-                           (char*)workspace, (hipStream_t)hip_stream, io_u8);
+                           (char*)workspace, (hipStream_t)hip_stream, io_u8, views);
         if (rc) return rc;
     }
     return MZ_OK;
@@ -1254,6 +1264,37 @@ extern "C" int mz_forward_u8(mz_handle* h, const uint8_t* x, uint8_t* out_sr, fl
                              void* workspace, size_t workspace_bytes, int max_images_in_flight, void* hip_stream) {
     return forward_impl(h, x, out_sr, out_qa, B, H, W, /*clamp (implied by the uint8 store)*/ 1, workspace, workspace_bytes,
                         max_images_in_flight, hip_stream, 1);
+}
+
+// Images as views at both ends: every check before the weights check and before any HIP call, so that a bad call is refused on a
+// machine without a GPU as well.  mz_forward / mz_forward_u8 are the dense special case and keep their own kernels.
+extern "C" int mz_forward_view(mz_handle* h, const mz_image_view* x, const mz_image_view* out, float* out_qa, int B, int H, int W,
+                               int clamp, int elem, const int32_t window[4], void* workspace, size_t workspace_bytes,
+                               int max_images_in_flight, void* hip_stream) {
+    if (!h) return fail(MZ_ERR_INVALID_ARGUMENT, "null handle");
+    if (!x || !out) return fail(MZ_ERR_INVALID_ARGUMENT, "null image view");
+    if (!x->data || !out->data) return fail(MZ_ERR_INVALID_ARGUMENT, "an image view has null data");
+    if (elem != 0 && elem != 1) return fail(MZ_ERR_INVALID_ARGUMENT, "elem must be 0 (the handle's dtype) or 1 (uint8), got %d", elem);
+    if (B <= 0 || H < 8 || W < 8) return fail(MZ_ERR_INVALID_ARGUMENT, "need B >= 1 and H, W >= 8 (got %d, %d, %d)", B, H, W);
+    const long long rH = (long long)h->cfg.upscale_ratio * H, rW = (long long)h->cfg.upscale_ratio * W;
+    if (rH > 0x7fffffffLL || rW > 0x7fffffffLL) return fail(MZ_ERR_INVALID_ARGUMENT, "the output of %d x %d is too large", H, W);
+    ImageViews v;
+    v.y0 = 0; v.x0 = 0; v.h = (int)rH; v.w = (int)rW;
+    if (window) {
+        v.y0 = window[0]; v.x0 = window[1]; v.h = window[2]; v.w = window[3];
+        if (v.h <= 0 || v.w <= 0) return fail(MZ_ERR_INVALID_ARGUMENT, "empty window (%d x %d)", v.h, v.w);
+        if (v.y0 < 0 || v.x0 < 0 || (long long)v.y0 + v.h > rH || (long long)v.x0 + v.w > rW)
+            return fail(MZ_ERR_INVALID_ARGUMENT, "window {%d, %d, %d, %d} is not inside the %lld x %lld output", v.y0, v.x0, v.h, v.w, rH, rW);
+    }
+    static const char* const dim[4] = {"image", "channel", "row", "column"};
+    for (int i = 0; i < 4; ++i) {
+        v.in[i] = x->stride[i];
+        v.out[i] = out->stride[i];
+        if (out->stride[i] == 0 && (i > 0 || B > 1))
+            return fail(MZ_ERR_INVALID_ARGUMENT, "the output view's %s stride is 0: its elements would overlap", dim[i]);
+    }
+    return forward_impl(h, x->data, out->data, out_qa, B, H, W, elem == 1 ? 1 : clamp, workspace, workspace_bytes,
+                        max_images_in_flight, hip_stream, elem, &v);
 }
 
 // ------------------------------------------------------------------------------------------------

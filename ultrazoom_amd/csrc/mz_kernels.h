@@ -84,6 +84,18 @@ struct ConvArgs {
     const float* film_beta;   //   (float [B][cp_out], pad channels zero); nullptr = off.  No reference counterpart.
     int use_glds;      // read by no kernel and no launcher
     unsigned long long* dbg;  // -DMZ_DIAG builds (mz_diag.h): cycle counters of one workgroup of conv3r_kernel
+    // EPI_FINAL through image views (mz_forward_view), read by the VIEW instantiations only: img = element (image 0, channel 0, row 0,
+    // column 0) of the input view, out = the element that receives output pixel (win_y0, win_x0); strides in ELEMENTS, signed: image,
+    // channel, row, column.  Only output pixels inside the window [win_y0, win_y0 + win_h) x [win_x0, win_x0 + win_w) are stored.
+    int view;
+    long long vin[4], vout[4];
+    int win_y0, win_x0, win_h, win_w;
+};
+
+// The two image views of one mz_forward_view call and its output window (Conv3Call -> ConvArgs::vin / vout / win_*; launch_stem reads in)
+struct ImageViews {
+    long long in[4], out[4];  // element strides: image, channel, row, column
+    int y0, x0, h, w;         // the window in output pixels
 };
 
 // picks NT (32*NT output channels per workgroup) for a logical padded N
@@ -121,7 +133,8 @@ constexpr int kMaxDevices = 64;  // device ordinals with per-device state (the r
 inline bool walk_ok(const ConvArgs& a) {
     return a.mtiles > 0 && a.ntiles > 0 && a.gm > 0 && a.gn > 0 && a.grid > 0 && a.grid < (1 << 24);
 }
-// conv_kernel<TT, NT, mode>, mode = MODE_CONV3 / MODE_GEMM1, nt = 1..4: a.grid workgroups of 256 threads
+// conv_kernel<TT, NT, mode>, mode = MODE_CONV3 / MODE_GEMM1, nt = 1..4: a.grid workgroups of 256 threads.  a.view: the image head's VIEW
+// instantiations (EPI_FINAL, nt = 1; conv_kernel: MODE_CONV3, conv3w_kernel: f32), anything else is hipErrorInvalidValue
 hipError_t launch_conv256(int dtype, int mode, int nt, const ConvArgs& a, hipStream_t s);
 // The 512-pixel kernels, mode = MODE_C3W16 / MODE_C3W8, nt = 1..3.  conv3w: a.grid workgroups, one per tile, any epilogue.  conv3p and
 // conv3s: a.persist workgroups, EPI_STORE / EPI_D2S; conv3s also EPI_FUSEDMIX, 16-bit types only, a.wpk16 / a.nchunks16 = PK_CONV16
@@ -181,8 +194,9 @@ hipError_t launch_pack(const PackArgs& a, hipStream_t s);
 // ---- small kernels ----------------------------------------------------------------------------
 // stem weights: float [cp][4] = {w0, w1, w2, bias}
 hipError_t launch_pack_stem(const float* w, const float* b, float* dst, int c, int cp, hipStream_t s);
+// vin: x is a view with these element strides (image, channel, row, column) instead of dense NCHW
 hipError_t launch_stem(int dtype, const void* x, const float* w4, void* out, int B, int H, int W, int cp,
-                       hipStream_t s, int u8 = 0);
+                       hipStream_t s, int u8 = 0, const long long* vin = nullptr);
 // zero rows >= Hv and columns >= Wv of an NHWC tensor [B,Hout,Wout,cp]
 hipError_t launch_zero_border(int dtype, void* t, int B, int Hout, int Wout, int cp, int Hv, int Wv,
                               hipStream_t s);

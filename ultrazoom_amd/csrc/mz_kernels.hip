@@ -50,18 +50,11 @@ hipError_t launch_pack_stem(const float* w, const float* b, float* dst, int c, i
 }
 
 // FanOutProjection (reference model.py:239-242): per-pixel 3 -> C affine, NCHW image -> plane-major features.
-template <class TT, bool U8> __global__ void stem_kernel(const void* x, const float4* w4, void* out, long long total,
-                                                          long long HW, int groups) {
+// channels 8 g .. 8 g + 7 of pixel p of image b from its three colour values
+template <class TT> __device__ __forceinline__ void stem_project(const float4* w4, void* out, long long b, int g, long long p, long long HW,
+                                                                 int groups, float r0, float r1, float r2) {
     constexpr int SZ = TT::SZ;
     constexpr int NPL = SZ / 2;  // planes per group of 8 channels
-    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= total) return;
-    const long long p = idx % HW;  // pixel fastest: loads and stores are contiguous along p
-    const long long t = idx / HW;
-    const int g = (int)(t % groups);
-    const long long b = t / groups;
-    const long long xi = b * 3 * HW + p;
-    const float r0 = ld_img<TT, U8>(x, xi), r1 = ld_img<TT, U8>(x, xi + HW), r2 = ld_img<TT, U8>(x, xi + 2 * HW);
     float v[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
@@ -77,12 +70,58 @@ template <class TT, bool U8> __global__ void stem_kernel(const void* x, const fl
         st4<TT>(op + HW * 16, v + 4);
     }
 }
+template <class TT, bool U8> __global__ void stem_kernel(const void* x, const float4* w4, void* out, long long total,
+                                                          long long HW, int groups) {
+    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= total) return;
+    const long long p = idx % HW;  // pixel fastest: loads and stores are contiguous along p
+    const long long t = idx / HW;
+    const int g = (int)(t % groups);
+    const long long b = t / groups;
+    const long long xi = b * 3 * HW + p;
+    const float r0 = ld_img<TT, U8>(x, xi), r1 = ld_img<TT, U8>(x, xi + HW), r2 = ld_img<TT, U8>(x, xi + 2 * HW);
+    stem_project<TT>(w4, out, b, g, p, HW, groups, r0, r1, r2);
+}
+// The same from an image view: element (b, c, y, x) at x[b s0 + c s1 + y s2 + x s3] (element strides, signed).  The plane-major store
+// is the dense kernel's.
+struct StemView {
+    long long s[4];
+    int W;
+};
+template <class TT, bool U8> __global__ void stem_view_kernel(const void* x, const float4* w4, void* out, long long total,
+                                                               long long HW, int groups, const StemView v) {
+    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= total) return;
+    const long long p = idx % HW;
+    const long long t = idx / HW;
+    const int g = (int)(t % groups);
+    const long long b = t / groups;
+    const long long py = p / v.W, px = p - py * v.W;
+    const long long xi = b * v.s[0] + py * v.s[2] + px * v.s[3];
+    const float r0 = ld_img<TT, U8>(x, xi), r1 = ld_img<TT, U8>(x, xi + v.s[1]), r2 = ld_img<TT, U8>(x, xi + 2 * v.s[1]);
+    stem_project<TT>(w4, out, b, g, p, HW, groups, r0, r1, r2);
+}
 hipError_t launch_stem(int dtype, const void* x, const float* w4, void* out, int B, int H, int W, int cp, hipStream_t s,
-                       int u8) {
+                       int u8, const long long* vin) {
     const long long HW = (long long)H * W;
     const int groups = cp / 8;
     const long long total = HW * B * groups;
     const int blocks = (int)((total + 255) / 256);
+    if (vin) {
+        const StemView v = {{vin[0], vin[1], vin[2], vin[3]}, W};
+        auto go = [&](auto tt) {
+            using TT = decltype(tt);
+            if (u8) hipLaunchKernelGGL((stem_view_kernel<TT, true>), dim3(blocks), dim3(256), 0, s, x, (const float4*)w4, out, total, HW, groups, v);
+            else hipLaunchKernelGGL((stem_view_kernel<TT, false>), dim3(blocks), dim3(256), 0, s, x, (const float4*)w4, out, total, HW, groups, v);
+        };
+        switch (dtype) {
+            case DT_F32: go(TF32{}); break;
+            case DT_BF16: go(TBF16{}); break;
+            case DT_F16: go(TF16{}); break;
+            default: return hipErrorInvalidValue;
+        }
+        return hipGetLastError();
+    }
     switch (dtype) {
         case DT_F32: if (u8) hipLaunchKernelGGL((stem_kernel<TF32, true>), dim3(blocks), dim3(256), 0, s, x, (const float4*)w4, out, total, HW, groups); else hipLaunchKernelGGL((stem_kernel<TF32, false>), dim3(blocks), dim3(256), 0, s, x, (const float4*)w4, out, total, HW, groups); break;
         case DT_BF16: if (u8) hipLaunchKernelGGL((stem_kernel<TBF16, true>), dim3(blocks), dim3(256), 0, s, x, (const float4*)w4, out, total, HW, groups); else hipLaunchKernelGGL((stem_kernel<TBF16, false>), dim3(blocks), dim3(256), 0, s, x, (const float4*)w4, out, total, HW, groups); break;

@@ -291,7 +291,10 @@ class MewZoom(nn.Module, PyTorchModelHubMixin):
     def _run(self, x: Tensor, clamp: bool, want_qa: bool):
         assert x.dim() == 4 and x.shape[1] == 3, "expected a (B, 3, H, W) tensor"
         engine = self._get_engine(x)
-        return engine.run(x.contiguous(), clamp, want_qa, self.max_images_in_flight)
+        if x.is_contiguous():
+            return engine.run(x, clamp, want_qa, self.max_images_in_flight)
+        # any other layout (channels_last, a permuted HWC frame, a crop, a strided batch) is read in place: no copy
+        return engine.run_view(x, None, None, clamp, want_qa, self.max_images_in_flight)
 
     # ---- the reference's public methods -----------------------------------------------------
     def forward(self, x: Tensor) -> Tuple[Tensor, Tensor]:
@@ -323,7 +326,46 @@ class MewZoom(nn.Module, PyTorchModelHubMixin):
             raise RuntimeError("ultrazoom_amd.MewZoom computes on an MI355X only: move the input to a 'cuda' device.")
         p0 = next(self.parameters())
         engine = self._get_engine(torch.empty(0, dtype=p0.dtype, device=x.device))
-        return engine.run_u8(x.contiguous(), self.max_images_in_flight)
+        if x.is_contiguous():
+            return engine.run_u8(x, self.max_images_in_flight)
+        return engine.run_view(x, None, None, True, False, self.max_images_in_flight)[0]
+
+    @torch.inference_mode()
+    def upscale_into(self, x: Tensor, out: Tensor, window: Optional[Tuple[int, int, int, int]] = None) -> Tensor:
+        """``upscale(x)`` (``upscale_uint8(x)`` for uint8 tensors) written straight into ``out``; returns ``out``.
+
+        ``x`` and ``out`` are logical ``[B, 3, H, W]`` / ``[B, 3, h, w]`` tensors with ANY strides: channels_last, a permuted
+        HWC frame, a crop of a larger frame, every second image of a batch.  Nothing is copied on either side.  ``window`` =
+        ``(y0, x0, h, w)`` in output pixels selects the part of the ``rH x rW`` result that is stored (``out`` has its shape);
+        without one ``out`` is ``[B, 3, rH, rW]``.  The window changes where results go, never what is computed: a tile of
+        ``tiling.upscale_tiled`` passes its haloed slice as ``x`` and its core as the window.  ``x`` and ``out`` must not
+        overlap, and ``out`` must not overlap itself (expanded dimensions)."""
+        if x.dim() != 4 or x.shape[1] != 3 or out.dim() != 4:
+            raise RuntimeError(f"expected (B, 3, H, W) tensors, got {tuple(x.shape)} and {tuple(out.shape)}")
+        if out.device != x.device:
+            raise RuntimeError(f"the input is on {x.device} but the output is on {out.device}")
+        p0 = next(self.parameters())
+        if x.dtype == torch.uint8:
+            if out.dtype != torch.uint8:
+                raise RuntimeError(f"uint8 input needs a uint8 output, got {out.dtype}")
+            engine = self._get_engine(torch.empty(0, dtype=p0.dtype, device=x.device))
+        else:
+            if out.dtype != x.dtype:
+                raise RuntimeError(f"Input type ({x.dtype}) and output type ({out.dtype}) should be the same")
+            engine = self._get_engine(x)
+        B, _, H, W = x.shape
+        r = self.upscale_ratio
+        if window is None:
+            want = (B, 3, H * r, W * r)
+        else:
+            window = tuple(int(v) for v in window)
+            if len(window) != 4:
+                raise RuntimeError("window is (y0, x0, h, w) in output pixels")
+            want = (B, 3, window[2], window[3])
+        if tuple(out.shape) != want:
+            raise RuntimeError(f"the output has shape {tuple(out.shape)}, expected {want}")
+        engine.run_view(x, out, window, True, False, self.max_images_in_flight)
+        return out
 
     # ---- checkpoint ingestion (test_compare.py:32-45 of the reference) -------------------------
     def load_training_checkpoint(self, state_dict: Dict[str, Tensor], lora_alpha: Optional[float] = None) -> None:
@@ -446,6 +488,24 @@ class _Engine:
             )
             self._mark_done(stream)
         return sr, qa
+
+    def run_view(self, x: Tensor, out: Optional[Tensor], window, clamp: bool, want_qa: bool, max_in_flight: int):
+        """The same through mz_forward_view: x (and out, when given) with any strides, read and written in place.  uint8 tensors
+        take the fused uint8 ends.  Without `out` the result is a new dense NCHW tensor."""
+        B, _, H, W = x.shape
+        r = self.config["upscale_ratio"]
+        with torch.cuda.device(self.device):
+            stream = torch.cuda.current_stream(self.device)
+            ws = self._workspace_for(self.handle.workspace_bytes(B, H, W, max_in_flight), stream)
+            if out is None:
+                out = torch.empty((B, 3, H * r, W * r), dtype=x.dtype, device=self.device)
+            qa = torch.empty((B, self.config["num_deg_features"]), dtype=torch.float32, device=self.device) if want_qa else None
+            self.handle.forward_view(
+                x.data_ptr(), x.stride(), out.data_ptr(), out.stride(), qa.data_ptr() if want_qa else 0, B, H, W, clamp,
+                1 if x.dtype == torch.uint8 else 0, window, ws.data_ptr(), ws.numel(), max_in_flight, stream.cuda_stream,
+            )
+            self._mark_done(stream)
+        return out, qa
 
     def run_u8(self, x: Tensor, max_in_flight: int) -> Tensor:
         B, _, H, W = x.shape

@@ -40,7 +40,12 @@ def receptive_field(config: dict) -> int:
 def upscale_tiled(model, x: Tensor, tile: Tuple[int, int] = (512, 512), halo: Optional[int] = None) -> Tensor:
     """`model.upscale(x)` computed tile by tile.  `tile` = core size in low-resolution pixels (rounded up to multiples
     of 8); `halo` defaults to `receptive_field(config)`; a smaller halo is refused, because the result would no
-    longer equal the untiled one."""
+    longer equal the untiled one.
+
+    A model that offers `upscale_into` (MewZoom) gets one call per tile with the haloed slice of `x` as an input view,
+    the tile's core as the output window and the core's place in the result as the output view: no slice is copied, no
+    haloed tile is written anywhere, and uint8 input gives `model.upscale_uint8(x)`.  Any other object with `upscale`
+    is called on contiguous slices and the cores are copied out, as before."""
     if x.dim() != 4 or x.shape[1] != 3:
         raise ValueError("expected a [B, 3, H, W] tensor")
     cfg = model._cfg
@@ -52,12 +57,17 @@ def upscale_tiled(model, x: Tensor, tile: Tuple[int, int] = (512, 512), halo: Op
     B, _, H, W = x.shape
     r = cfg["upscale_ratio"]
     out = torch.empty((B, 3, H * r, W * r), dtype=x.dtype, device=x.device)
+    into = getattr(model, "upscale_into", None)
     for y0 in range(0, H, th):
         y1 = min(H, y0 + th)
         ya, yb = max(0, y0 - halo), min(H, y1 + halo)
         for x0 in range(0, W, tw):
             x1 = min(W, x0 + tw)
             xa, xb = max(0, x0 - halo), min(W, x1 + halo)
+            core = out[:, :, y0 * r : y1 * r, x0 * r : x1 * r]
+            if into is not None:
+                into(x[:, :, ya:yb, xa:xb], core, window=((y0 - ya) * r, (x0 - xa) * r, (y1 - y0) * r, (x1 - x0) * r))
+                continue
             sr = model.upscale(x[:, :, ya:yb, xa:xb].contiguous())
-            out[:, :, y0 * r : y1 * r, x0 * r : x1 * r] = sr[:, :, (y0 - ya) * r : (y1 - ya) * r, (x0 - xa) * r : (x1 - xa) * r]
+            core.copy_(sr[:, :, (y0 - ya) * r : (y1 - ya) * r, (x0 - xa) * r : (x1 - xa) * r])
     return out
