@@ -173,6 +173,41 @@ int mz_op_conv_film(int dtype, const void* in0, const float* w_dev_f32, const fl
                     const float* beta_dev_f32, void* out, int B, int H, int W, int cin, int cout, int silu,
                     void* hip_stream);
 
+/* ---- image-quality metrics: no reference counterpart in `model.py`; stands in for torchmetrics as the reference's
+ *      `pretrain.py:209-211, 301-329` uses it (PeakSignalNoiseRatio, StructuralSimilarityIndexMeasure,
+ *      VisualInformationFidelity with their defaults; ultrazoom_amd/evaluate.py restates them) ------------------------------------
+ * Stateless like the mz_op_* entries (no handle): the calls enqueue on the given stream and never synchronise.  Both images are
+ * VIEWS of one logical shape [B,3,H,W] (mz_image_view above: any strides, nothing is copied) and of one element type; a uint8
+ * value v means v / 255, as in mz_forward_u8.  All arithmetic is float64; reductions add in a fixed order (no atomics), so two
+ * calls give the same bits and the sums of an image do not depend on the batch it is measured in (SSIM with data_range <= 0
+ * excepted, by its definition).
+ *
+ * out_dev[b][slot], float64, MZ_METRIC_SLOTS per image:
+ *    0      sum of (p - t)^2 over the image            1      its element count 3 H W            (PSNR, bit 0; also written when
+ *    2, 3   min, max of p                              4, 5   min, max of t                       SSIM takes its range from the batch)
+ *    6      sum of the SSIM map: the 3 (H-10) (W-10) pixels whose 11 x 11 Gaussian window (sigma 1.5) lies inside the image -- what
+ *           torchmetrics keeps after reflect-padding by 5 and cropping 5 again;   7   that pixel count;   14  the data range used   (SSIM, bit 1)
+ *    8..10  per channel: sum over the four scales (windows of 17, 9, 5, 3 taps, sigma = taps / 5, "valid" filtering, every second
+ *           row and column between scales) of log10(1 + g^2 s_tt / (s_v + sigma_n_sq));   11..13  ... of log10(1 + s_tt / sigma_n_sq)   (VIF, bit 2)
+ *    15     reserved
+ * The caller divides: MSE = slot 0 / slot 1 (over all updates), SSIM = slot 6 / slot 7, VIF = mean over channels of
+ * slot (8 + c) / slot (11 + c) -- 0 / 0 stays NaN exactly where the torch restatement gives NaN.  Slots of metrics that were not
+ * requested are left as they were.
+ *
+ * Return MZ_ERR_INVALID_ARGUMENT, before anything touches the GPU, for: a null view or null data; elem outside 0..3; which == 0 or
+ * with unknown bits; B, H or W < 1 (or B > 65535); H or W < 11 with SSIM; H or W < 41 with VIF; a null out_dev.
+ * MZ_ERR_WORKSPACE_TOO_SMALL as elsewhere. */
+#define MZ_METRIC_SLOTS 16
+#define MZ_METRIC_PSNR 1
+#define MZ_METRIC_SSIM 2
+#define MZ_METRIC_VIF 4
+/* which: bit 0 PSNR, bit 1 SSIM, bit 2 VIF.  Host only. */
+int mz_metrics_workspace_bytes(int B, int H, int W, int which, size_t* bytes);
+/* elem: 0..2 = mz_dtype, 3 = uint8.  data_range (SSIM): > 0 fixed; <= 0: max(range of pred, range of target) of THIS batch, found on
+ * the device, as torchmetrics' data_range=None.  sigma_n_sq (VIF): the reference's default is 2.0. */
+int mz_metrics(const mz_image_view* pred, const mz_image_view* target, int elem, int B, int H, int W, int which,
+               double data_range, double sigma_n_sq, double* out_dev, void* workspace, size_t workspace_bytes, void* hip_stream);
+
 /* ---- introspection ------------------------------------------------------------------------ */
 const char* mz_last_error(void);
 const char* mz_version(void);

@@ -18,6 +18,10 @@ LIB_PATH = Path(__file__).resolve().parent / LIB_NAME
 MZ_F32, MZ_BF16, MZ_F16 = 0, 1, 2
 
 MZ_ERR_INVALID_ARGUMENT = -1
+MZ_ERR_WORKSPACE_TOO_SMALL = -5
+
+MZ_METRIC_SLOTS = 16  # doubles per image of mz_metrics' output (include/mewzoom_hip.h documents the slots)
+MZ_METRIC_PSNR, MZ_METRIC_SSIM, MZ_METRIC_VIF = 1, 2, 4
 
 
 class MzConfig(Structure):
@@ -66,6 +70,11 @@ def _declare(lib) -> None:
     lib.mz_forward_view.argtypes = [H, POINTER(MzImageView), POINTER(MzImageView), c_void_p, c_int, c_int, c_int, c_int, c_int,
                                     POINTER(c_int32), c_void_p, c_size_t, c_int, c_void_p]
     lib.mz_forward_view.restype = c_int
+    lib.mz_metrics_workspace_bytes.argtypes = [c_int, c_int, c_int, c_int, POINTER(c_size_t)]
+    lib.mz_metrics_workspace_bytes.restype = c_int
+    lib.mz_metrics.argtypes = [POINTER(MzImageView), POINTER(MzImageView), c_int, c_int, c_int, c_int, c_int, c_double, c_double,
+                               c_void_p, c_void_p, c_size_t, c_void_p]
+    lib.mz_metrics.restype = c_int
     lib.mz_padded_channels.argtypes = [c_int]
     lib.mz_op_conv.argtypes = [c_int, c_int, c_void_p, c_void_p, c_void_p, c_float, c_void_p] + [c_int] * 8 + [c_void_p]
     lib.mz_op_conv_film.argtypes = [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p] + [c_int] * 6 + [c_void_p]
@@ -120,6 +129,25 @@ def dtype_code(torch_dtype) -> int:
 
 def make_config(cfg: dict) -> MzConfig:
     return MzConfig(**{k: int(cfg[k]) for k, _ in MzConfig._fields_})
+
+
+def metrics_workspace_bytes(B: int, H: int, W: int, which: int) -> int:
+    out = c_size_t()
+    check(lib().mz_metrics_workspace_bytes(B, H, W, which, byref(out)))
+    return int(out.value)
+
+
+def metrics(pred_ptr, pred_strides, target_ptr, target_strides, elem, B, H, W, which, data_range, sigma_n_sq, out_ptr, ws_ptr, ws_bytes,
+            stream) -> None:
+    """mz_metrics: the two views as for Handle.forward_view; `elem` 0..2 = MZ_F32 / MZ_BF16 / MZ_F16, 3 = uint8."""
+    pv = MzImageView(c_void_p(pred_ptr), (c_int64 * 4)(*[int(v) for v in pred_strides]))
+    tv = MzImageView(c_void_p(target_ptr), (c_int64 * 4)(*[int(v) for v in target_strides]))
+    check(
+        lib().mz_metrics(
+            byref(pv), byref(tv), int(elem), B, H, W, int(which), float(data_range), float(sigma_n_sq), c_void_p(out_ptr),
+            c_void_p(ws_ptr), ws_bytes, c_void_p(stream),
+        )
+    )
 
 
 class Handle:

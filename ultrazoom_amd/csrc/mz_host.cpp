@@ -18,6 +18,7 @@
 
 #include "../../include/mewzoom_hip.h"
 #include "mz_geo.h"
+#include "mz_metrics.h"
 #include "mz_pack.h"
 
 using namespace mz;
@@ -1426,6 +1427,64 @@ extern "C" int mz_op_final(int dtype, const void* feat, const void* img, const f
     k.img = img; k.R = R; k.clamp = clamp;
     op.run.conv3(k);
     return op.finish();
+}
+
+// ------------------------------------------------------------------------------------------------
+// image-quality metrics (mz_metrics.h): no reference counterpart in model.py; stands in for torchmetrics as the reference's
+// pretrain.py:209-211, 301-329 uses it.  Stateless like the mz_op_* entries.
+// ------------------------------------------------------------------------------------------------
+static int check_metrics_shape(int B, int H, int W, int which) {
+    if (which <= 0 || (which & ~(MET_PSNR | MET_SSIM | MET_VIF)))
+        return fail(MZ_ERR_INVALID_ARGUMENT, "which must be a non-empty combination of 1 (PSNR), 2 (SSIM), 4 (VIF), got %d", which);
+    if (B < 1 || H < 1 || W < 1) return fail(MZ_ERR_INVALID_ARGUMENT, "need B, H, W >= 1 (got %d, %d, %d)", B, H, W);
+    if (B > 65535 || H > (1 << 28) || W > (1 << 28))
+        return fail(MZ_ERR_INVALID_ARGUMENT, "at most 65535 images of at most 2^28 pixels a side (got %d, %d, %d)", B, H, W);
+    if ((which & MET_SSIM) && (H < 11 || W < 11))
+        return fail(MZ_ERR_INVALID_ARGUMENT, "SSIM needs images of at least 11 x 11 pixels, got %d x %d", H, W);
+    if ((which & MET_VIF) && (H < 41 || W < 41))
+        return fail(MZ_ERR_INVALID_ARGUMENT, "VIF needs images of at least 41 x 41 pixels, got %d x %d", H, W);
+    return MZ_OK;
+}
+
+extern "C" int mz_metrics_workspace_bytes(int B, int H, int W, int which, size_t* bytes) {
+    if (!bytes) return fail(MZ_ERR_INVALID_ARGUMENT, "null argument");
+    if (int rc = check_metrics_shape(B, H, W, which)) return rc;
+    *bytes = metrics_plan(B, H, W, which).total;
+    return MZ_OK;
+}
+
+extern "C" int mz_metrics(const mz_image_view* pred, const mz_image_view* target, int elem, int B, int H, int W, int which,
+                          double data_range, double sigma_n_sq, double* out_dev, void* workspace, size_t workspace_bytes,
+                          void* hip_stream) {
+    if (!pred || !target) return fail(MZ_ERR_INVALID_ARGUMENT, "null image view");
+    if (!pred->data || !target->data) return fail(MZ_ERR_INVALID_ARGUMENT, "an image view has null data");
+    if (elem < 0 || elem > 3) return fail(MZ_ERR_INVALID_ARGUMENT, "elem must be 0 (f32), 1 (bf16), 2 (f16) or 3 (uint8), got %d", elem);
+    if (int rc = check_metrics_shape(B, H, W, which)) return rc;
+    if (!out_dev) return fail(MZ_ERR_INVALID_ARGUMENT, "null out_dev");
+    MetricsArgs a = {};
+    a.plan = metrics_plan(B, H, W, which);
+    if (!workspace || workspace_bytes < a.plan.total)
+        return fail(MZ_ERR_WORKSPACE_TOO_SMALL, "workspace too small: %zu bytes given, %zu needed", workspace ? workspace_bytes : (size_t)0,
+                    a.plan.total);
+    if (int rc = ensure_device_ready()) return rc;
+    a.pred.data = pred->data;
+    a.target.data = target->data;
+    for (int i = 0; i < 4; ++i) {
+        a.pred.s[i] = pred->stride[i];
+        a.target.s[i] = target->stride[i];
+    }
+    a.elem = elem;
+    a.B = B;
+    a.H = H;
+    a.W = W;
+    a.which = which;
+    a.data_range = data_range;
+    a.sigma_n_sq = sigma_n_sq;
+    a.out = out_dev;
+    a.ws = (char*)workspace;
+    const hipError_t e = launch_metrics(a, (hipStream_t)hip_stream);
+    if (e != hipSuccess) return fail(MZ_ERR_HIP, "metrics launch: %s", hipGetErrorString(e));
+    return MZ_OK;
 }
 
 // ------------------------------------------------------------------------------------------------

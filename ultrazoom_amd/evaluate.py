@@ -11,8 +11,9 @@ The reference takes both metrics from `torchmetrics` (absent from this image), w
     `sigma_n_sq = 2.0`, four scales with Gaussian windows of 17, 9, 5, 3 taps (sigma = taps / 5), "valid" filtering, the
     coarser scales low-pass filtered and decimated by two; per channel, mean over channels, mean over images.  Images
     must be at least 41 pixels in both directions.
-The arithmetic is plain torch and runs wherever the tensors live; it is the evaluation harness, not part of the
-kernel path.  torchmetrics is absent from this image: the three metrics are checked against independent numpy / scipy
+The arithmetic here is plain torch and runs wherever the tensors live; it is the evaluation harness, not part of the
+kernel path, and the float64 checker of the HIP kernels that compute the same metrics (`ultrazoom_amd/metrics.py`,
+`evaluate(..., backend="hip")`).  torchmetrics is absent from this image: the three metrics are checked against independent numpy / scipy
 computations of the same published definitions ("parity unpinned" for the metrics themselves)."""
 
 from __future__ import annotations
@@ -162,10 +163,23 @@ class VIF:
 
 
 @torch.inference_mode()
-def evaluate(model, pairs: Iterable[Tuple[Tensor, Tensor]]) -> dict:
+def evaluate(model, pairs: Iterable[Tuple[Tensor, Tensor]], backend: str = "torch") -> dict:
     """`pairs` yields (low-resolution input, high-resolution target) batches already on the model's device/dtype;
     returns {"psnr": ..., "ssim": ..., "vif": ..., "images": n} as the reference's test loop accumulates them (pretrain.py:301-329;
-    "vif" is None when the images are smaller than the 41 x 41 pixels the metric needs)."""
+    "vif" is None when the images are smaller than the 41 x 41 pixels the metric needs).  `backend="torch"`: the functions above,
+    wherever the tensors live; `backend="hip"`: the same metrics from the library's kernels (`ultrazoom_amd.metrics`, CUDA tensors
+    only), accumulated on the device and read once at the end."""
+    if backend not in ("torch", "hip"):
+        raise ValueError(f"backend is 'torch' or 'hip', got {backend!r}")
+    if backend == "hip":
+        from .metrics import MetricsAccumulator
+
+        acc = MetricsAccumulator(1.0)
+        n = 0
+        for x, y in pairs:
+            acc.update(model.upscale(x), y)
+            n += x.shape[0]
+        return {**acc.compute(), "images": n}
     psnr, ssim, vif = PSNR(1.0), SSIM(), VIF()
     n = 0
     for x, y in pairs:
