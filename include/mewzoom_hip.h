@@ -92,7 +92,14 @@ int mz_weights_complete(const mz_handle* h);
 
 /* Bytes of scratch HBM a call with this batch/shape needs.  The library processes the batch in
  * micro-batches of at most `max_images_in_flight` images (0 = library default), so memory does
- * not grow beyond that. */
+ * not grow beyond that.
+ *
+ * What a call touches (mz_forward, mz_forward_u8, mz_forward_view, mz_metrics and the mz_op_* entries alike): it READS only its
+ * input tensors -- the elements its shape and strides name, never a byte next to them -- and the workspace bytes it has itself
+ * written during that call; it WRITES only its outputs (of a view: the elements of the window) and its workspace, never an input.
+ * The workspace needs no initialisation and carries nothing from one call to the next: whatever it holds, NaN patterns included,
+ * the results have the same bits.  mz_metrics writes the `out` slots of the metrics `which` selects and leaves the others alone.
+ * tests/test_poison_ops_gpu.py, tests/test_poison_forward_gpu.py and tests/test_metrics_gpu.py hold every entry to this. */
 int mz_workspace_bytes(const mz_handle* h, int B, int H, int W, int max_images_in_flight, size_t* bytes);
 
 /* x        [B,3,H,W]      input, handle dtype

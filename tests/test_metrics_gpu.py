@@ -317,3 +317,50 @@ def test_refusals_leave_the_library_usable():
     got = image_metrics(p, t)
     assert_close(got["ssim"], want["ssim"], 1e-9, "ssim")
     assert_close(got["vif"], want["vif"], 1e-9, "vif")
+
+
+# ---- nothing outside the images is read, nothing outside out and the workspace written (tests/poison_util.py) ------------------------
+@pytest.mark.parametrize("dt", ["bf16", "f32"])
+@pytest.mark.parametrize("shape", [(2 * TILE_H + 1 + 10, 2 * TILE_W + 1 + 10), (42, 57)], ids=lambda s: f"{s[0]}x{s[1]}")
+def test_a_crop_inside_a_nan_frame_gives_the_bits_of_a_dense_copy(shape, dt):
+    """The `crop` view again, the pair inside a larger tensor of NaN instead of 0.77: a halo that reaches over the image's edge, at
+    the tile edges of the SSIM map and at the smallest VIF sizes, turns a sum into NaN."""
+    B, (H, W) = 2, shape
+    p, t = (v.cuda() for v in pair(B, H, W, 0.3, dt))
+    dense = raw_of(p, t)
+    assert not bool(torch.isnan(dense).any()) and dense[:, 6].abs().min() > 0 and dense[:, 11].abs().min() > 0
+
+    def framed(x):
+        big = torch.full((B, 3, H + 7, W + 9), float("nan"), device="cuda").to(x.dtype)
+        big[:, :, 3:3 + H, 5:5 + W] = x
+        return big, big[:, :, 3:3 + H, 5:5 + W]
+
+    (keep_p, pv), (keep_t, tv) = framed(p), framed(t)
+    assert torch.equal(raw_of(pv, tv), dense)
+    assert torch.equal(raw_of(pv, t), dense) and torch.equal(raw_of(p, tv), dense)
+
+
+@pytest.mark.parametrize("which", [7, 3, 4])
+def test_a_poisoned_workspace_and_the_slots_that_are_not_asked_for(which):
+    """The workspace starts as 0xFF bytes (NaN as float64) between pattern guards, the images sit between NaN guards: the same bits as
+    on a fresh workspace, no guard touched, and the `out` slots of the metrics that `which` leaves out keep what they held."""
+    from poison_util import Arena
+
+    B, H, W = 2, 45, 52
+    p, t = (v.cuda() for v in pair(B, H, W, 0.3, "bf16"))
+    dense = raw_of(p, t, which=which)
+    written = sorted(([0, 1, 2, 3, 4, 5] if which & 1 else []) + ([0, 1, 2, 3, 4, 5, 6, 7, 14] if which & 2 else [])
+                     + ([8, 9, 10, 11, 12, 13] if which & 4 else []))  # (SSIM of data_range=None takes the batch's range from the PSNR pass)
+    written = sorted(set(written))
+    kept = [s for s in range(_ffi.MZ_METRIC_SLOTS) if s not in written]
+    need = _ffi.metrics_workspace_bytes(B, H, W, which)
+    arena = Arena("cuda")
+    pa, ta = arena.input(p, name="pred"), arena.input(t, name="target")
+    out = arena.output((B, _ffi.MZ_METRIC_SLOTS), torch.float64, fill=-1.0, name="out")
+    ws = arena.raw(need, 0xFF, name="workspace")
+    _ffi.metrics(pa.data_ptr(), pa.stride(), ta.data_ptr(), ta.stride(), 1, B, H, W, which, -1.0, 2.0, out.data_ptr(), ws.data_ptr(), need,
+                 torch.cuda.current_stream().cuda_stream)
+    arena.check()
+    assert not bool(torch.isnan(out).any()), out
+    assert torch.equal(out[:, written], dense[:, written]), (out, dense)
+    assert bool((out[:, kept] == -1.0).all()), f"slots {kept} are not {which}'s to write: {out}"
