@@ -94,7 +94,7 @@ int mz_weights_complete(const mz_handle* h);
  * micro-batches of at most `max_images_in_flight` images (0 = library default), so memory does
  * not grow beyond that.
  *
- * What a call touches (mz_forward, mz_forward_u8, mz_forward_view, mz_metrics and the mz_op_* entries alike): it READS only its
+ * What a call touches (mz_forward, mz_forward_u8, mz_forward_view, mz_metrics, mz_resize and the mz_op_* entries alike): it READS only its
  * input tensors -- the elements its shape and strides name, never a byte next to them -- and the workspace bytes it has itself
  * written during that call; it WRITES only its outputs (of a view: the elements of the window) and its workspace, never an input.
  * The workspace needs no initialisation and carries nothing from one call to the next: whatever it holds, NaN patterns included,
@@ -214,6 +214,43 @@ int mz_metrics_workspace_bytes(int B, int H, int W, int which, size_t* bytes);
  * the device, as torchmetrics' data_range=None.  sigma_n_sq (VIF): the reference's default is 2.0. */
 int mz_metrics(const mz_image_view* pred, const mz_image_view* target, int elem, int B, int H, int W, int which,
                double data_range, double sigma_n_sq, double* out_dev, void* workspace, size_t workspace_bytes, void* hip_stream);
+
+/* ---- antialiased resampling to any size: no reference counterpart in `model.py`; stands in for torchvision's antialiased `Resize`
+ *      as the reference's `data.py:91-108` uses it (HR -> LR for validation), and serves "a 3X or a true-4K result from a 4X model"
+ *      (ultrazoom_amd/model.py: MewZoom.upscale_to) -------------------------------------------------------------------------------
+ * Stateless like mz_metrics (no handle): the call enqueues on the given stream and never synchronises, allocates nothing and copies
+ * nothing from the host -- its tap tables are built on the device, in the workspace.  x is a VIEW of [B,3,Hin,Win], out a view of the
+ * window {y0, x0, h, w} of the [B,3,Hout,Wout] result, or of all of it when window is NULL (mz_image_view and the window as for
+ * mz_forward_view: out->data receives result pixel (y0, x0); the window changes where results are stored, never what is computed).  Both
+ * views have one element type; a uint8 value v is read as v / 255 and stored as clamp -> * 255 + 0.5 -> truncate, exactly as
+ * mz_forward_u8; clamp != 0 clamps the other types to [0, 1] before the store (bicubic overshoots).  The touch contract of the
+ * workspace paragraph above holds: the call reads only the elements of x that the window's outputs need, writes only the window's
+ * elements and its workspace, and a workspace full of NaN patterns gives the same bits.
+ *
+ * The arithmetic is torch.nn.functional.interpolate(..., mode = "bicubic" | "bilinear", antialias=True, align_corners=False).  Per
+ * axis, n_in samples to n_out:   scale = n_in / n_out (double, from the two sizes);   support = interp / 2 * max(scale, 1);
+ * inv = 1 / max(scale, 1);   center = scale (i + 0.5);   first = max((int)(center - support + 0.5), 0);
+ * count = min((int)(center + support + 0.5), n_in) - first;   w_j = f((j + first - center + 0.5) inv) / sum_j f(..), in double;
+ * out[i] = sum_j w_j in[first + j].   f: bicubic with A = -0.5 (interp 4; torch's antialiased kernels use the PIL constant, not the
+ * -0.75 of the model's skip) or the triangle 1 - |u| (interp 2).  Horizontal pass, then vertical pass; both ACCUMULATE IN FLOAT64 with
+ * fma in ascending j from the double weights; the intermediate between them is float32, never the storage type.  An axis with
+ * n_out == n_in has the table {0, 1, 0, 0}: finite values pass through it exactly.  Dense and strided views give the same bits, two
+ * calls give the same bits (no atomics), and an image does not depend on the batch it is resized in.
+ *
+ * Return MZ_ERR_INVALID_ARGUMENT, before anything touches the GPU, for: a null view or null data; elem outside 0..3; a filter outside
+ * {0, 1}; B or any size < 1; B > 65535; n_in / n_out > 16 on either axis (bounds count at 66; enlarging is not bounded); a window that
+ * is empty or not inside the result; an output view whose channel, row or column stride is 0, or whose image stride is 0 when B > 1.
+ * MZ_ERR_WORKSPACE_TOO_SMALL as elsewhere. */
+#define MZ_RESIZE_BICUBIC 0
+#define MZ_RESIZE_BILINEAR 1
+/* Host only. */
+int mz_resize_workspace_bytes(int Hin, int Win, int Hout, int Wout, int filter, size_t* bytes);
+/* elem: 0..2 = mz_dtype, 3 = uint8. */
+int mz_resize(const mz_image_view* x, const mz_image_view* out, int elem, int B, int Hin, int Win, int Hout, int Wout,
+              int filter, int clamp, const int32_t window[4], void* workspace, size_t workspace_bytes, void* hip_stream);
+/* Host only (no GPU): the table of output index i of one axis, from the source the device compiles too: returns count (<= cap), *first,
+ * w[0..count) in double; negative on bad arguments (count > cap among them).  No reference counterpart. */
+int mz_debug_resize_taps(int n_in, int n_out, int filter, int i, int* first, double* w, int cap);
 
 /* ---- introspection ------------------------------------------------------------------------ */
 const char* mz_last_error(void);

@@ -22,6 +22,8 @@ MZ_ERR_WORKSPACE_TOO_SMALL = -5
 
 MZ_METRIC_SLOTS = 16  # doubles per image of mz_metrics' output (include/mewzoom_hip.h documents the slots)
 MZ_METRIC_PSNR, MZ_METRIC_SSIM, MZ_METRIC_VIF = 1, 2, 4
+MZ_RESIZE_BICUBIC, MZ_RESIZE_BILINEAR = 0, 1
+MZ_RESIZE_MAX_TAPS = 66  # taps of one output at the largest accepted ratio (n_in / n_out = 16, bicubic)
 
 
 class MzConfig(Structure):
@@ -75,6 +77,13 @@ def _declare(lib) -> None:
     lib.mz_metrics.argtypes = [POINTER(MzImageView), POINTER(MzImageView), c_int, c_int, c_int, c_int, c_int, c_double, c_double,
                                c_void_p, c_void_p, c_size_t, c_void_p]
     lib.mz_metrics.restype = c_int
+    lib.mz_resize_workspace_bytes.argtypes = [c_int, c_int, c_int, c_int, c_int, POINTER(c_size_t)]
+    lib.mz_resize_workspace_bytes.restype = c_int
+    lib.mz_resize.argtypes = [POINTER(MzImageView), POINTER(MzImageView), c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                              POINTER(c_int32), c_void_p, c_size_t, c_void_p]
+    lib.mz_resize.restype = c_int
+    lib.mz_debug_resize_taps.argtypes = [c_int, c_int, c_int, c_int, POINTER(c_int), POINTER(c_double), c_int]
+    lib.mz_debug_resize_taps.restype = c_int
     lib.mz_padded_channels.argtypes = [c_int]
     lib.mz_op_conv.argtypes = [c_int, c_int, c_void_p, c_void_p, c_void_p, c_float, c_void_p] + [c_int] * 8 + [c_void_p]
     lib.mz_op_conv_film.argtypes = [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p] + [c_int] * 6 + [c_void_p]
@@ -148,6 +157,36 @@ def metrics(pred_ptr, pred_strides, target_ptr, target_strides, elem, B, H, W, w
             c_void_p(ws_ptr), ws_bytes, c_void_p(stream),
         )
     )
+
+
+def resize_workspace_bytes(Hin: int, Win: int, Hout: int, Wout: int, filter_: int) -> int:
+    out = c_size_t()
+    check(lib().mz_resize_workspace_bytes(Hin, Win, Hout, Wout, int(filter_), byref(out)))
+    return int(out.value)
+
+
+def resize(x_ptr, x_strides, out_ptr, out_strides, elem, B, Hin, Win, Hout, Wout, filter_, clamp, window, ws_ptr, ws_bytes, stream) -> None:
+    """mz_resize: the two views as for Handle.forward_view (out: of the window); `elem` 0..2 = MZ_F32 / MZ_BF16 / MZ_F16, 3 = uint8;
+    `window` = (y0, x0, h, w) in pixels of the Hout x Wout result, or None."""
+    xv = MzImageView(c_void_p(x_ptr), (c_int64 * 4)(*[int(v) for v in x_strides]))
+    ov = MzImageView(c_void_p(out_ptr), (c_int64 * 4)(*[int(v) for v in out_strides]))
+    win = (c_int32 * 4)(*[int(v) for v in window]) if window is not None else None
+    check(
+        lib().mz_resize(
+            byref(xv), byref(ov), int(elem), B, Hin, Win, Hout, Wout, int(filter_), int(bool(clamp)), win, c_void_p(ws_ptr), ws_bytes,
+            c_void_p(stream),
+        )
+    )
+
+
+def resize_taps(n_in: int, n_out: int, filter_: int, i: int):
+    """mz_debug_resize_taps (host only): (first, [w_0 .. w_{count-1}]) of output index i of one axis."""
+    first = c_int()
+    w = (c_double * MZ_RESIZE_MAX_TAPS)()
+    count = lib().mz_debug_resize_taps(n_in, n_out, int(filter_), i, byref(first), w, MZ_RESIZE_MAX_TAPS)
+    if count < 0:
+        check(count)
+    return int(first.value), [float(w[j]) for j in range(count)]
 
 
 class Handle:

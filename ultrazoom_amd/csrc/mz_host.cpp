@@ -20,6 +20,7 @@
 #include "mz_geo.h"
 #include "mz_metrics.h"
 #include "mz_pack.h"
+#include "mz_resize.h"
 
 using namespace mz;
 
@@ -1485,6 +1486,79 @@ extern "C" int mz_metrics(const mz_image_view* pred, const mz_image_view* target
     const hipError_t e = launch_metrics(a, (hipStream_t)hip_stream);
     if (e != hipSuccess) return fail(MZ_ERR_HIP, "metrics launch: %s", hipGetErrorString(e));
     return MZ_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// antialiased resampling to any size (mz_resize.h): no reference counterpart in model.py; stands in for torchvision's Resize as the
+// reference's data.py:91-108 uses it.  Stateless like mz_metrics.  Every check comes before anything touches the GPU.
+// ------------------------------------------------------------------------------------------------
+static int check_resize_shape(int Hin, int Win, int Hout, int Wout, int filter) {
+    if (filter != RF_BICUBIC && filter != RF_BILINEAR)
+        return fail(MZ_ERR_INVALID_ARGUMENT, "filter must be 0 (bicubic) or 1 (bilinear), got %d", filter);
+    if (Hin < 1 || Win < 1 || Hout < 1 || Wout < 1)
+        return fail(MZ_ERR_INVALID_ARGUMENT, "need sizes >= 1 (got %d x %d -> %d x %d)", Hin, Win, Hout, Wout);
+    if (Hin > (1 << 28) || Win > (1 << 28) || Hout > (1 << 28) || Wout > (1 << 28))
+        return fail(MZ_ERR_INVALID_ARGUMENT, "at most 2^28 pixels a side (got %d x %d -> %d x %d)", Hin, Win, Hout, Wout);
+    if ((long long)Hin > (long long)kResizeMaxRatio * Hout || (long long)Win > (long long)kResizeMaxRatio * Wout)
+        return fail(MZ_ERR_INVALID_ARGUMENT, "%d x %d -> %d x %d shrinks an axis by more than %d", Hin, Win, Hout, Wout, kResizeMaxRatio);
+    return MZ_OK;
+}
+
+extern "C" int mz_resize_workspace_bytes(int Hin, int Win, int Hout, int Wout, int filter, size_t* bytes) {
+    if (!bytes) return fail(MZ_ERR_INVALID_ARGUMENT, "null argument");
+    if (int rc = check_resize_shape(Hin, Win, Hout, Wout, filter)) return rc;
+    *bytes = resize_plan(Hin, Win, Hout, Wout, filter).total;
+    return MZ_OK;
+}
+
+extern "C" int mz_resize(const mz_image_view* x, const mz_image_view* out, int elem, int B, int Hin, int Win, int Hout, int Wout, int filter,
+                         int clamp, const int32_t window[4], void* workspace, size_t workspace_bytes, void* hip_stream) {
+    if (!x || !out) return fail(MZ_ERR_INVALID_ARGUMENT, "null image view");
+    if (!x->data || !out->data) return fail(MZ_ERR_INVALID_ARGUMENT, "an image view has null data");
+    if (elem < 0 || elem > 3) return fail(MZ_ERR_INVALID_ARGUMENT, "elem must be 0 (f32), 1 (bf16), 2 (f16) or 3 (uint8), got %d", elem);
+    if (B < 1 || B > 65535) return fail(MZ_ERR_INVALID_ARGUMENT, "need 1 <= B <= 65535 (got %d)", B);
+    if (int rc = check_resize_shape(Hin, Win, Hout, Wout, filter)) return rc;
+    ResizeArgs a = {};
+    a.y0 = 0; a.x0 = 0; a.h = Hout; a.w = Wout;
+    if (window) {
+        a.y0 = window[0]; a.x0 = window[1]; a.h = window[2]; a.w = window[3];
+        if (a.h <= 0 || a.w <= 0) return fail(MZ_ERR_INVALID_ARGUMENT, "empty window (%d x %d)", a.h, a.w);
+        if (a.y0 < 0 || a.x0 < 0 || (long long)a.y0 + a.h > Hout || (long long)a.x0 + a.w > Wout)
+            return fail(MZ_ERR_INVALID_ARGUMENT, "window {%d, %d, %d, %d} is not inside the %d x %d output", a.y0, a.x0, a.h, a.w, Hout, Wout);
+    }
+    static const char* const dim[4] = {"image", "channel", "row", "column"};
+    for (int i = 0; i < 4; ++i) {
+        a.x.s[i] = x->stride[i];
+        a.out.s[i] = out->stride[i];
+        if (out->stride[i] == 0 && (i > 0 || B > 1))
+            return fail(MZ_ERR_INVALID_ARGUMENT, "the output view's %s stride is 0: its elements would overlap", dim[i]);
+    }
+    a.plan = resize_plan(Hin, Win, Hout, Wout, filter);
+    if (!workspace || workspace_bytes < a.plan.total)
+        return fail(MZ_ERR_WORKSPACE_TOO_SMALL, "workspace too small: %zu bytes given, %zu needed", workspace ? workspace_bytes : (size_t)0,
+                    a.plan.total);
+    if (int rc = ensure_device_ready()) return rc;
+    a.x.data = x->data;
+    a.out.data = out->data;
+    a.elem = elem;
+    a.B = B;
+    a.Hin = Hin; a.Win = Win; a.Hout = Hout; a.Wout = Wout;
+    a.filter = filter;
+    a.clamp = clamp != 0;
+    a.ws = (char*)workspace;
+    const hipError_t e = launch_resize(a, (hipStream_t)hip_stream);
+    if (e != hipSuccess) return fail(MZ_ERR_HIP, "resize launch: %s", hipGetErrorString(e));
+    return MZ_OK;
+}
+
+// Host only: resize_taps() (mz_resize.h) of one output index, the source the device's table kernel compiles too
+extern "C" int mz_debug_resize_taps(int n_in, int n_out, int filter, int i, int* first, double* w, int cap) {
+    if (!first || !w || cap < 0) return fail(MZ_ERR_INVALID_ARGUMENT, "null argument or negative cap");
+    if (int rc = check_resize_shape(n_in, 1, n_out, 1, filter)) return rc;
+    if (i < 0 || i >= n_out) return fail(MZ_ERR_INVALID_ARGUMENT, "output index %d is not in [0, %d)", i, n_out);
+    const int count = resize_taps(n_in, n_out, filter, i, first, cap, [&](int j, double v) { w[j] = v; });
+    if (count > cap) return fail(MZ_ERR_INVALID_ARGUMENT, "output %d has %d taps, room for %d", i, count, cap);
+    return count;
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -190,3 +190,36 @@ def evaluate(model, pairs: Iterable[Tuple[Tensor, Tensor]], backend: str = "torc
             vif.update(sr, y)
         n += x.shape[0]
     return {"psnr": psnr.compute(), "ssim": ssim.compute(), "vif": vif.compute() if vif.n else None, "images": n}
+
+
+_INTERP_MODES = ("bicubic", "bilinear")
+
+
+@torch.inference_mode()
+def lr_from_hr(hr: Tensor, ratio: int, filter: str = "bicubic", backend: str = "torch") -> Tuple[Tensor, Tensor]:
+    """The low-resolution input of a high-resolution batch, as the reference derives it (data.py:91-108: an antialiased `Resize`,
+    BICUBIC or BILINEAR; pretrain.py:301-329 validates on such pairs): `hr` [B, C, H, W] is cropped at the top-left to multiples of
+    `ratio` (a view, nothing is copied) and resized by 1 / ratio.  Returns (lr, hr_cropped).  `backend="torch"`:
+    `F.interpolate(..., antialias=True)` wherever the tensor lives (uint8 is not taken); `backend="hip"`: the library's kernel
+    (`ultrazoom_amd.resize`, CUDA tensors only), which reads the cropped view in place.  The rest of the reference's degradation chain
+    (blur, noise, JPEG: transforms.py) is not part of this."""
+    if backend not in ("torch", "hip"):
+        raise ValueError(f"backend is 'torch' or 'hip', got {backend!r}")
+    if filter not in _INTERP_MODES:
+        raise ValueError(f"filter is 'bicubic' or 'bilinear', got {filter!r}")
+    ratio = int(ratio)
+    if hr.dim() != 4 or ratio < 1 or hr.shape[-2] < ratio or hr.shape[-1] < ratio:
+        raise ValueError(f"expected a [B, C, H, W] tensor of at least {ratio} x {ratio} pixels, got {tuple(hr.shape)}")
+    h, w = hr.shape[-2] // ratio, hr.shape[-1] // ratio
+    hr = hr[..., : h * ratio, : w * ratio]
+    if backend == "hip":
+        from .resize import resize
+
+        return resize(hr, (h, w), filter=filter), hr
+    return F.interpolate(hr, size=(h, w), mode=filter, antialias=True, align_corners=False), hr
+
+
+def evaluate_hr(model, hr_batches: Iterable[Tensor], *, filter: str = "bicubic", backend: str = "torch") -> dict:
+    """`evaluate` on high-resolution batches alone: each is turned into its (LR, HR) pair by `lr_from_hr` at the model's ratio.  With
+    `backend="hip"` the chain HR -> LR -> upscale -> metrics stays on the device and is read once, at the end."""
+    return evaluate(model, (lr_from_hr(hr, model.upscale_ratio, filter, backend) for hr in hr_batches), backend)

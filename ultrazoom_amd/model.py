@@ -367,6 +367,42 @@ class MewZoom(nn.Module, PyTorchModelHubMixin):
         engine.run_view(x, out, window, True, False, self.max_images_in_flight)
         return out
 
+    @torch.inference_mode()
+    def upscale_to(self, x: Tensor, size: Tuple[int, int], out: Optional[Tensor] = None, filter: str = "bicubic") -> Tensor:
+        """``upscale(x)`` resampled to ``size`` = (Hout, Wout): ``resize(self.upscale(x), size, filter=filter, clamp=True)``
+        (``ultrazoom_amd.resize``: the antialiased bicubic / bilinear of ``F.interpolate(..., antialias=True)`` as a HIP kernel), bit
+        for bit, with the one ``rH x rW`` intermediate and nothing else materialised.  A 4X model serves ``size=(3H, 3W)`` or
+        ``(2H, 2W)`` this way -- "4X model + resample", which is not a 3X model.  ``size == (rH, rW)`` is ``upscale(x)`` itself: no
+        resample, the same bits.  No reference counterpart (model.py has no resampler; data.py:91-108 resizes with torchvision).
+
+        uint8 input goes through ``upscale_uint8``: the intermediate is rounded to uint8 and the resampled result is rounded again,
+        exactly as saving the upscaled image and resizing the file would.  ``out`` ([B, 3, Hout, Wout], any strides, x's dtype) receives
+        the result in place."""
+        if x.dim() != 4 or x.shape[1] != 3:
+            raise RuntimeError(f"expected a (B, 3, H, W) tensor, got {tuple(x.shape)}")
+        p0 = next(self.parameters())
+        if x.dtype != torch.uint8 and x.dtype != p0.dtype:
+            raise RuntimeError(f"Input type ({x.dtype}) and weight type ({p0.dtype}) should be the same")
+        if not x.is_cuda:
+            raise RuntimeError("ultrazoom_amd.MewZoom computes on an MI355X only: move the model and the input to a 'cuda' device. "
+                               "There is no CPU path.")
+        from .resize import resize
+
+        size = tuple(int(v) for v in size)
+        if len(size) != 2 or min(size) < 1:
+            raise ValueError(f"size is (Hout, Wout) with both at least 1, got {size}")
+        B, _, H, W = x.shape
+        r = self.upscale_ratio
+        if out is not None and (tuple(out.shape) != (B, 3) + size or out.dtype != x.dtype or out.device != x.device):
+            raise RuntimeError(f"out should be a {(B, 3) + size} {x.dtype} tensor on {x.device}, got {tuple(out.shape)} {out.dtype} "
+                               f"on {out.device}")
+        if size == (r * H, r * W):
+            if out is not None:
+                return self.upscale_into(x, out)
+            return self.upscale_uint8(x) if x.dtype == torch.uint8 else self.upscale(x)
+        sr = self.upscale_uint8(x) if x.dtype == torch.uint8 else self.upscale(x)
+        return resize(sr, size, filter=filter, clamp=True, out=out)
+
     # ---- checkpoint ingestion (test_compare.py:32-45 of the reference) -------------------------
     def load_training_checkpoint(self, state_dict: Dict[str, Tensor], lora_alpha: Optional[float] = None) -> None:
         """Loads a raw training checkpoint: strips ``_orig_mod.`` prefixes left by torch.compile, bakes weight-norm

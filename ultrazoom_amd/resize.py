@@ -1,0 +1,73 @@
+"""Antialiased resampling of image batches to any size on the MI355X: `mz_resize` (include/mewzoom_hip.h) behind a tensor interface.
+
+The arithmetic is that of torch's `interpolate(x, size, mode="bicubic" | "bilinear", antialias=True)` (align_corners=False;
+its float64 CPU result is the checker of the kernel), in HIP, on the tensors as they lie in memory: any strides (channels-last, an HWC
+frame permuted to NCHW, a crop, every second image), float32 / bfloat16 / float16 / uint8 (a uint8 value v means v / 255 and is stored
+as clamp -> * 255 + 0.5 -> truncate, as `MewZoom.upscale_uint8` does).  Both passes accumulate in float64; the intermediate between them is float32.  Nothing is copied and
+nothing here synchronises with the host."""
+
+from __future__ import annotations
+
+from typing import Optional, Tuple
+
+import torch
+from torch import Tensor
+
+from . import _ffi
+
+_FILTERS = {"bicubic": _ffi.MZ_RESIZE_BICUBIC, "bilinear": _ffi.MZ_RESIZE_BILINEAR}
+_ELEM = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2, torch.uint8: 3}
+MAX_RATIO = 16  # an axis shrinks at most this much in one call (include/mewzoom_hip.h)
+
+
+def resize(x: Tensor, size: Tuple[int, int], *, filter: str = "bicubic", clamp: bool = False, out: Optional[Tensor] = None,
+           window: Optional[Tuple[int, int, int, int]] = None) -> Tensor:
+    """A logical [B, 3, H, W] CUDA tensor resampled to `size` = (Hout, Wout); returns a new dense NCHW tensor of x's dtype, or `out`.
+
+    `clamp` clamps floating-point results to [0, 1] (bicubic overshoots; uint8 results are always clamped).  `window` = (y0, x0, h, w) in
+    pixels of the Hout x Wout result selects the part that is computed and stored, `out` ([B, 3, h, w], or [B, 3, Hout, Wout] without a
+    window; any strides, x's dtype) receives it in place: a window of a result equals that part of the whole result bit for bit.  An
+    axis may shrink by at most 16; enlarging is not bounded.  x and out must not overlap."""
+    if filter not in _FILTERS:
+        raise ValueError(f"filter is 'bicubic' or 'bilinear', got {filter!r}")
+    if x.dim() != 4 or x.shape[1] != 3:
+        raise ValueError(f"expected a [B, 3, H, W] tensor, got {tuple(x.shape)}")
+    if x.dtype not in _ELEM:
+        raise TypeError(f"unsupported dtype {x.dtype}; use float32, bfloat16, float16 or uint8")
+    if not x.is_cuda:
+        raise RuntimeError("ultrazoom_amd.resize computes on an MI355X only: move the image to a 'cuda' device. There is no CPU path.")
+    size = tuple(int(v) for v in size)
+    if len(size) != 2 or min(size) < 1:
+        raise ValueError(f"size is (Hout, Wout) with both at least 1, got {size}")
+    B, _, H, W = x.shape
+    if B < 1 or H < 1 or W < 1:
+        raise ValueError(f"an empty batch or image: {tuple(x.shape)}")
+    Hout, Wout = size
+    if H > MAX_RATIO * Hout or W > MAX_RATIO * Wout:
+        raise ValueError(f"{(H, W)} -> {size} shrinks an axis by more than {MAX_RATIO}: resize in two steps")
+    if window is None:
+        want = (B, 3, Hout, Wout)
+    else:
+        window = tuple(int(v) for v in window)
+        if len(window) != 4:
+            raise ValueError("window is (y0, x0, h, w) in output pixels")
+        y0, x0, h, w = window
+        if h < 1 or w < 1 or y0 < 0 or x0 < 0 or y0 + h > Hout or x0 + w > Wout:
+            raise ValueError(f"window {window} is empty or not inside the {Hout} x {Wout} result")
+        want = (B, 3, h, w)
+    if out is not None:
+        if out.device != x.device:
+            raise RuntimeError(f"the input is on {x.device} but the output is on {out.device}")
+        if out.dtype != x.dtype:
+            raise TypeError(f"x ({x.dtype}) and out ({out.dtype}) should have the same dtype")
+        if tuple(out.shape) != want:
+            raise ValueError(f"the output has shape {tuple(out.shape)}, expected {want}")
+    with torch.cuda.device(x.device):
+        stream = torch.cuda.current_stream(x.device)
+        need = _ffi.resize_workspace_bytes(H, W, Hout, Wout, _FILTERS[filter])
+        ws = torch.empty(need, dtype=torch.uint8, device=x.device)
+        if out is None:
+            out = torch.empty(want, dtype=x.dtype, device=x.device)
+        _ffi.resize(x.data_ptr(), x.stride(), out.data_ptr(), out.stride(), _ELEM[x.dtype], B, H, W, Hout, Wout, _FILTERS[filter], clamp,
+                    window, ws.data_ptr(), need, stream.cuda_stream)
+    return out
