@@ -94,7 +94,7 @@ int mz_weights_complete(const mz_handle* h);
  * micro-batches of at most `max_images_in_flight` images (0 = library default), so memory does
  * not grow beyond that.
  *
- * What a call touches (mz_forward, mz_forward_u8, mz_forward_view, mz_metrics, mz_resize and the mz_op_* entries alike): it READS only its
+ * What a call touches (mz_forward, mz_forward_u8, mz_forward_view, mz_metrics, mz_resize, mz_blur, mz_noise, mz_jpeg and the mz_op_* entries alike): it READS only its
  * input tensors -- the elements its shape and strides name, never a byte next to them -- and the workspace bytes it has itself
  * written during that call; it WRITES only its outputs (of a view: the elements of the window) and its workspace, never an input.
  * The workspace needs no initialisation and carries nothing from one call to the next: whatever it holds, NaN patterns included,
@@ -251,6 +251,43 @@ int mz_resize(const mz_image_view* x, const mz_image_view* out, int elem, int B,
 /* Host only (no GPU): the table of output index i of one axis, from the source the device compiles too: returns count (<= cap), *first,
  * w[0..count) in double; negative on bad arguments (count > cap among them).  No reference counterpart. */
 int mz_debug_resize_taps(int n_in, int n_out, int filter, int i, int* first, double* w, int cap);
+
+/* ---- the degradation chain: no reference counterpart in `model.py`; stands in for torchvision's `gaussian_blur`, `gaussian_noise`
+ *      and `jpeg` as the reference's `transforms.py` calls them (data.py:134-164: blur -> noise -> resize -> JPEG makes the LR input of
+ *      an HR image; the three parameters are the quality head's target) ---------------------------------------------------------------
+ * Stateless like mz_resize: each call enqueues on the given stream, never synchronises and allocates nothing.  x and out are VIEWS of
+ * one logical shape [B,3,H,W] and one element type (elem 0..2 = mz_dtype, 3 = uint8: v means v / 255, stored as clamp -> * 255 + 0.5 ->
+ * truncate).  Parameters are scalars of the call: per-image parameters are one call per image, on a view of that image.  Dense and
+ * strided views give the same bits; the touch contract of the workspace paragraph above holds.  ultrazoom_amd/csrc/mz_degrade.h states
+ * the arithmetic in full; in short:
+ *
+ * mz_blur   k = 2 * int(3 sigma) + 1 taps (transforms.py:39), w_j = exp(-0.5 (j / sigma)^2) / sum in double, separable, reflect
+ *           padding, both passes accumulated in float64 in ascending j, float32 between them.  sigma < 1 / 3 copies.
+ * mz_noise  out = clamp(x + sigma n, 0, 1), n from the library's own stream: Philox4x32-10 keyed by `seed`, counter = (element index
+ *           (c H + y) W + x, stream id offset + b), Box-Muller on the first two words in float64.  The noise of a pixel depends on
+ *           neither layout nor strides nor how a batch is split into calls (pass offset + b for image b).  out may be the SAME view as
+ *           x (in place); any other overlap is refused.
+ * mz_jpeg   a baseline JPEG round trip at `quality` 1..100, 4:2:0, modelled in arithmetic (no entropy coder, which is lossless):
+ *           8-bit RGB -> YCbCr -> 2 x 2 chroma means -> 8 x 8 DCT-II (float64) -> Annex K tables scaled by the quality -> rounding ->
+ *           inverse DCT -> triangle chroma upsampling -> RGB.  The workspace holds the decoded planes (1.5 bytes a padded pixel).
+ *
+ * Return MZ_ERR_INVALID_ARGUMENT, before anything touches the GPU, for: a null view or null data; elem outside 0..3; B, H or W < 1;
+ * B > 65535; an output view whose channel, row or column stride is 0, or whose image stride is 0 when B > 1; x and out whose byte
+ * ranges overlap (mz_noise: unless they are the same view); mz_blur: sigma negative or not finite, int(3 sigma) > 15, or
+ * int(3 sigma) >= min(H, W), where reflect padding is undefined; mz_noise: sigma negative or not finite; mz_jpeg: quality outside
+ * 1..100.  MZ_ERR_WORKSPACE_TOO_SMALL as elsewhere. */
+int mz_blur(const mz_image_view* x, const mz_image_view* out, int elem, int B, int H, int W, double sigma, void* hip_stream);
+int mz_noise(const mz_image_view* x, const mz_image_view* out, int elem, int B, int H, int W, double sigma, uint64_t seed,
+             uint64_t offset, void* hip_stream);
+/* Host only. */
+int mz_jpeg_workspace_bytes(int B, int H, int W, size_t* bytes);
+int mz_jpeg(const mz_image_view* x, const mz_image_view* out, int elem, int B, int H, int W, int quality, void* workspace,
+            size_t workspace_bytes, void* hip_stream);
+/* Host only (no GPU), from the source the kernels are built from: the k weights of a sigma (returns k <= cap); the two quantisation
+ * tables of a quality, row-major [64] each; one Philox4x32-10 block.  No reference counterpart. */
+int mz_debug_blur_weights(double sigma, double* w, int cap);
+int mz_debug_jpeg_qtable(int quality, uint8_t* luma, uint8_t* chroma);
+int mz_debug_philox(const uint32_t counter[4], const uint32_t key[2], uint32_t out[4]);
 
 /* ---- introspection ------------------------------------------------------------------------ */
 const char* mz_last_error(void);

@@ -7,7 +7,7 @@ here="$(cd "$(dirname "$0")/../ultrazoom_amd/csrc" && pwd)"
 mkdir -p "$here/build"
 # the -D flags reach the host file too: it reads the kernels' LDS geometry (mz_kernels.h: MZ_GEMM1_S)
 /opt/rocm/bin/hipcc -O2 -std=c++17 -fPIC "$@" -c "$here/mz_host.cpp" -o "$here/build/mz_host_$tag.o"
-units=(mz_kernels mz_conv32 mz_conv3s mz_mix16 mz_conv3r mz_conv3t mz_metrics mz_resize mz_probe)
+units=(mz_kernels mz_conv32 mz_conv3s mz_mix16 mz_conv3r mz_conv3t mz_metrics mz_resize mz_degrade mz_probe)
 pids=()
 for u in "${units[@]}"; do
     /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC "$@" -c "$here/$u.hip" -o "$here/build/${u}_$tag.o" &

@@ -7,6 +7,7 @@
 All arithmetic runs in hand-written gfx950 kernels behind the C ABI in include/mewzoom_hip.h.
 """
 
+from .degrade import Degradation, gaussian_blur, gaussian_noise, jpeg  # noqa: F401
 from .model import MewZoom, bake_state_dict  # noqa: F401
 
-__all__ = ["MewZoom", "bake_state_dict"]
+__all__ = ["MewZoom", "bake_state_dict", "Degradation", "gaussian_blur", "gaussian_noise", "jpeg"]

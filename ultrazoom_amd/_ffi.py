@@ -9,7 +9,7 @@ from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import POINTER, Structure, byref, c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_size_t, c_void_p
+from ctypes import POINTER, Structure, byref, c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_size_t, c_uint8, c_uint32, c_uint64, c_void_p
 from pathlib import Path
 
 LIB_NAME = "libmewzoom_hip.so"
@@ -84,6 +84,20 @@ def _declare(lib) -> None:
     lib.mz_resize.restype = c_int
     lib.mz_debug_resize_taps.argtypes = [c_int, c_int, c_int, c_int, POINTER(c_int), POINTER(c_double), c_int]
     lib.mz_debug_resize_taps.restype = c_int
+    lib.mz_blur.argtypes = [POINTER(MzImageView), POINTER(MzImageView), c_int, c_int, c_int, c_int, c_double, c_void_p]
+    lib.mz_blur.restype = c_int
+    lib.mz_noise.argtypes = [POINTER(MzImageView), POINTER(MzImageView), c_int, c_int, c_int, c_int, c_double, c_uint64, c_uint64, c_void_p]
+    lib.mz_noise.restype = c_int
+    lib.mz_jpeg_workspace_bytes.argtypes = [c_int, c_int, c_int, POINTER(c_size_t)]
+    lib.mz_jpeg_workspace_bytes.restype = c_int
+    lib.mz_jpeg.argtypes = [POINTER(MzImageView), POINTER(MzImageView), c_int, c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p]
+    lib.mz_jpeg.restype = c_int
+    lib.mz_debug_blur_weights.argtypes = [c_double, POINTER(c_double), c_int]
+    lib.mz_debug_blur_weights.restype = c_int
+    lib.mz_debug_jpeg_qtable.argtypes = [c_int, POINTER(c_uint8), POINTER(c_uint8)]
+    lib.mz_debug_jpeg_qtable.restype = c_int
+    lib.mz_debug_philox.argtypes = [POINTER(c_uint32), POINTER(c_uint32), POINTER(c_uint32)]
+    lib.mz_debug_philox.restype = c_int
     lib.mz_padded_channels.argtypes = [c_int]
     lib.mz_op_conv.argtypes = [c_int, c_int, c_void_p, c_void_p, c_void_p, c_float, c_void_p] + [c_int] * 8 + [c_void_p]
     lib.mz_op_conv_film.argtypes = [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p] + [c_int] * 6 + [c_void_p]
@@ -187,6 +201,59 @@ def resize_taps(n_in: int, n_out: int, filter_: int, i: int):
     if count < 0:
         check(count)
     return int(first.value), [float(w[j]) for j in range(count)]
+
+
+def _views(x_ptr, x_strides, out_ptr, out_strides):
+    return (MzImageView(c_void_p(x_ptr), (c_int64 * 4)(*[int(v) for v in x_strides])),
+            MzImageView(c_void_p(out_ptr), (c_int64 * 4)(*[int(v) for v in out_strides])))
+
+
+def blur(x_ptr, x_strides, out_ptr, out_strides, elem, B, H, W, sigma, stream) -> None:
+    """mz_blur: the two views as for `resize`; `elem` 0..2 = MZ_F32 / MZ_BF16 / MZ_F16, 3 = uint8."""
+    xv, ov = _views(x_ptr, x_strides, out_ptr, out_strides)
+    check(lib().mz_blur(byref(xv), byref(ov), int(elem), B, H, W, float(sigma), c_void_p(stream)))
+
+
+def noise(x_ptr, x_strides, out_ptr, out_strides, elem, B, H, W, sigma, seed, offset, stream) -> None:
+    """mz_noise: `seed` and `offset` are taken modulo 2^64; out may be the same view as x."""
+    xv, ov = _views(x_ptr, x_strides, out_ptr, out_strides)
+    check(lib().mz_noise(byref(xv), byref(ov), int(elem), B, H, W, float(sigma), int(seed) & (2**64 - 1), int(offset) & (2**64 - 1),
+                         c_void_p(stream)))
+
+
+def jpeg_workspace_bytes(B: int, H: int, W: int) -> int:
+    out = c_size_t()
+    check(lib().mz_jpeg_workspace_bytes(B, H, W, byref(out)))
+    return int(out.value)
+
+
+def jpeg(x_ptr, x_strides, out_ptr, out_strides, elem, B, H, W, quality, ws_ptr, ws_bytes, stream) -> None:
+    """mz_jpeg: the round trip at `quality` 1..100 on a workspace of `jpeg_workspace_bytes(B, H, W)` bytes."""
+    xv, ov = _views(x_ptr, x_strides, out_ptr, out_strides)
+    check(lib().mz_jpeg(byref(xv), byref(ov), int(elem), B, H, W, int(quality), c_void_p(ws_ptr), ws_bytes, c_void_p(stream)))
+
+
+def blur_weights(sigma: float):
+    """mz_debug_blur_weights (host only): the k = 2 * int(3 sigma) + 1 normalised weights the kernel is handed."""
+    w = (c_double * 31)()
+    k = lib().mz_debug_blur_weights(float(sigma), w, 31)
+    if k < 0:
+        check(k)
+    return [float(w[j]) for j in range(k)]
+
+
+def jpeg_qtable(quality: int):
+    """mz_debug_jpeg_qtable (host only): (luminance, chrominance), 64 integers each, row-major."""
+    a, b = (c_uint8 * 64)(), (c_uint8 * 64)()
+    check(lib().mz_debug_jpeg_qtable(int(quality), a, b))
+    return list(a), list(b)
+
+
+def philox(counter, key):
+    """mz_debug_philox (host only): the four words of one Philox4x32-10 block, from the function the noise kernel compiles."""
+    out = (c_uint32 * 4)()
+    check(lib().mz_debug_philox((c_uint32 * 4)(*counter), (c_uint32 * 2)(*key), out))
+    return [int(v) for v in out]
 
 
 class Handle:

@@ -7,7 +7,7 @@ HIPCC="${HIPCC:-/opt/rocm/bin/hipcc}"
 mkdir -p "$here/build"
 # one compile per translation unit, in parallel; every PID is waited for on its own so that the FIRST broken unit fails the build
 # with its own compiler output (a bare `wait` returns 0 whatever the children did, and the failure surfaced only at link time)
-units=(mz_kernels mz_conv32 mz_conv3s mz_mix16 mz_conv3r mz_conv3t mz_metrics mz_resize mz_probe)
+units=(mz_kernels mz_conv32 mz_conv3s mz_mix16 mz_conv3r mz_conv3t mz_metrics mz_resize mz_degrade mz_probe)
 pids=()
 for u in "${units[@]}"; do
     "$HIPCC" --offload-arch=gfx950 -O3 -std=c++17 -fPIC -c "$here/$u.hip" -o "$here/build/$u.o" &

@@ -1,0 +1,70 @@
+// gfx950 (MI355X / CDNA4): the degradation family (mz_degrade.h) -- instantiations and the launchers of mz_blur(), mz_noise(), mz_jpeg().
+#define MZ_DEGRADE_KERNELS
+#include "mz_degrade.h"
+
+namespace mz {
+
+template <int E> static hipError_t launch_blur_e(const DegradeArgs& a, const BlurWeights& bw, hipStream_t s) {
+    const int tiles_x = (a.W + kBlurTile - 1) / kBlurTile, tiles_y = (a.H + kBlurTile - 1) / kBlurTile;
+    const long long tiles = (long long)tiles_x * tiles_y;
+    const long long wgs = tiles * 3 * a.B;
+    if (wgs <= 0 || wgs > 0x7fffffffLL) return hipErrorInvalidValue;
+    hipLaunchKernelGGL((blur_kernel<E>), dim3((unsigned)wgs), dim3(kDegradeThreads), 0, s, a.x, a.out, a.H, a.W, tiles, tiles_x, bw);
+    return hipGetLastError();
+}
+
+template <int E> static hipError_t launch_noise_e(const DegradeArgs& a, double sigma, unsigned long long seed, unsigned long long offset, hipStream_t s) {
+    const long long chunks = (3LL * a.H * a.W + kDegradeThreads - 1) / kDegradeThreads;
+    const long long wgs = chunks * a.B;
+    if (wgs <= 0 || wgs > 0x7fffffffLL) return hipErrorInvalidValue;
+    hipLaunchKernelGGL((noise_kernel<E>), dim3((unsigned)wgs), dim3(kDegradeThreads), 0, s, a.x, a.out, a.H, a.W, chunks, sigma, seed, offset);
+    return hipGetLastError();
+}
+
+template <int E> static hipError_t launch_jpeg_e(const DegradeArgs& a, const JpegTables& t, const JpegPlan& pl, char* ws, hipStream_t s) {
+    uint8_t* ws_y = (uint8_t*)(ws + pl.off_y);
+    uint8_t* ws_c = (uint8_t*)(ws + pl.off_c);
+    const int tiles_x = (pl.Wp / 16 + kJpegMcus - 1) / kJpegMcus;
+    const long long tiles = (long long)tiles_x * (pl.Hp / 16);
+    const long long chunks = ((long long)a.H * a.W + kDegradeThreads - 1) / kDegradeThreads;
+    if (tiles * a.B <= 0 || tiles * a.B > 0x7fffffffLL || chunks * a.B > 0x7fffffffLL) return hipErrorInvalidValue;
+    hipLaunchKernelGGL((jpeg_code_kernel<E>), dim3((unsigned)(tiles * a.B)), dim3(kDegradeThreads), 0, s, a.x, a.H, a.W, pl.Hp, pl.Wp, tiles, tiles_x, t,
+                       ws_y, ws_c);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL((jpeg_image_kernel<E>), dim3((unsigned)(chunks * a.B)), dim3(kDegradeThreads), 0, s, a.out, a.H, a.W, pl.Hp, pl.Wp, chunks,
+                       (const uint8_t*)ws_y, (const uint8_t*)ws_c);
+    return hipGetLastError();
+}
+
+hipError_t launch_blur(const DegradeArgs& a, const BlurWeights& bw, hipStream_t s) {
+    switch (a.elem) {
+        case RE_F32: return launch_blur_e<RE_F32>(a, bw, s);
+        case RE_BF16: return launch_blur_e<RE_BF16>(a, bw, s);
+        case RE_F16: return launch_blur_e<RE_F16>(a, bw, s);
+        case RE_U8: return launch_blur_e<RE_U8>(a, bw, s);
+        default: return hipErrorInvalidValue;
+    }
+}
+
+hipError_t launch_noise(const DegradeArgs& a, double sigma, unsigned long long seed, unsigned long long offset, hipStream_t s) {
+    switch (a.elem) {
+        case RE_F32: return launch_noise_e<RE_F32>(a, sigma, seed, offset, s);
+        case RE_BF16: return launch_noise_e<RE_BF16>(a, sigma, seed, offset, s);
+        case RE_F16: return launch_noise_e<RE_F16>(a, sigma, seed, offset, s);
+        case RE_U8: return launch_noise_e<RE_U8>(a, sigma, seed, offset, s);
+        default: return hipErrorInvalidValue;
+    }
+}
+
+hipError_t launch_jpeg(const DegradeArgs& a, const JpegTables& t, const JpegPlan& plan, char* ws, hipStream_t s) {
+    switch (a.elem) {
+        case RE_F32: return launch_jpeg_e<RE_F32>(a, t, plan, ws, s);
+        case RE_BF16: return launch_jpeg_e<RE_BF16>(a, t, plan, ws, s);
+        case RE_F16: return launch_jpeg_e<RE_F16>(a, t, plan, ws, s);
+        case RE_U8: return launch_jpeg_e<RE_U8>(a, t, plan, ws, s);
+        default: return hipErrorInvalidValue;
+    }
+}
+
+}  // namespace mz

@@ -21,6 +21,7 @@
 #include "mz_metrics.h"
 #include "mz_pack.h"
 #include "mz_resize.h"
+#include "mz_degrade.h"
 
 using namespace mz;
 
@@ -1559,6 +1560,126 @@ extern "C" int mz_debug_resize_taps(int n_in, int n_out, int filter, int i, int*
     const int count = resize_taps(n_in, n_out, filter, i, first, cap, [&](int j, double v) { w[j] = v; });
     if (count > cap) return fail(MZ_ERR_INVALID_ARGUMENT, "output %d has %d taps, room for %d", i, count, cap);
     return count;
+}
+
+// ------------------------------------------------------------------------------------------------
+// the degradation chain (mz_degrade.h): no reference counterpart in model.py; stands in for torchvision's gaussian_blur, gaussian_noise
+// and jpeg as the reference's transforms.py uses them.  Stateless like mz_resize.  Every check comes before anything touches the GPU.
+// ------------------------------------------------------------------------------------------------
+// the byte range [lo, hi) the elements of a [B,3,H,W] view lie in
+static void view_extent(const mz_image_view* v, int elem, int B, int H, int W, long long* lo, long long* hi) {
+    const long long es = elem == RE_F32 ? 4 : elem == RE_U8 ? 1 : 2;
+    const long long n[4] = {B, 3, H, W};
+    long long a = 0, b = 0;
+    for (int i = 0; i < 4; ++i) {
+        const long long span = (n[i] - 1) * (long long)v->stride[i];
+        if (span < 0) a += span; else b += span;
+    }
+    *lo = (long long)(intptr_t)v->data + a * es;
+    *hi = (long long)(intptr_t)v->data + (b + 1) * es;
+}
+
+static int check_degrade_views(const mz_image_view* x, const mz_image_view* out, int elem, int B, int H, int W, int in_place_ok, DegradeArgs* a) {
+    if (!x || !out) return fail(MZ_ERR_INVALID_ARGUMENT, "null image view");
+    if (!x->data || !out->data) return fail(MZ_ERR_INVALID_ARGUMENT, "an image view has null data");
+    if (elem < 0 || elem > 3) return fail(MZ_ERR_INVALID_ARGUMENT, "elem must be 0 (f32), 1 (bf16), 2 (f16) or 3 (uint8), got %d", elem);
+    if (B < 1 || B > 65535) return fail(MZ_ERR_INVALID_ARGUMENT, "need 1 <= B <= 65535 (got %d)", B);
+    if (H < 1 || W < 1) return fail(MZ_ERR_INVALID_ARGUMENT, "need H, W >= 1 (got %d x %d)", H, W);
+    if (H > (1 << 28) || W > (1 << 28)) return fail(MZ_ERR_INVALID_ARGUMENT, "at most 2^28 pixels a side (got %d x %d)", H, W);
+    static const char* const dim[4] = {"image", "channel", "row", "column"};
+    for (int i = 0; i < 4; ++i) {
+        a->x.s[i] = x->stride[i];
+        a->out.s[i] = out->stride[i];
+        if (out->stride[i] == 0 && (i > 0 || B > 1))
+            return fail(MZ_ERR_INVALID_ARGUMENT, "the output view's %s stride is 0: its elements would overlap", dim[i]);
+    }
+    const bool same = x->data == out->data && x->stride[0] == out->stride[0] && x->stride[1] == out->stride[1] &&
+                      x->stride[2] == out->stride[2] && x->stride[3] == out->stride[3];
+    if (!(same && in_place_ok)) {
+        long long xl, xh, ol, oh;
+        view_extent(x, elem, B, H, W, &xl, &xh);
+        view_extent(out, elem, B, H, W, &ol, &oh);
+        if (xl < oh && ol < xh)
+            return fail(MZ_ERR_INVALID_ARGUMENT, in_place_ok ? "x and out overlap without being the same view" : "x and out overlap: this entry does not work in place");
+    }
+    a->x.data = x->data;
+    a->out.data = out->data;
+    a->elem = elem;
+    a->B = B;
+    a->H = H;
+    a->W = W;
+    return MZ_OK;
+}
+
+extern "C" int mz_blur(const mz_image_view* x, const mz_image_view* out, int elem, int B, int H, int W, double sigma, void* hip_stream) {
+    DegradeArgs a = {};
+    if (int rc = check_degrade_views(x, out, elem, B, H, W, 0, &a)) return rc;
+    BlurWeights bw = {};
+    const int half = blur_weights(sigma, &bw);
+    if (half < 0) return fail(MZ_ERR_INVALID_ARGUMENT, "sigma %g: need 0 <= sigma and int(3 sigma) <= %d", sigma, kBlurMaxHalf);
+    if (half >= (H < W ? H : W))
+        return fail(MZ_ERR_INVALID_ARGUMENT, "sigma %g needs %d pixels of reflect padding, a %d x %d image has no such reflection", sigma, half, H, W);
+    if (int rc = ensure_device_ready()) return rc;
+    const hipError_t e = launch_blur(a, bw, (hipStream_t)hip_stream);
+    if (e != hipSuccess) return fail(MZ_ERR_HIP, "blur launch: %s", hipGetErrorString(e));
+    return MZ_OK;
+}
+
+extern "C" int mz_noise(const mz_image_view* x, const mz_image_view* out, int elem, int B, int H, int W, double sigma, uint64_t seed,
+                        uint64_t offset, void* hip_stream) {
+    DegradeArgs a = {};
+    if (int rc = check_degrade_views(x, out, elem, B, H, W, 1, &a)) return rc;
+    if (!(sigma >= 0.0) || !(sigma <= 1e6)) return fail(MZ_ERR_INVALID_ARGUMENT, "sigma %g: need 0 <= sigma <= 1e6", sigma);
+    if (int rc = ensure_device_ready()) return rc;
+    const hipError_t e = launch_noise(a, sigma, seed, offset, (hipStream_t)hip_stream);
+    if (e != hipSuccess) return fail(MZ_ERR_HIP, "noise launch: %s", hipGetErrorString(e));
+    return MZ_OK;
+}
+
+extern "C" int mz_jpeg_workspace_bytes(int B, int H, int W, size_t* bytes) {
+    if (!bytes) return fail(MZ_ERR_INVALID_ARGUMENT, "null argument");
+    if (B < 1 || B > 65535 || H < 1 || W < 1 || H > (1 << 28) || W > (1 << 28))
+        return fail(MZ_ERR_INVALID_ARGUMENT, "need 1 <= B <= 65535 and 1 <= H, W <= 2^28 (got %d, %d, %d)", B, H, W);
+    *bytes = jpeg_plan(B, H, W).total;
+    return MZ_OK;
+}
+
+extern "C" int mz_jpeg(const mz_image_view* x, const mz_image_view* out, int elem, int B, int H, int W, int quality, void* workspace,
+                       size_t workspace_bytes, void* hip_stream) {
+    DegradeArgs a = {};
+    if (int rc = check_degrade_views(x, out, elem, B, H, W, 0, &a)) return rc;
+    if (quality < 1 || quality > 100) return fail(MZ_ERR_INVALID_ARGUMENT, "quality must be 1..100, got %d", quality);
+    const JpegPlan plan = jpeg_plan(B, H, W);
+    if (!workspace || workspace_bytes < plan.total)
+        return fail(MZ_ERR_WORKSPACE_TOO_SMALL, "workspace too small: %zu bytes given, %zu needed", workspace ? workspace_bytes : (size_t)0, plan.total);
+    JpegTables t;
+    jpeg_qtable(quality, &t);
+    if (int rc = ensure_device_ready()) return rc;
+    const hipError_t e = launch_jpeg(a, t, plan, (char*)workspace, (hipStream_t)hip_stream);
+    if (e != hipSuccess) return fail(MZ_ERR_HIP, "jpeg launch: %s", hipGetErrorString(e));
+    return MZ_OK;
+}
+
+// Host only: what the kernels are handed and compile -- the blur weights of a sigma, the quantisation tables of a quality, one Philox block
+extern "C" int mz_debug_blur_weights(double sigma, double* w, int cap) {
+    BlurWeights bw = {};
+    const int half = blur_weights(sigma, &bw);
+    if (!w || half < 0 || 2 * half + 1 > cap) return fail(MZ_ERR_INVALID_ARGUMENT, "null argument, a bad sigma (%g) or room for fewer than k weights", sigma);
+    for (int j = 0; j <= 2 * half; ++j) w[j] = bw.w[j];
+    return 2 * half + 1;
+}
+extern "C" int mz_debug_jpeg_qtable(int quality, uint8_t* luma, uint8_t* chroma) {
+    if (!luma || !chroma || quality < 1 || quality > 100) return fail(MZ_ERR_INVALID_ARGUMENT, "null argument or quality %d outside 1..100", quality);
+    JpegTables t;
+    jpeg_qtable(quality, &t);
+    memcpy(luma, t.q[0], 64);
+    memcpy(chroma, t.q[1], 64);
+    return MZ_OK;
+}
+extern "C" int mz_debug_philox(const uint32_t counter[4], const uint32_t key[2], uint32_t out[4]) {
+    if (!counter || !key || !out) return fail(MZ_ERR_INVALID_ARGUMENT, "null argument");
+    philox4x32_10(counter[0], counter[1], counter[2], counter[3], key[0], key[1], out);
+    return MZ_OK;
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -202,7 +202,7 @@ def lr_from_hr(hr: Tensor, ratio: int, filter: str = "bicubic", backend: str = "
     `ratio` (a view, nothing is copied) and resized by 1 / ratio.  Returns (lr, hr_cropped).  `backend="torch"`:
     `F.interpolate(..., antialias=True)` wherever the tensor lives (uint8 is not taken); `backend="hip"`: the library's kernel
     (`ultrazoom_amd.resize`, CUDA tensors only), which reads the cropped view in place.  The rest of the reference's degradation chain
-    (blur, noise, JPEG: transforms.py) is not part of this."""
+    (blur, noise, JPEG: transforms.py) is `ultrazoom_amd.degrade`: `Degradation.apply` runs this resize between them."""
     if backend not in ("torch", "hip"):
         raise ValueError(f"backend is 'torch' or 'hip', got {backend!r}")
     if filter not in _INTERP_MODES:
@@ -219,7 +219,37 @@ def lr_from_hr(hr: Tensor, ratio: int, filter: str = "bicubic", backend: str = "
     return F.interpolate(hr, size=(h, w), mode=filter, antialias=True, align_corners=False), hr
 
 
-def evaluate_hr(model, hr_batches: Iterable[Tensor], *, filter: str = "bicubic", backend: str = "torch") -> dict:
+def evaluate_hr(model, hr_batches: Iterable[Tensor], *, filter: str = "bicubic", backend: str = "torch", degrade=None) -> dict:
     """`evaluate` on high-resolution batches alone: each is turned into its (LR, HR) pair by `lr_from_hr` at the model's ratio.  With
-    `backend="hip"` the chain HR -> LR -> upscale -> metrics stays on the device and is read once, at the end."""
-    return evaluate(model, (lr_from_hr(hr, model.upscale_ratio, filter, backend) for hr in hr_batches), backend)
+    `backend="hip"` the chain HR -> LR -> upscale -> metrics stays on the device and is read once, at the end.
+
+    `degrade`: a `ultrazoom_amd.degrade.Degradation` (`backend="hip"` only; its own `filter` is used) validates under the reference's
+    blind-degradation recipe instead: the pairs come from `Degradation.apply` (blur -> noise -> resize -> JPEG, image n of the run
+    drawing parameters and noise n of the seed), the network runs once per batch for the clamped SR and the quality head's output,
+    and the result gains "deg_l2": the mean squared error of that output against the normalised parameters (pretrain.py:246-250),
+    accumulated on the device and read with the image metrics."""
+    if degrade is None:
+        return evaluate(model, (lr_from_hr(hr, model.upscale_ratio, filter, backend) for hr in hr_batches), backend)
+    if backend != "hip":
+        raise ValueError("degrade runs on the device only: use backend='hip'. There is no CPU path.")
+    return _evaluate_degraded(model, hr_batches, degrade)
+
+
+@torch.inference_mode()
+def _evaluate_degraded(model, hr_batches: Iterable[Tensor], degrade) -> dict:
+    from .metrics import MetricsAccumulator
+
+    acc = MetricsAccumulator(1.0)
+    sq, count, n = None, 0, 0
+    for hr in hr_batches:
+        lr, target, want = degrade.apply(hr, model.upscale_ratio, index=n)
+        sr, qa = model.forward(lr)
+        acc.update(sr.clamp(0, 1), target)
+        d = qa.double() - want.double()
+        sq = (d * d).sum() if sq is None else sq + (d * d).sum()
+        count += d.numel()
+        n += hr.shape[0]
+    if sq is None:
+        return {**acc.compute(), "deg_l2": float("nan"), "images": 0}
+    res, (total,) = acc.compute(extra=sq.reshape(1))  # the one read of the run
+    return {**res, "deg_l2": total / count, "images": n}

@@ -90,10 +90,15 @@ class MetricsAccumulator:
         self.ssim_n += pred.shape[0]
         self.vif_n += pred.shape[0] if with_vif else 0
 
-    def compute(self) -> dict:
+    def compute(self, extra: Optional[Tensor] = None):
+        """The metrics; with `extra` (a float64 device vector the caller accumulated next to them) `(metrics, extra values)`, both
+        from the same single read."""
         if self._sums is None:
-            return {"psnr": float("nan"), "ssim": float("nan"), "vif": None}
-        sq, n, ssim, vif = self._sums.tolist()  # the one read of the device values
+            res = {"psnr": float("nan"), "ssim": float("nan"), "vif": None}
+            return res if extra is None else (res, extra.tolist())
+        values = (self._sums if extra is None else torch.cat([self._sums, extra.to(self._sums.device, torch.float64)])).tolist()  # the one read
+        sq, n, ssim, vif = values[:4]
         mse = sq / n
         psnr = float("inf") if mse == 0.0 else 10.0 * math.log10(self.psnr_range**2 / mse)
-        return {"psnr": psnr, "ssim": ssim / self.ssim_n, "vif": vif / self.vif_n if self.vif_n else None}
+        res = {"psnr": psnr, "ssim": ssim / self.ssim_n, "vif": vif / self.vif_n if self.vif_n else None}
+        return res if extra is None else (res, values[4:])
