@@ -124,7 +124,15 @@ int mz_forward_u8(mz_handle* h, const uint8_t* x, uint8_t* out_sr, float* out_qa
  *
  * `data` is the address of element (image 0, channel 0, row 0, column 0) and needs the alignment of ONE element only; strides are
  * counted in ELEMENTS and may be negative.  The library reads and writes exactly the elements the view names.  Overlap between x
- * and out, or between elements of out, is the caller's responsibility and is not checked (beyond refusing an output stride of 0). */
+ * and out, or between elements of out, is the caller's responsibility and is not checked (beyond refusing an output stride of 0;
+ * mz_blur, mz_noise and mz_jpeg also compare the two byte ranges).
+ *
+ * THE VIEW REFUSALS.  Every entry that takes views (mz_forward_view, mz_metrics, mz_resize, mz_blur, mz_noise, mz_jpeg) returns
+ * MZ_ERR_INVALID_ARGUMENT, before anything touches the GPU, for: a null view or null data; an `elem` outside the entry's codes; a view
+ * that is WRITTEN whose channel, row or column stride is 0, or whose image stride is 0 when B > 1 (strides of a view that is only read
+ * may be 0, and any stride may be negative); where the entry takes a window: one that is empty or not inside the result.  Each entry
+ * below lists only what it refuses beyond these.  A workspace that is null or smaller than the entry's *_workspace_bytes is
+ * MZ_ERR_WORKSPACE_TOO_SMALL.  (ultrazoom_amd/csrc/mz_view_check.h is the one statement of these checks.) */
 typedef struct mz_image_view {
     void*   data;        /* element (image 0, channel 0, row 0, column 0) */
     int64_t stride[4];   /* in ELEMENTS, signed: image, channel, row, column */
@@ -136,9 +144,7 @@ typedef struct mz_image_view {
  *         output pixel (y0, x0); out spans h x w pixels.  The window changes where results are stored, never what is computed: a
  *         window of a result equals that part of the whole result bit for bit (tiling: the haloed slice as x, the core as window).
  * elem    0 = the handle's dtype, 1 = uint8 (scaling and rounding exactly as mz_forward_u8; clamp is implied).
- * Returns MZ_ERR_INVALID_ARGUMENT, before anything touches the GPU, for: a null view or null data; elem outside {0, 1}; a window
- * that is empty or not inside [0, rH) x [0, rW); an output view whose channel, row or column stride is 0, or whose image stride
- * is 0 when B > 1. */
+ * Refuses the view refusals above (elem outside {0, 1}; the window inside [0, rH) x [0, rW)), and a null handle, B < 1, H or W < 8. */
 int mz_forward_view(mz_handle* h, const mz_image_view* x, const mz_image_view* out, float* out_qa,
                     int B, int H, int W, int clamp, int elem, const int32_t window[4],
                     void* workspace, size_t workspace_bytes, int max_images_in_flight, void* hip_stream);
@@ -201,9 +207,8 @@ int mz_op_conv_film(int dtype, const void* in0, const float* w_dev_f32, const fl
  * slot (8 + c) / slot (11 + c) -- 0 / 0 stays NaN exactly where the torch restatement gives NaN.  Slots of metrics that were not
  * requested are left as they were.
  *
- * Return MZ_ERR_INVALID_ARGUMENT, before anything touches the GPU, for: a null view or null data; elem outside 0..3; which == 0 or
- * with unknown bits; B, H or W < 1 (or B > 65535); H or W < 11 with SSIM; H or W < 41 with VIF; a null out_dev.
- * MZ_ERR_WORKSPACE_TOO_SMALL as elsewhere. */
+ * Refuses the view refusals above (elem outside 0..3; both views are only read), and: which == 0 or with unknown bits; B, H or W < 1
+ * (or B > 65535, H or W > 2^28); H or W < 11 with SSIM; H or W < 41 with VIF; a null out_dev. */
 #define MZ_METRIC_SLOTS 16
 #define MZ_METRIC_PSNR 1
 #define MZ_METRIC_SSIM 2
@@ -237,10 +242,8 @@ int mz_metrics(const mz_image_view* pred, const mz_image_view* target, int elem,
  * n_out == n_in has the table {0, 1, 0, 0}: finite values pass through it exactly.  Dense and strided views give the same bits, two
  * calls give the same bits (no atomics), and an image does not depend on the batch it is resized in.
  *
- * Return MZ_ERR_INVALID_ARGUMENT, before anything touches the GPU, for: a null view or null data; elem outside 0..3; a filter outside
- * {0, 1}; B or any size < 1; B > 65535; n_in / n_out > 16 on either axis (bounds count at 66; enlarging is not bounded); a window that
- * is empty or not inside the result; an output view whose channel, row or column stride is 0, or whose image stride is 0 when B > 1.
- * MZ_ERR_WORKSPACE_TOO_SMALL as elsewhere. */
+ * Refuses the view refusals above (elem outside 0..3), and: a filter outside {0, 1}; B or any size < 1; B > 65535; a size > 2^28;
+ * n_in / n_out > 16 on either axis (bounds count at 66; enlarging is not bounded). */
 #define MZ_RESIZE_BICUBIC 0
 #define MZ_RESIZE_BILINEAR 1
 /* Host only. */
@@ -271,11 +274,10 @@ int mz_debug_resize_taps(int n_in, int n_out, int filter, int i, int* first, dou
  *           8-bit RGB -> YCbCr -> 2 x 2 chroma means -> 8 x 8 DCT-II (float64) -> Annex K tables scaled by the quality -> rounding ->
  *           inverse DCT -> triangle chroma upsampling -> RGB.  The workspace holds the decoded planes (1.5 bytes a padded pixel).
  *
- * Return MZ_ERR_INVALID_ARGUMENT, before anything touches the GPU, for: a null view or null data; elem outside 0..3; B, H or W < 1;
- * B > 65535; an output view whose channel, row or column stride is 0, or whose image stride is 0 when B > 1; x and out whose byte
- * ranges overlap (mz_noise: unless they are the same view); mz_blur: sigma negative or not finite, int(3 sigma) > 15, or
- * int(3 sigma) >= min(H, W), where reflect padding is undefined; mz_noise: sigma negative or not finite; mz_jpeg: quality outside
- * 1..100.  MZ_ERR_WORKSPACE_TOO_SMALL as elsewhere. */
+ * Refuse the view refusals above (elem outside 0..3), and: B, H or W < 1; B > 65535; H or W > 2^28; x and out whose byte ranges
+ * overlap (mz_noise: unless they are the same view) or do not fit in signed 64-bit addresses; mz_blur: sigma negative or not finite,
+ * int(3 sigma) > 15, or int(3 sigma) >= min(H, W), where reflect padding is undefined; mz_noise: sigma negative, not finite or
+ * > 1e6; mz_jpeg: quality outside 1..100. */
 int mz_blur(const mz_image_view* x, const mz_image_view* out, int elem, int B, int H, int W, double sigma, void* hip_stream);
 int mz_noise(const mz_image_view* x, const mz_image_view* out, int elem, int B, int H, int W, double sigma, uint64_t seed,
              uint64_t offset, void* hip_stream);

@@ -1,0 +1,128 @@
+// Host-only driver of ultrazoom_amd/csrc/mz_view_check.h: extreme strides, sizes, windows and addresses through check_views,
+// check_window, view_extent and check_overlap.  tests/test_view_checks_cpu.py compiles it with g++ -fsanitize=address,undefined
+// -fno-sanitize-recover=undefined and runs it: exit status 0 and no sanitizer report (a signed overflow in the checks would abort it).
+#include <limits.h>
+#include <stdint.h>
+#include <stdio.h>
+
+#include <initializer_list>
+
+#include "../ultrazoom_amd/csrc/mz_view_check.h"
+
+using namespace mz;
+
+static int g_failed = 0;
+#define EXPECT(cond)                                                \
+    do {                                                            \
+        if (!(cond)) {                                              \
+            printf("%s:%d: %s is false\n", __FILE__, __LINE__, #cond); \
+            ++g_failed;                                             \
+        }                                                           \
+    } while (0)
+
+static mz_image_view view(uintptr_t data, int64_t s0, int64_t s1, int64_t s2, int64_t s3) {
+    mz_image_view v;
+    v.data = (void*)data;
+    v.stride[0] = s0; v.stride[1] = s1; v.stride[2] = s2; v.stride[3] = s3;
+    return v;
+}
+
+static const ViewRules kOut = {3, MZ_ELEM_NAMES_0_3, true, true, true};     // as mz_blur / mz_noise / mz_jpeg
+static const ViewRules kBoth = {3, MZ_ELEM_NAMES_0_3, false, false, false};  // as mz_metrics
+
+int main() {
+    const int side = 1 << 28;
+    const int64_t extremes[] = {INT64_MAX, INT64_MIN, -1, 1, 0};
+    const uintptr_t addresses[] = {0x10000, (uintptr_t)INT64_MAX - 64, UINTPTR_MAX - 64};  // low, the sign change, the top
+    StridedView a, b;
+
+    // check_views: the strides are copied as they are, whatever they are; only an output stride of 0 is refused
+    for (int64_t s : extremes)
+        for (uintptr_t at : addresses) {
+            const mz_image_view x = view(at, s, s, s, s), dense = view(0x10000, 3LL * side * side, (int64_t)side * side, side, 1);
+            Refusal r = check_views(&x, &dense, kOut, 3, 65535, side, side, &a, &b);
+            EXPECT(r.code == MZ_OK && a.s[0] == s && a.s[3] == s && a.data == x.data && b.s[2] == side);
+            r = check_views(&dense, &x, kOut, 0, 65535, side, side, &a, &b);
+            EXPECT(r.code == (s == 0 ? MZ_ERR_INVALID_ARGUMENT : MZ_OK));
+            EXPECT((r.code == MZ_OK) == (r.msg[0] == 0));
+            r = check_views(&x, &x, kBoth, 3, INT_MAX, INT_MAX, INT_MIN, &a, &b);  // an entry that states its own bounds
+            EXPECT(r.code == MZ_OK);
+        }
+    {
+        const mz_image_view x = view(0x10000, 1, 1, 1, 1);
+        EXPECT(check_views(nullptr, &x, kOut, 0, 1, 1, 1, &a, &b).code == MZ_ERR_INVALID_ARGUMENT);
+        EXPECT(check_views(&x, nullptr, kOut, 0, 1, 1, 1, &a, &b).code == MZ_ERR_INVALID_ARGUMENT);
+        const mz_image_view null_data = view(0, 1, 1, 1, 1);
+        EXPECT(check_views(&null_data, &x, kOut, 0, 1, 1, 1, &a, &b).code == MZ_ERR_INVALID_ARGUMENT);
+        EXPECT(check_views(&x, &null_data, kOut, 0, 1, 1, 1, &a, &b).code == MZ_ERR_INVALID_ARGUMENT);
+        for (int elem : {INT_MIN, -1, 4, INT_MAX}) EXPECT(check_views(&x, &x, kOut, elem, 1, 1, 1, &a, &b).code == MZ_ERR_INVALID_ARGUMENT);
+        for (int batch : {INT_MIN, 0, 65536, INT_MAX}) EXPECT(check_views(&x, &x, kOut, 0, batch, 1, 1, &a, &b).code == MZ_ERR_INVALID_ARGUMENT);
+        for (int n : {INT_MIN, 0, side + 1, INT_MAX}) {
+            EXPECT(check_views(&x, &x, kOut, 0, 1, n, 1, &a, &b).code == MZ_ERR_INVALID_ARGUMENT);
+            EXPECT(check_views(&x, &x, kOut, 0, 1, 1, n, &a, &b).code == MZ_ERR_INVALID_ARGUMENT);
+        }
+        const mz_image_view one_image = view(0x10000, 0, 1, 1, 1);
+        EXPECT(check_views(&x, &one_image, kOut, 0, 1, 1, 1, &a, &b).code == MZ_OK);
+        EXPECT(check_views(&x, &one_image, kOut, 0, 2, 1, 1, &a, &b).code == MZ_ERR_INVALID_ARGUMENT);
+    }
+
+    // check_window
+    {
+        int y0, x0, h, w;
+        EXPECT(check_window(nullptr, INT_MAX, INT_MAX, &y0, &x0, &h, &w).code == MZ_OK && y0 == 0 && x0 == 0 && h == INT_MAX && w == INT_MAX);
+        const int32_t all[4] = {0, 0, INT32_MAX, INT32_MAX}, last[4] = {INT32_MAX - 1, INT32_MAX - 1, 1, 1};
+        EXPECT(check_window(all, INT_MAX, INT_MAX, &y0, &x0, &h, &w).code == MZ_OK && h == INT_MAX);
+        EXPECT(check_window(last, INT_MAX, INT_MAX, &y0, &x0, &h, &w).code == MZ_OK && y0 == INT_MAX - 1 && w == 1);
+        const int32_t bad[][4] = {{INT32_MAX, INT32_MAX, INT32_MAX, INT32_MAX}, {1, 0, INT32_MAX, 1}, {0, 1, 1, INT32_MAX}, {INT32_MAX, 0, 1, 1},
+                                  {INT32_MIN, 0, 1, 1}, {0, INT32_MIN, INT32_MAX, INT32_MAX}, {0, 0, INT32_MIN, 1}, {0, 0, 1, 0}, {-1, 0, 4, 4}};
+        for (const auto& win : bad) EXPECT(check_window(win, INT_MAX, INT_MAX, &y0, &x0, &h, &w).code == MZ_ERR_INVALID_ARGUMENT);
+        const int32_t past[4] = {5, 0, 4, 4};
+        EXPECT(check_window(past, 8, 8, &y0, &x0, &h, &w).code == MZ_ERR_INVALID_ARGUMENT);
+    }
+
+    // view_extent and check_overlap: whatever the strides and the address, a code and no overflow
+    for (int64_t s : extremes)
+        for (int64_t t : extremes)
+            for (uintptr_t at : addresses)
+                for (int elem = 0; elem < 4; ++elem) {
+                    const mz_image_view x = view(at, s, t, s, t), out = view(0x10000, t, s, 1, s);
+                    long long lo = 0, hi = 0;
+                    if (view_extent(&x, elem, 65535, side, side, &lo, &hi)) EXPECT(lo < hi);
+                    const int rc = check_overlap(&x, &out, elem, 65535, side, side, false).code;
+                    EXPECT(rc == MZ_OK || rc == MZ_ERR_INVALID_ARGUMENT);
+                    EXPECT(check_overlap(&x, &x, elem, 65535, side, side, true).code == MZ_OK);           // the same view, in place
+                    EXPECT(check_overlap(&x, &x, elem, 65535, side, side, false).code == MZ_ERR_INVALID_ARGUMENT);
+                }
+    {
+        long long lo, hi;
+        const mz_image_view huge = view(0x10000, INT64_MAX, INT64_MAX, INT64_MAX, INT64_MAX), tiny = view(0x10000, 1, 1, 1, 1);
+        EXPECT(!view_extent(&huge, 0, 65535, side, side, &lo, &hi));  // no range of 63-bit addresses: refused, not undefined
+        EXPECT(check_overlap(&huge, &tiny, 0, 65535, side, side, false).code == MZ_ERR_INVALID_ARGUMENT);
+        EXPECT(check_overlap(&tiny, &huge, 0, 65535, side, side, true).code == MZ_ERR_INVALID_ARGUMENT);
+        const mz_image_view top = view(UINTPTR_MAX - 4095, 3 * 16 * 16, 16 * 16, 16, 1);  // one 16 x 16 uint8 image under the top of the address space
+        EXPECT(view_extent(&top, 3, 1, 16, 16, &lo, &hi) && hi - lo == 3 * 16 * 16);
+        const mz_image_view bgr = view(0x10000 + 2 * 256 * 4, 768, -256, 16, 1);  // negative channel stride, data at channel 2
+        EXPECT(view_extent(&bgr, 0, 2, 16, 16, &lo, &hi) && lo == 0x10000 && hi == 0x10000 + 2 * 768 * 4);
+    }
+
+    // the ordinary cases: a 1080 x 1920 float32 frame
+    {
+        const int H = 1080, W = 1920;
+        const mz_image_view frame = view(0x100000, 3LL * H * W, (int64_t)H * W, W, 1);
+        EXPECT(check_overlap(&frame, &frame, 0, 2, H, W, true).code == MZ_OK);                        // mz_noise in place
+        EXPECT(check_overlap(&frame, &frame, 0, 2, H, W, false).code == MZ_ERR_INVALID_ARGUMENT);     // mz_blur in place
+        // two 256 x 256 crops of the frame, the second shifted by (8, 8): they share pixels
+        const mz_image_view crop = view(0x100000, 3LL * H * W, (int64_t)H * W, W, 1), shifted = view(0x100000 + 4 * (8 * W + 8), 3LL * H * W, (int64_t)H * W, W, 1);
+        EXPECT(check_overlap(&crop, &shifted, 0, 1, 256, 256, false).code == MZ_ERR_INVALID_ARGUMENT);
+        EXPECT(check_overlap(&crop, &shifted, 0, 1, 256, 256, true).code == MZ_ERR_INVALID_ARGUMENT);
+        const mz_image_view apart = view(0x100000 + 4 * 3LL * H * W * 2, 3LL * H * W, (int64_t)H * W, W, 1);  // the frame behind the batch of two
+        EXPECT(check_overlap(&frame, &apart, 0, 2, H, W, false).code == MZ_OK);
+        EXPECT(check_workspace((void*)0x10000, 8, 16).code == MZ_ERR_WORKSPACE_TOO_SMALL);
+        EXPECT(check_workspace(nullptr, SIZE_MAX, 16).code == MZ_ERR_WORKSPACE_TOO_SMALL);
+        EXPECT(check_workspace((void*)0x10000, SIZE_MAX, SIZE_MAX).code == MZ_OK);
+    }
+
+    if (g_failed) printf("%d expectation(s) failed\n", g_failed);
+    else printf("view checks OK\n");
+    return g_failed ? 1 : 0;
+}

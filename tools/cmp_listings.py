@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Are the kernels of the working tree the SAME MACHINE CODE as those of another commit?
 
-    tools/cmp_listings.py [--base REV] [--work DIR] [--jobs N] [unit ...]      (units: mz_conv3r mz_conv3t ..; default: every csrc/*.hip)
+    tools/cmp_listings.py [--base REV] [--work DIR] [--jobs N] [--rename OLD=NEW ..] [unit ...]
+                                                                      (units: mz_conv3r mz_conv3t ..; default: every csrc/*.hip)
 
 Compiles every unit device-only to a gfx950 assembly listing -- the flags of tests/test_kernel_resources.py, no GPU needed -- once from
 `git archive REV` (default HEAD; kept in DIR/<commit> and reused) and once from the working tree, and compares the listings PER KERNEL
@@ -9,6 +10,10 @@ SYMBOL after removing what differs between any two compiles of equal code: the _
 .LBB<n>_<m> / .Lfunc_end<n> labels and loop comments, the .file / .ident lines.  What lies outside the functions (the code-object
 metadata: argument layouts, register counts) is compared as the pseudo symbol <module>.  Prints a count per unit; exit status 1 if
 anything differs, and then DIR/diff/<unit>.<n>.diff holds the first differing symbols.
+
+--rename OLD=NEW (repeatable) substitutes text in the base listing before it is split into symbols: a struct a kernel takes by value is
+part of the kernel's mangled name, so renaming the struct (say 10ResizeView=11StridedView) would otherwise report every kernel as
+"only in base".
 
 For refactors of kernels that live at their register cap, where "about as fast" is not a criterion one can check without a GPU and
 "the same listing" is.
@@ -37,11 +42,14 @@ BEGIN = re.compile(r"; -- Begin function (\S+)")
 TAIL = re.compile(r"^\s*\.section\s+\.AMDGPU\.gpr_maximums|__hip_cuid_")
 
 
-def symbols(listing: Path):
+def symbols(listing: Path, renames=()):
     """{symbol: normalised lines}; '<module>' = everything in front of the first and behind the last function."""
     out = {"<module>": []}
     cur = "<module>"
-    for line in listing.read_text().splitlines():
+    text = listing.read_text()
+    for old, new in renames:
+        text = text.replace(old, new)
+    for line in text.splitlines():
         if DROP.match(line):
             continue
         m = BEGIN.search(line)
@@ -71,7 +79,9 @@ def main():
     ap.add_argument("--base", default="HEAD", help="commit to compare the working tree against")
     ap.add_argument("--work", default=str(Path(tempfile.gettempdir()) / "mz_cmp_listings"), help="where listings are kept")
     ap.add_argument("--jobs", type=int, default=4, help="hipcc processes side by side")
+    ap.add_argument("--rename", action="append", default=[], metavar="OLD=NEW", help="text substitution in the base listing")
     args = ap.parse_args()
+    renames = [tuple(r.split("=", 1)) for r in args.rename]
     work = Path(args.work)
     units = args.units or sorted(p.stem for p in (ROOT / CSRC).glob("*.hip"))
     sha = subprocess.run(["git", "-C", str(ROOT), "rev-parse", args.base], capture_output=True, text=True, check=True).stdout.strip()
@@ -87,7 +97,7 @@ def main():
 
     bad = 0
     for u in units:
-        b, h = symbols(base_dir / "s" / f"{u}.s"), symbols(work / "head" / f"{u}.s")
+        b, h = symbols(base_dir / "s" / f"{u}.s", renames), symbols(work / "head" / f"{u}.s")
         differing = [s for s in sorted(set(b) | set(h)) if b.get(s) != h.get(s)]
         every = set(b) | set(h)
         print(f"{u}: {len(every) - len(differing)} of {len(every)} symbols identical (<module> + {len(every) - 1} functions)")

@@ -150,6 +150,46 @@ def dtype_code(torch_dtype) -> int:
     return table[torch_dtype]
 
 
+def elem_code(torch_dtype) -> int:
+    """The `elem` of the image-view entries: 0..2 = MZ_F32 / MZ_BF16 / MZ_F16, 3 = uint8 (mz_forward_view: 0 = the handle's dtype, 1 = uint8)."""
+    import torch
+
+    ELEM = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2, torch.uint8: 3}
+    if torch_dtype not in ELEM:
+        raise TypeError(f"unsupported dtype {torch_dtype}; use float32, bfloat16, float16 or uint8")
+    return ELEM[torch_dtype]
+
+
+def check_same_batch(x, other, shape, names=("x", "out")) -> None:
+    """`other` (the output of `x`, or a second input) is on x's device, of x's dtype and of `shape`."""
+    if other.device != x.device:
+        raise RuntimeError(f"{names[0]} is on {x.device} but {names[1]} is on {other.device}")
+    if other.dtype != x.dtype:
+        raise TypeError(f"{names[0]} ({x.dtype}) and {names[1]} ({other.dtype}) should have the same dtype")
+    if tuple(other.shape) != tuple(shape):
+        raise ValueError(f"{names[1]} has shape {tuple(other.shape)}, expected the one shape {tuple(shape)}")
+
+
+def check_image_batch(x, what: str, other=None, names=("x", "out")):
+    """(elem code, B, H, W) of a logical [B, 3, H, W] CUDA image batch given to ultrazoom_amd.`what`; `other` as check_same_batch."""
+    if x.dim() != 4 or x.shape[1] != 3:
+        raise ValueError(f"expected a [B, 3, H, W] tensor, got {tuple(x.shape)}")
+    elem = elem_code(x.dtype)
+    if not x.is_cuda:
+        raise RuntimeError(f"ultrazoom_amd.{what} computes on an MI355X only: move the image to a 'cuda' device. There is no CPU path.")
+    B, _, H, W = x.shape
+    if B < 1 or H < 1 or W < 1:
+        raise ValueError(f"an empty batch or image: {tuple(x.shape)}")
+    if other is not None:
+        check_same_batch(x, other, x.shape, names)
+    return elem, B, H, W
+
+
+def view(ptr, strides) -> MzImageView:
+    """An mz_image_view: the address of element (0, 0, 0, 0) and the element strides (image, channel, row, column; signed)."""
+    return MzImageView(c_void_p(ptr), (c_int64 * 4)(*[int(v) for v in strides]))
+
+
 def make_config(cfg: dict) -> MzConfig:
     return MzConfig(**{k: int(cfg[k]) for k, _ in MzConfig._fields_})
 
@@ -163,8 +203,7 @@ def metrics_workspace_bytes(B: int, H: int, W: int, which: int) -> int:
 def metrics(pred_ptr, pred_strides, target_ptr, target_strides, elem, B, H, W, which, data_range, sigma_n_sq, out_ptr, ws_ptr, ws_bytes,
             stream) -> None:
     """mz_metrics: the two views as for Handle.forward_view; `elem` 0..2 = MZ_F32 / MZ_BF16 / MZ_F16, 3 = uint8."""
-    pv = MzImageView(c_void_p(pred_ptr), (c_int64 * 4)(*[int(v) for v in pred_strides]))
-    tv = MzImageView(c_void_p(target_ptr), (c_int64 * 4)(*[int(v) for v in target_strides]))
+    pv, tv = view(pred_ptr, pred_strides), view(target_ptr, target_strides)
     check(
         lib().mz_metrics(
             byref(pv), byref(tv), int(elem), B, H, W, int(which), float(data_range), float(sigma_n_sq), c_void_p(out_ptr),
@@ -182,8 +221,7 @@ def resize_workspace_bytes(Hin: int, Win: int, Hout: int, Wout: int, filter_: in
 def resize(x_ptr, x_strides, out_ptr, out_strides, elem, B, Hin, Win, Hout, Wout, filter_, clamp, window, ws_ptr, ws_bytes, stream) -> None:
     """mz_resize: the two views as for Handle.forward_view (out: of the window); `elem` 0..2 = MZ_F32 / MZ_BF16 / MZ_F16, 3 = uint8;
     `window` = (y0, x0, h, w) in pixels of the Hout x Wout result, or None."""
-    xv = MzImageView(c_void_p(x_ptr), (c_int64 * 4)(*[int(v) for v in x_strides]))
-    ov = MzImageView(c_void_p(out_ptr), (c_int64 * 4)(*[int(v) for v in out_strides]))
+    xv, ov = view(x_ptr, x_strides), view(out_ptr, out_strides)
     win = (c_int32 * 4)(*[int(v) for v in window]) if window is not None else None
     check(
         lib().mz_resize(
@@ -203,20 +241,15 @@ def resize_taps(n_in: int, n_out: int, filter_: int, i: int):
     return int(first.value), [float(w[j]) for j in range(count)]
 
 
-def _views(x_ptr, x_strides, out_ptr, out_strides):
-    return (MzImageView(c_void_p(x_ptr), (c_int64 * 4)(*[int(v) for v in x_strides])),
-            MzImageView(c_void_p(out_ptr), (c_int64 * 4)(*[int(v) for v in out_strides])))
-
-
 def blur(x_ptr, x_strides, out_ptr, out_strides, elem, B, H, W, sigma, stream) -> None:
     """mz_blur: the two views as for `resize`; `elem` 0..2 = MZ_F32 / MZ_BF16 / MZ_F16, 3 = uint8."""
-    xv, ov = _views(x_ptr, x_strides, out_ptr, out_strides)
+    xv, ov = view(x_ptr, x_strides), view(out_ptr, out_strides)
     check(lib().mz_blur(byref(xv), byref(ov), int(elem), B, H, W, float(sigma), c_void_p(stream)))
 
 
 def noise(x_ptr, x_strides, out_ptr, out_strides, elem, B, H, W, sigma, seed, offset, stream) -> None:
     """mz_noise: `seed` and `offset` are taken modulo 2^64; out may be the same view as x."""
-    xv, ov = _views(x_ptr, x_strides, out_ptr, out_strides)
+    xv, ov = view(x_ptr, x_strides), view(out_ptr, out_strides)
     check(lib().mz_noise(byref(xv), byref(ov), int(elem), B, H, W, float(sigma), int(seed) & (2**64 - 1), int(offset) & (2**64 - 1),
                          c_void_p(stream)))
 
@@ -229,7 +262,7 @@ def jpeg_workspace_bytes(B: int, H: int, W: int) -> int:
 
 def jpeg(x_ptr, x_strides, out_ptr, out_strides, elem, B, H, W, quality, ws_ptr, ws_bytes, stream) -> None:
     """mz_jpeg: the round trip at `quality` 1..100 on a workspace of `jpeg_workspace_bytes(B, H, W)` bytes."""
-    xv, ov = _views(x_ptr, x_strides, out_ptr, out_strides)
+    xv, ov = view(x_ptr, x_strides), view(out_ptr, out_strides)
     check(lib().mz_jpeg(byref(xv), byref(ov), int(elem), B, H, W, int(quality), c_void_p(ws_ptr), ws_bytes, c_void_p(stream)))
 
 
@@ -329,8 +362,7 @@ class Handle:
                      max_in_flight, stream) -> None:
         """mz_forward_view: `x_ptr` / `out_ptr` address element (0, 0, 0, 0) of each view (out: of the window), the strides count
         elements (image, channel, row, column; signed); `window` = (y0, x0, h, w) in output pixels or None; `elem` 1 = uint8."""
-        xv = MzImageView(c_void_p(x_ptr), (c_int64 * 4)(*[int(v) for v in x_strides]))
-        ov = MzImageView(c_void_p(out_ptr), (c_int64 * 4)(*[int(v) for v in out_strides]))
+        xv, ov = view(x_ptr, x_strides), view(out_ptr, out_strides)
         win = (c_int32 * 4)(*[int(v) for v in window]) if window is not None else None
         check(
             lib().mz_forward_view(

@@ -47,7 +47,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
-#include "mz_resize.h"  // ResizeView, ResizeElem: one statement of a view and of the element codes
+#include "mz_view.h"
 
 namespace mz {
 
@@ -109,8 +109,8 @@ inline JpegPlan jpeg_plan(int B, int H, int W) {
 }
 
 struct DegradeArgs {
-    ResizeView x, out;
-    int elem;  // ResizeElem
+    StridedView x, out;
+    int elem;  // Elem 0..3
     int B, H, W;
 };
 // Each enqueues one call; hipErrorInvalidValue for a grid beyond 2^31 - 1 workgroups
@@ -132,25 +132,11 @@ __host__ __device__ inline void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t
 
 #ifdef MZ_DEGRADE_KERNELS  // mz_degrade.hip only
 
-// the element types' loads and stores, as mz_resize.h has them (its own are compiled into mz_resize.hip only)
-template <int E> __device__ __forceinline__ float ld_elem(const void* base, long long i) {
-    if constexpr (E == RE_F32) return ((const float*)base)[i];
-    else if constexpr (E == RE_BF16) return __builtin_bit_cast(float, (uint32_t)((const uint16_t*)base)[i] << 16);
-    else if constexpr (E == RE_F16) return (float)((const _Float16*)base)[i];
-    else return (float)((const uint8_t*)base)[i] / 255.0f;  // a true division, as mz_forward_u8's read
-}
-template <int E> __device__ __forceinline__ void st_elem(void* base, long long i, float v) {
-    if constexpr (E == RE_U8) ((uint8_t*)base)[i] = (uint8_t)fminf(fmaxf(v * 255.0f + 0.5f, 0.0f), 255.0f);  // exactly mz_forward_u8's store
-    else if constexpr (E == RE_F32) ((float*)base)[i] = v;
-    else if constexpr (E == RE_BF16) ((__bf16*)base)[i] = (__bf16)v;
-    else ((_Float16*)base)[i] = (_Float16)v;
-}
-
 __device__ __forceinline__ int reflect_index(int i, int n) { return i < 0 ? -i : i >= n ? 2 * (n - 1) - i : i; }
 
 // grid: tiles * 3 * B workgroups, tile fastest
 template <int E>
-__global__ __launch_bounds__(kDegradeThreads) void blur_kernel(const ResizeView x, const ResizeView out, int H, int W, long long tiles, int tiles_x,
+__global__ __launch_bounds__(kDegradeThreads) void blur_kernel(const StridedView x, const StridedView out, int H, int W, long long tiles, int tiles_x,
                                                                  const BlurWeights bw) {
     constexpr int T = kBlurTile, S = T + 2 * kBlurMaxHalf, SP = 64;  // staged tile: at most S x S, rows SP floats apart
     static_assert(S <= SP, "row pitch");
@@ -171,7 +157,7 @@ __global__ __launch_bounds__(kDegradeThreads) void blur_kernel(const ResizeView 
     for (int e = tid; e < rows * cols; e += kDegradeThreads) {
         const int r = e / cols, q = e - r * cols;
         const int gy = reflect_index(y0 - half + r, H), gx = reflect_index(x0 - half + q, W);
-        in_t[r * SP + q] = ld_elem<E>(x.data, xb + (long long)gy * x.s[2] + (long long)gx * x.s[3]);
+        in_t[r * SP + q] = ld_f32<E>(x.data, xb + (long long)gy * x.s[2] + (long long)gx * x.s[3]);
     }
     __syncthreads();
     // horizontal pass: thread (ty, tx) filters column tx of rows ty, ty + 8, ..
@@ -187,24 +173,13 @@ __global__ __launch_bounds__(kDegradeThreads) void blur_kernel(const ResizeView 
         for (int r = ty; r < th; r += kDegradeThreads / T) {
             double acc = 0.0;
             for (int j = 0; j < k; ++j) acc = fma(wl[j], (double)hrow[(r + j) * T + tx], acc);
-            st_elem<E>((void*)out.data, b * out.s[0] + c * out.s[1] + (long long)(y0 + r) * out.s[2] + (long long)(x0 + tx) * out.s[3], (float)acc);
+            st_f32<E>((void*)out.data, b * out.s[0] + c * out.s[1] + (long long)(y0 + r) * out.s[2] + (long long)(x0 + tx) * out.s[3], (float)acc, 0);
         }
-}
-
-template <int E> __device__ __forceinline__ double ld_double(const void* base, long long i) {
-    if constexpr (E == RE_U8) return (double)((const uint8_t*)base)[i] / 255.0;
-    else return (double)ld_elem<E>(base, i);
-}
-template <int E> __device__ __forceinline__ void st_double01(void* base, long long i, double v) {  // v in [0, 1]
-    if constexpr (E == RE_U8) ((uint8_t*)base)[i] = (uint8_t)(v * 255.0 + 0.5);
-    else if constexpr (E == RE_F32) ((float*)base)[i] = (float)v;
-    else if constexpr (E == RE_BF16) ((__bf16*)base)[i] = (__bf16)(float)v;
-    else ((_Float16*)base)[i] = (_Float16)v;
 }
 
 // grid: ceil(3 H W / 256) * B workgroups, chunk fastest.  x and out may be the same view: a thread reads and writes its own element only
 template <int E>
-__global__ __launch_bounds__(kDegradeThreads) void noise_kernel(const ResizeView x, const ResizeView out, int H, int W, long long chunks, double sigma,
+__global__ __launch_bounds__(kDegradeThreads) void noise_kernel(const StridedView x, const StridedView out, int H, int W, long long chunks, double sigma,
                                                                   unsigned long long seed, unsigned long long offset) {
     const long long wg = blockIdx.x;
     const long long b = wg / chunks;
@@ -217,30 +192,17 @@ __global__ __launch_bounds__(kDegradeThreads) void noise_kernel(const ResizeView
     philox4x32_10((uint32_t)i, (uint32_t)((unsigned long long)i >> 32), (uint32_t)s, (uint32_t)(s >> 32), (uint32_t)seed, (uint32_t)(seed >> 32), u);
     const double u1 = ((double)u[0] + 0.5) * (1.0 / 4294967296.0), u2 = ((double)u[1] + 0.5) * (1.0 / 4294967296.0);
     const double n = sqrt(-2.0 * log(u1)) * cos(6.283185307179586476925 * u2);
-    double v = ld_double<E>(x.data, b * x.s[0] + c * x.s[1] + y * x.s[2] + xx * x.s[3]) + sigma * n;
+    double v = ld_f64<E>(x.data, b * x.s[0] + c * x.s[1] + y * x.s[2] + xx * x.s[3]) + sigma * n;
     v = fmin(fmax(v, 0.0), 1.0);  // (a NaN input becomes 0)
-    st_double01<E>((void*)out.data, b * out.s[0] + c * out.s[1] + y * out.s[2] + xx * out.s[3], v);
+    st_f64_unit<E>((void*)out.data, b * out.s[0] + c * out.s[1] + y * out.s[2] + xx * out.s[3], v);
 }
 
-template <int E> __device__ __forceinline__ int ld_8bit(const void* base, long long i) {
-    if constexpr (E == RE_U8) return ((const uint8_t*)base)[i];
-    else return (int)(uint8_t)fminf(fmaxf(ld_elem<E>(base, i) * 255.0f + 0.5f, 0.0f), 255.0f);
-}
-template <int E> __device__ __forceinline__ void st_8bit(void* base, long long i, int v) {
-    if constexpr (E == RE_U8) ((uint8_t*)base)[i] = (uint8_t)v;
-    else {
-        const float f = (float)v / 255.0f;  // a true division
-        if constexpr (E == RE_F32) ((float*)base)[i] = f;
-        else if constexpr (E == RE_BF16) ((__bf16*)base)[i] = (__bf16)f;
-        else ((_Float16*)base)[i] = (_Float16)f;
-    }
-}
 __device__ __forceinline__ int clamp255(int v) { return v < 0 ? 0 : v > 255 ? 255 : v; }
 __device__ __forceinline__ int dct_sign4(int x) { return ((x + 1) & 2) ? -1 : 1; }  // s_4: + - - + + - - +
 
 // grid: ceil(Wp / (16 kJpegMcus)) * (Hp / 16) * B workgroups, tile fastest.  Blocks of one MCU: 0..3 Y (row-major), 4 Cb, 5 Cr
 template <int E>
-__global__ __launch_bounds__(kDegradeThreads) void jpeg_code_kernel(const ResizeView x, int H, int W, int Hp, int Wp, long long tiles, int tiles_x,
+__global__ __launch_bounds__(kDegradeThreads) void jpeg_code_kernel(const StridedView x, int H, int W, int Hp, int Wp, long long tiles, int tiles_x,
                                                                       const JpegTables qt, uint8_t* ws_y, uint8_t* ws_c) {
     constexpr int M = kJpegMcus, NB = 6 * M, TW = 16 * M;
     __shared__ double Tm[64];           // T[u][x]
@@ -348,7 +310,7 @@ __global__ __launch_bounds__(kDegradeThreads) void jpeg_code_kernel(const Resize
 
 // grid: ceil(H W / 256) * B workgroups, chunk fastest
 template <int E>
-__global__ __launch_bounds__(kDegradeThreads) void jpeg_image_kernel(const ResizeView out, int H, int W, int Hp, int Wp, long long chunks,
+__global__ __launch_bounds__(kDegradeThreads) void jpeg_image_kernel(const StridedView out, int H, int W, int Hp, int Wp, long long chunks,
                                                                        const uint8_t* ws_y, const uint8_t* ws_c) {
     const long long wg = blockIdx.x;
     const long long b = wg / chunks;

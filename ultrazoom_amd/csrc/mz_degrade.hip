@@ -38,33 +38,15 @@ template <int E> static hipError_t launch_jpeg_e(const DegradeArgs& a, const Jpe
 }
 
 hipError_t launch_blur(const DegradeArgs& a, const BlurWeights& bw, hipStream_t s) {
-    switch (a.elem) {
-        case RE_F32: return launch_blur_e<RE_F32>(a, bw, s);
-        case RE_BF16: return launch_blur_e<RE_BF16>(a, bw, s);
-        case RE_F16: return launch_blur_e<RE_F16>(a, bw, s);
-        case RE_U8: return launch_blur_e<RE_U8>(a, bw, s);
-        default: return hipErrorInvalidValue;
-    }
+    return for_elem(a.elem, [&](auto e) { return launch_blur_e<decltype(e)::value>(a, bw, s); });
 }
 
 hipError_t launch_noise(const DegradeArgs& a, double sigma, unsigned long long seed, unsigned long long offset, hipStream_t s) {
-    switch (a.elem) {
-        case RE_F32: return launch_noise_e<RE_F32>(a, sigma, seed, offset, s);
-        case RE_BF16: return launch_noise_e<RE_BF16>(a, sigma, seed, offset, s);
-        case RE_F16: return launch_noise_e<RE_F16>(a, sigma, seed, offset, s);
-        case RE_U8: return launch_noise_e<RE_U8>(a, sigma, seed, offset, s);
-        default: return hipErrorInvalidValue;
-    }
+    return for_elem(a.elem, [&](auto e) { return launch_noise_e<decltype(e)::value>(a, sigma, seed, offset, s); });
 }
 
 hipError_t launch_jpeg(const DegradeArgs& a, const JpegTables& t, const JpegPlan& plan, char* ws, hipStream_t s) {
-    switch (a.elem) {
-        case RE_F32: return launch_jpeg_e<RE_F32>(a, t, plan, ws, s);
-        case RE_BF16: return launch_jpeg_e<RE_BF16>(a, t, plan, ws, s);
-        case RE_F16: return launch_jpeg_e<RE_F16>(a, t, plan, ws, s);
-        case RE_U8: return launch_jpeg_e<RE_U8>(a, t, plan, ws, s);
-        default: return hipErrorInvalidValue;
-    }
+    return for_elem(a.elem, [&](auto e) { return launch_jpeg_e<decltype(e)::value>(a, t, plan, ws, s); });
 }
 
 }  // namespace mz

@@ -22,6 +22,7 @@
 #include "mz_pack.h"
 #include "mz_resize.h"
 #include "mz_degrade.h"
+#include "mz_view_check.h"
 
 using namespace mz;
 
@@ -38,6 +39,7 @@ static int fail(int code, const char* fmt, ...) {
     va_end(ap);
     return code;
 }
+static int fail(const Refusal& r) { return fail(r.code, "%s", r.msg); }  // what a check of mz_view_check.h refused
 #define HIPCHK(expr)                                                                               \
     do {                                                                                           \
         hipError_t e_ = (expr);                                                                    \
@@ -1241,8 +1243,7 @@ static int forward_impl(mz_handle* h, const void* x, void* out_sr, float* out_qa
     const int nbmax = default_micro_batch(h, B, H, W, max_images_in_flight);
     Plan p;
     make_plan(h, nbmax, H, W, p);
-    if (workspace_bytes < p.total)
-        return fail(MZ_ERR_WORKSPACE_TOO_SMALL, "workspace too small: %zu bytes given, %zu needed", workspace_bytes, p.total);
+    if (const Refusal r = check_workspace(workspace, workspace_bytes, p.total)) return fail(r);
     const size_t sz = io_u8 ? 1 : dtype_size(h->dtype);
     const int r = h->cfg.upscale_ratio;
     // bytes from one image to the next: dense NCHW, or the views' image strides (signed)
@@ -1275,26 +1276,17 @@ extern "C" int mz_forward_view(mz_handle* h, const mz_image_view* x, const mz_im
                                int clamp, int elem, const int32_t window[4], void* workspace, size_t workspace_bytes,
                                int max_images_in_flight, void* hip_stream) {
     if (!h) return fail(MZ_ERR_INVALID_ARGUMENT, "null handle");
-    if (!x || !out) return fail(MZ_ERR_INVALID_ARGUMENT, "null image view");
-    if (!x->data || !out->data) return fail(MZ_ERR_INVALID_ARGUMENT, "an image view has null data");
-    if (elem != 0 && elem != 1) return fail(MZ_ERR_INVALID_ARGUMENT, "elem must be 0 (the handle's dtype) or 1 (uint8), got %d", elem);
+    static const ViewRules rules = {1, "0 (the handle's dtype) or 1 (uint8)", /*second_is_output*/ true, /*batch_bound*/ false, /*side_bound*/ false};
+    StridedView xv, ov;
+    if (const Refusal r = check_views(x, out, rules, elem, B, H, W, &xv, &ov)) return fail(r);
     if (B <= 0 || H < 8 || W < 8) return fail(MZ_ERR_INVALID_ARGUMENT, "need B >= 1 and H, W >= 8 (got %d, %d, %d)", B, H, W);
     const long long rH = (long long)h->cfg.upscale_ratio * H, rW = (long long)h->cfg.upscale_ratio * W;
     if (rH > 0x7fffffffLL || rW > 0x7fffffffLL) return fail(MZ_ERR_INVALID_ARGUMENT, "the output of %d x %d is too large", H, W);
     ImageViews v;
-    v.y0 = 0; v.x0 = 0; v.h = (int)rH; v.w = (int)rW;
-    if (window) {
-        v.y0 = window[0]; v.x0 = window[1]; v.h = window[2]; v.w = window[3];
-        if (v.h <= 0 || v.w <= 0) return fail(MZ_ERR_INVALID_ARGUMENT, "empty window (%d x %d)", v.h, v.w);
-        if (v.y0 < 0 || v.x0 < 0 || (long long)v.y0 + v.h > rH || (long long)v.x0 + v.w > rW)
-            return fail(MZ_ERR_INVALID_ARGUMENT, "window {%d, %d, %d, %d} is not inside the %lld x %lld output", v.y0, v.x0, v.h, v.w, rH, rW);
-    }
-    static const char* const dim[4] = {"image", "channel", "row", "column"};
+    if (const Refusal r = check_window(window, (int)rH, (int)rW, &v.y0, &v.x0, &v.h, &v.w)) return fail(r);
     for (int i = 0; i < 4; ++i) {
-        v.in[i] = x->stride[i];
-        v.out[i] = out->stride[i];
-        if (out->stride[i] == 0 && (i > 0 || B > 1))
-            return fail(MZ_ERR_INVALID_ARGUMENT, "the output view's %s stride is 0: its elements would overlap", dim[i]);
+        v.in[i] = xv.s[i];
+        v.out[i] = ov.s[i];
     }
     return forward_impl(h, x->data, out->data, out_qa, B, H, W, elem == 1 ? 1 : clamp, workspace, workspace_bytes,
                         max_images_in_flight, hip_stream, elem, &v);
@@ -1458,27 +1450,15 @@ extern "C" int mz_metrics_workspace_bytes(int B, int H, int W, int which, size_t
 extern "C" int mz_metrics(const mz_image_view* pred, const mz_image_view* target, int elem, int B, int H, int W, int which,
                           double data_range, double sigma_n_sq, double* out_dev, void* workspace, size_t workspace_bytes,
                           void* hip_stream) {
-    if (!pred || !target) return fail(MZ_ERR_INVALID_ARGUMENT, "null image view");
-    if (!pred->data || !target->data) return fail(MZ_ERR_INVALID_ARGUMENT, "an image view has null data");
-    if (elem < 0 || elem > 3) return fail(MZ_ERR_INVALID_ARGUMENT, "elem must be 0 (f32), 1 (bf16), 2 (f16) or 3 (uint8), got %d", elem);
+    static const ViewRules rules = {3, MZ_ELEM_NAMES_0_3, /*second_is_output*/ false, /*batch_bound*/ false, /*side_bound*/ false};
+    MetricsArgs a = {};
+    if (const Refusal r = check_views(pred, target, rules, elem, B, H, W, &a.pred, &a.target)) return fail(r);
     if (int rc = check_metrics_shape(B, H, W, which)) return rc;
     if (!out_dev) return fail(MZ_ERR_INVALID_ARGUMENT, "null out_dev");
-    MetricsArgs a = {};
     a.plan = metrics_plan(B, H, W, which);
-    if (!workspace || workspace_bytes < a.plan.total)
-        return fail(MZ_ERR_WORKSPACE_TOO_SMALL, "workspace too small: %zu bytes given, %zu needed", workspace ? workspace_bytes : (size_t)0,
-                    a.plan.total);
+    if (const Refusal r = check_workspace(workspace, workspace_bytes, a.plan.total)) return fail(r);
     if (int rc = ensure_device_ready()) return rc;
-    a.pred.data = pred->data;
-    a.target.data = target->data;
-    for (int i = 0; i < 4; ++i) {
-        a.pred.s[i] = pred->stride[i];
-        a.target.s[i] = target->stride[i];
-    }
-    a.elem = elem;
-    a.B = B;
-    a.H = H;
-    a.W = W;
+    a.elem = elem; a.B = B; a.H = H; a.W = W;
     a.which = which;
     a.data_range = data_range;
     a.sigma_n_sq = sigma_n_sq;
@@ -1514,33 +1494,14 @@ extern "C" int mz_resize_workspace_bytes(int Hin, int Win, int Hout, int Wout, i
 
 extern "C" int mz_resize(const mz_image_view* x, const mz_image_view* out, int elem, int B, int Hin, int Win, int Hout, int Wout, int filter,
                          int clamp, const int32_t window[4], void* workspace, size_t workspace_bytes, void* hip_stream) {
-    if (!x || !out) return fail(MZ_ERR_INVALID_ARGUMENT, "null image view");
-    if (!x->data || !out->data) return fail(MZ_ERR_INVALID_ARGUMENT, "an image view has null data");
-    if (elem < 0 || elem > 3) return fail(MZ_ERR_INVALID_ARGUMENT, "elem must be 0 (f32), 1 (bf16), 2 (f16) or 3 (uint8), got %d", elem);
-    if (B < 1 || B > 65535) return fail(MZ_ERR_INVALID_ARGUMENT, "need 1 <= B <= 65535 (got %d)", B);
-    if (int rc = check_resize_shape(Hin, Win, Hout, Wout, filter)) return rc;
+    static const ViewRules rules = {3, MZ_ELEM_NAMES_0_3, /*second_is_output*/ true, /*batch_bound*/ true, /*side_bound*/ false};
     ResizeArgs a = {};
-    a.y0 = 0; a.x0 = 0; a.h = Hout; a.w = Wout;
-    if (window) {
-        a.y0 = window[0]; a.x0 = window[1]; a.h = window[2]; a.w = window[3];
-        if (a.h <= 0 || a.w <= 0) return fail(MZ_ERR_INVALID_ARGUMENT, "empty window (%d x %d)", a.h, a.w);
-        if (a.y0 < 0 || a.x0 < 0 || (long long)a.y0 + a.h > Hout || (long long)a.x0 + a.w > Wout)
-            return fail(MZ_ERR_INVALID_ARGUMENT, "window {%d, %d, %d, %d} is not inside the %d x %d output", a.y0, a.x0, a.h, a.w, Hout, Wout);
-    }
-    static const char* const dim[4] = {"image", "channel", "row", "column"};
-    for (int i = 0; i < 4; ++i) {
-        a.x.s[i] = x->stride[i];
-        a.out.s[i] = out->stride[i];
-        if (out->stride[i] == 0 && (i > 0 || B > 1))
-            return fail(MZ_ERR_INVALID_ARGUMENT, "the output view's %s stride is 0: its elements would overlap", dim[i]);
-    }
+    if (const Refusal r = check_views(x, out, rules, elem, B, Hout, Wout, &a.x, &a.out)) return fail(r);
+    if (int rc = check_resize_shape(Hin, Win, Hout, Wout, filter)) return rc;
+    if (const Refusal r = check_window(window, Hout, Wout, &a.y0, &a.x0, &a.h, &a.w)) return fail(r);
     a.plan = resize_plan(Hin, Win, Hout, Wout, filter);
-    if (!workspace || workspace_bytes < a.plan.total)
-        return fail(MZ_ERR_WORKSPACE_TOO_SMALL, "workspace too small: %zu bytes given, %zu needed", workspace ? workspace_bytes : (size_t)0,
-                    a.plan.total);
+    if (const Refusal r = check_workspace(workspace, workspace_bytes, a.plan.total)) return fail(r);
     if (int rc = ensure_device_ready()) return rc;
-    a.x.data = x->data;
-    a.out.data = out->data;
     a.elem = elem;
     a.B = B;
     a.Hin = Hin; a.Win = Win; a.Hout = Hout; a.Wout = Wout;
@@ -1566,48 +1527,11 @@ extern "C" int mz_debug_resize_taps(int n_in, int n_out, int filter, int i, int*
 // the degradation chain (mz_degrade.h): no reference counterpart in model.py; stands in for torchvision's gaussian_blur, gaussian_noise
 // and jpeg as the reference's transforms.py uses them.  Stateless like mz_resize.  Every check comes before anything touches the GPU.
 // ------------------------------------------------------------------------------------------------
-// the byte range [lo, hi) the elements of a [B,3,H,W] view lie in
-static void view_extent(const mz_image_view* v, int elem, int B, int H, int W, long long* lo, long long* hi) {
-    const long long es = elem == RE_F32 ? 4 : elem == RE_U8 ? 1 : 2;
-    const long long n[4] = {B, 3, H, W};
-    long long a = 0, b = 0;
-    for (int i = 0; i < 4; ++i) {
-        const long long span = (n[i] - 1) * (long long)v->stride[i];
-        if (span < 0) a += span; else b += span;
-    }
-    *lo = (long long)(intptr_t)v->data + a * es;
-    *hi = (long long)(intptr_t)v->data + (b + 1) * es;
-}
-
 static int check_degrade_views(const mz_image_view* x, const mz_image_view* out, int elem, int B, int H, int W, int in_place_ok, DegradeArgs* a) {
-    if (!x || !out) return fail(MZ_ERR_INVALID_ARGUMENT, "null image view");
-    if (!x->data || !out->data) return fail(MZ_ERR_INVALID_ARGUMENT, "an image view has null data");
-    if (elem < 0 || elem > 3) return fail(MZ_ERR_INVALID_ARGUMENT, "elem must be 0 (f32), 1 (bf16), 2 (f16) or 3 (uint8), got %d", elem);
-    if (B < 1 || B > 65535) return fail(MZ_ERR_INVALID_ARGUMENT, "need 1 <= B <= 65535 (got %d)", B);
-    if (H < 1 || W < 1) return fail(MZ_ERR_INVALID_ARGUMENT, "need H, W >= 1 (got %d x %d)", H, W);
-    if (H > (1 << 28) || W > (1 << 28)) return fail(MZ_ERR_INVALID_ARGUMENT, "at most 2^28 pixels a side (got %d x %d)", H, W);
-    static const char* const dim[4] = {"image", "channel", "row", "column"};
-    for (int i = 0; i < 4; ++i) {
-        a->x.s[i] = x->stride[i];
-        a->out.s[i] = out->stride[i];
-        if (out->stride[i] == 0 && (i > 0 || B > 1))
-            return fail(MZ_ERR_INVALID_ARGUMENT, "the output view's %s stride is 0: its elements would overlap", dim[i]);
-    }
-    const bool same = x->data == out->data && x->stride[0] == out->stride[0] && x->stride[1] == out->stride[1] &&
-                      x->stride[2] == out->stride[2] && x->stride[3] == out->stride[3];
-    if (!(same && in_place_ok)) {
-        long long xl, xh, ol, oh;
-        view_extent(x, elem, B, H, W, &xl, &xh);
-        view_extent(out, elem, B, H, W, &ol, &oh);
-        if (xl < oh && ol < xh)
-            return fail(MZ_ERR_INVALID_ARGUMENT, in_place_ok ? "x and out overlap without being the same view" : "x and out overlap: this entry does not work in place");
-    }
-    a->x.data = x->data;
-    a->out.data = out->data;
-    a->elem = elem;
-    a->B = B;
-    a->H = H;
-    a->W = W;
+    static const ViewRules rules = {3, MZ_ELEM_NAMES_0_3, /*second_is_output*/ true, /*batch_bound*/ true, /*side_bound*/ true};
+    if (const Refusal r = check_views(x, out, rules, elem, B, H, W, &a->x, &a->out)) return fail(r);
+    if (const Refusal r = check_overlap(x, out, elem, B, H, W, in_place_ok != 0)) return fail(r);
+    a->elem = elem; a->B = B; a->H = H; a->W = W;
     return MZ_OK;
 }
 
@@ -1650,8 +1574,7 @@ extern "C" int mz_jpeg(const mz_image_view* x, const mz_image_view* out, int ele
     if (int rc = check_degrade_views(x, out, elem, B, H, W, 0, &a)) return rc;
     if (quality < 1 || quality > 100) return fail(MZ_ERR_INVALID_ARGUMENT, "quality must be 1..100, got %d", quality);
     const JpegPlan plan = jpeg_plan(B, H, W);
-    if (!workspace || workspace_bytes < plan.total)
-        return fail(MZ_ERR_WORKSPACE_TOO_SMALL, "workspace too small: %zu bytes given, %zu needed", workspace ? workspace_bytes : (size_t)0, plan.total);
+    if (const Refusal r = check_workspace(workspace, workspace_bytes, plan.total)) return fail(r);
     JpegTables t;
     jpeg_qtable(quality, &t);
     if (int rc = ensure_device_ready()) return rc;

@@ -23,6 +23,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "mz_view.h"
+
 namespace mz {
 
 constexpr int kMetricsTileH = 16;   // output pixels of one moments_kernel workgroup
@@ -33,7 +35,6 @@ constexpr int kMetricsMaxTaps = 17;
 constexpr int kMetricSlots = 16;    // == MZ_METRIC_SLOTS
 constexpr int kPsnrBlocksMax = 512; // psnr_kernel workgroups per image (<= 2 * kMetricsThreads: psnr_reduce_kernel)
 
-enum MetricElem : int { ME_F32 = 0, ME_BF16 = 1, ME_F16 = 2, ME_U8 = 3, ME_F64 = 4 /* the VIF pyramid in the workspace */ };
 enum MetricBits : int { MET_PSNR = 1, MET_SSIM = 2, MET_VIF = 4 };
 // out[b][slot]
 enum MetricSlot : int {
@@ -41,10 +42,6 @@ enum MetricSlot : int {
     MS_VIF_NUM = 8 /* ..10: per channel */, MS_VIF_DEN = 11 /* ..13 */, MS_SSIM_RANGE = 14
 };
 
-struct MetricsView {
-    const void* data;  // element (image 0, channel 0, row 0, column 0)
-    long long s[4];    // element strides: image, channel, row, column
-};
 struct MetricsTaps {
     double w[kMetricsMaxTaps];  // the normalised 1-D Gaussian window, computed by the host in double
 };
@@ -97,8 +94,8 @@ inline MetricsPlan metrics_plan(int B, int H, int W, int which) {
 }
 
 struct MetricsArgs {
-    MetricsView pred, target;
-    int elem;            // MetricElem 0..3
+    StridedView pred, target;
+    int elem;            // Elem 0..3
     int B, H, W;
     int which;           // MetricBits
     double data_range;   // SSIM: > 0 fixed, <= 0 from the batch
@@ -111,14 +108,6 @@ struct MetricsArgs {
 hipError_t launch_metrics(const MetricsArgs& a, hipStream_t s);
 
 #ifdef MZ_METRICS_KERNELS  // mz_metrics.hip only: the host runtime includes the plan above without the device code
-
-template <int E> __device__ __forceinline__ double ld_metric(const void* base, long long i) {
-    if constexpr (E == ME_F32) return (double)((const float*)base)[i];
-    else if constexpr (E == ME_BF16) return (double)__builtin_bit_cast(float, (uint32_t)((const uint16_t*)base)[i] << 16);
-    else if constexpr (E == ME_F16) return (double)((const _Float16*)base)[i];
-    else if constexpr (E == ME_U8) return (double)((const uint8_t*)base)[i] / 255.0;  // a true division, as mz_forward_u8's read
-    else return ((const double*)base)[i];
-}
 
 struct OpSum { static __device__ __forceinline__ double f(double a, double b) { return a + b; } };
 struct OpMin { static __device__ __forceinline__ double f(double a, double b) { return b < a ? b : a; } };
@@ -139,7 +128,7 @@ template <class OP> __device__ __forceinline__ double block_reduce(double v, dou
 
 // ---- PSNR part ----------------------------------------------------------------------------------------------------------------------
 // grid (psnr_blocks, B): workgroup i takes rows i, i + psnr_blocks, .. of the 3 H channel rows of its image
-template <int E> __global__ __launch_bounds__(kMetricsThreads) void psnr_kernel(const MetricsView p, const MetricsView t, int H, int W,
+template <int E> __global__ __launch_bounds__(kMetricsThreads) void psnr_kernel(const StridedView p, const StridedView t, int H, int W,
                                                                                   double* part) {
     __shared__ double sh[kMetricsThreads];
     const long long b = blockIdx.y;
@@ -148,7 +137,7 @@ template <int E> __global__ __launch_bounds__(kMetricsThreads) void psnr_kernel(
         const long long c = r / H, y = r - c * H;
         const long long po = b * p.s[0] + c * p.s[1] + y * p.s[2], to = b * t.s[0] + c * t.s[1] + y * t.s[2];
         for (long long x = threadIdx.x; x < W; x += kMetricsThreads) {
-            const double pv = ld_metric<E>(p.data, po + x * p.s[3]), tv = ld_metric<E>(t.data, to + x * t.s[3]);
+            const double pv = ld_f64<E>(p.data, po + x * p.s[3]), tv = ld_f64<E>(t.data, to + x * t.s[3]);
             const double d = pv - tv;
             sq += d * d;
             pmin = OpMin::f(pmin, pv);
@@ -255,7 +244,7 @@ __device__ __forceinline__ void vif_pixel(const double m[5], double sigma_n_sq, 
 // param: EPI_SSIM the fixed data range (> 0) or <= 0 = read *range_dev; EPI_VIF sigma_n_sq.
 // part: EPI_SSIM [B * 3][tiles], EPI_VIF [B * 3][tiles][2]
 template <int E, int T, int EPI>
-__global__ __launch_bounds__(kMetricsThreads) void moments_kernel(const MetricsView p, const MetricsView t, int H, int W, long long tiles,
+__global__ __launch_bounds__(kMetricsThreads) void moments_kernel(const StridedView p, const StridedView t, int H, int W, long long tiles,
                                                                     int tiles_x, const MetricsTaps taps, double param,
                                                                     const double* range_dev, double* part) {
     constexpr int TH = kMetricsTileH, TW = kMetricsTileW, R = kMetricsRun;
@@ -278,8 +267,8 @@ __global__ __launch_bounds__(kMetricsThreads) void moments_kernel(const MetricsV
         const long long gy = y0 + yy, gx = x0 + xx;
         double pv = 0.0, tv = 0.0;
         if (gy < H && gx < W) {
-            pv = ld_metric<E>(p.data, pb + gy * p.s[2] + gx * p.s[3]);
-            tv = ld_metric<E>(t.data, tb + gy * t.s[2] + gx * t.s[3]);
+            pv = ld_f64<E>(p.data, pb + gy * p.s[2] + gx * p.s[3]);
+            tv = ld_f64<E>(t.data, tb + gy * t.s[2] + gx * t.s[3]);
         }
         sp[i] = pv;
         st[i] = tv;
@@ -353,7 +342,7 @@ __global__ __launch_bounds__(kMetricsThreads) void moments_kernel(const MetricsV
 // ---- VIF: the next scale --------------------------------------------------------------------------------------------------------------
 // out[plane][y][x] = sum_ij w[i] w[j] src[plane][2 y + i][2 x + j] for both images; grid: ceil(Ho * Wo / 256) * 3 * B workgroups
 template <int E, int T>
-__global__ __launch_bounds__(kMetricsThreads) void down_kernel(const MetricsView p, const MetricsView t, int Ho, int Wo, long long blocks,
+__global__ __launch_bounds__(kMetricsThreads) void down_kernel(const StridedView p, const StridedView t, int Ho, int Wo, long long blocks,
                                                                  const MetricsTaps taps, double* outp, double* outt) {
     const long long wg = blockIdx.x;
     const long long plane = wg / blocks;
@@ -370,8 +359,8 @@ __global__ __launch_bounds__(kMetricsThreads) void down_kernel(const MetricsView
         double hp_ = 0.0, ht_ = 0.0;
 #pragma unroll
         for (int k = 0; k < T; ++k) {
-            hp_ = fma(taps.w[k], ld_metric<E>(p.data, pb + r * p.s[2] + k * p.s[3]), hp_);
-            ht_ = fma(taps.w[k], ld_metric<E>(t.data, tb + r * t.s[2] + k * t.s[3]), ht_);
+            hp_ = fma(taps.w[k], ld_f64<E>(p.data, pb + r * p.s[2] + k * p.s[3]), hp_);
+            ht_ = fma(taps.w[k], ld_f64<E>(t.data, tb + r * t.s[2] + k * t.s[3]), ht_);
         }
         ap = fma(taps.w[r], hp_, ap);
         at = fma(taps.w[r], ht_, at);

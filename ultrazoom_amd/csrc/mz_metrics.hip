@@ -22,7 +22,7 @@ static MetricsTaps gaussian_taps(int n, double sigma) {
 static bool grid_ok(long long wgs) { return wgs > 0 && wgs <= 0x7fffffffLL; }
 
 template <int E, int T, int EPI>
-static hipError_t launch_moments(const MetricsView& p, const MetricsView& t, int B, int H, int W, long long tiles, const MetricsTaps& taps,
+static hipError_t launch_moments(const StridedView& p, const StridedView& t, int B, int H, int W, long long tiles, const MetricsTaps& taps,
                                  double param, const double* range_dev, double* part, hipStream_t s) {
     const long long wgs = tiles * 3 * B;
     if (!grid_ok(wgs)) return hipErrorInvalidValue;
@@ -33,7 +33,7 @@ static hipError_t launch_moments(const MetricsView& p, const MetricsView& t, int
 }
 
 template <int E, int T>
-static hipError_t launch_down(const MetricsView& p, const MetricsView& t, int B, int Ho, int Wo, double* outp, double* outt, hipStream_t s) {
+static hipError_t launch_down(const StridedView& p, const StridedView& t, int B, int Ho, int Wo, double* outp, double* outt, hipStream_t s) {
     const long long blocks = ((long long)Ho * Wo + kMetricsThreads - 1) / kMetricsThreads;
     const long long wgs = blocks * 3 * B;
     if (!grid_ok(wgs)) return hipErrorInvalidValue;
@@ -42,8 +42,8 @@ static hipError_t launch_down(const MetricsView& p, const MetricsView& t, int B,
     return hipGetLastError();
 }
 
-static MetricsView dense_f64(const double* data, int h, int w) {
-    return MetricsView{data, {3LL * h * w, (long long)h * w, w, 1}};
+static StridedView dense_f64(const double* data, int h, int w) {
+    return StridedView{data, {3LL * h * w, (long long)h * w, w, 1}};
 }
 
 template <int E> static hipError_t launch_metrics_e(const MetricsArgs& a, hipStream_t s) {
@@ -74,17 +74,17 @@ template <int E> static hipError_t launch_metrics_e(const MetricsArgs& a, hipStr
             pyr[k][0] = (double*)(a.ws + pl.off_pyr[k]);
             pyr[k][1] = pyr[k][0] + (size_t)a.B * 3 * pl.vif_h[k] * pl.vif_w[k];
         }
-        const MetricsView p1 = dense_f64(pyr[1][0], pl.vif_h[1], pl.vif_w[1]), t1 = dense_f64(pyr[1][1], pl.vif_h[1], pl.vif_w[1]);
-        const MetricsView p2 = dense_f64(pyr[2][0], pl.vif_h[2], pl.vif_w[2]), t2 = dense_f64(pyr[2][1], pl.vif_h[2], pl.vif_w[2]);
-        const MetricsView p3 = dense_f64(pyr[3][0], pl.vif_h[3], pl.vif_w[3]), t3 = dense_f64(pyr[3][1], pl.vif_h[3], pl.vif_w[3]);
+        const StridedView p1 = dense_f64(pyr[1][0], pl.vif_h[1], pl.vif_w[1]), t1 = dense_f64(pyr[1][1], pl.vif_h[1], pl.vif_w[1]);
+        const StridedView p2 = dense_f64(pyr[2][0], pl.vif_h[2], pl.vif_w[2]), t2 = dense_f64(pyr[2][1], pl.vif_h[2], pl.vif_w[2]);
+        const StridedView p3 = dense_f64(pyr[3][0], pl.vif_h[3], pl.vif_w[3]), t3 = dense_f64(pyr[3][1], pl.vif_h[3], pl.vif_w[3]);
         if ((e = launch_down<E, 9>(a.pred, a.target, a.B, pl.vif_h[1], pl.vif_w[1], pyr[1][0], pyr[1][1], s)) != hipSuccess) return e;
-        if ((e = launch_moments<ME_F64, 9, EPI_VIF>(p1, t1, a.B, pl.vif_h[1], pl.vif_w[1], pl.vif_tiles[1], gaussian_taps(9, 9 / 5.0), a.sigma_n_sq,
+        if ((e = launch_moments<EL_F64, 9, EPI_VIF>(p1, t1, a.B, pl.vif_h[1], pl.vif_w[1], pl.vif_tiles[1], gaussian_taps(9, 9 / 5.0), a.sigma_n_sq,
                                                     nullptr, (double*)(a.ws + pl.off_vif[1]), s)) != hipSuccess) return e;
-        if ((e = launch_down<ME_F64, 5>(p1, t1, a.B, pl.vif_h[2], pl.vif_w[2], pyr[2][0], pyr[2][1], s)) != hipSuccess) return e;
-        if ((e = launch_moments<ME_F64, 5, EPI_VIF>(p2, t2, a.B, pl.vif_h[2], pl.vif_w[2], pl.vif_tiles[2], gaussian_taps(5, 5 / 5.0), a.sigma_n_sq,
+        if ((e = launch_down<EL_F64, 5>(p1, t1, a.B, pl.vif_h[2], pl.vif_w[2], pyr[2][0], pyr[2][1], s)) != hipSuccess) return e;
+        if ((e = launch_moments<EL_F64, 5, EPI_VIF>(p2, t2, a.B, pl.vif_h[2], pl.vif_w[2], pl.vif_tiles[2], gaussian_taps(5, 5 / 5.0), a.sigma_n_sq,
                                                     nullptr, (double*)(a.ws + pl.off_vif[2]), s)) != hipSuccess) return e;
-        if ((e = launch_down<ME_F64, 3>(p2, t2, a.B, pl.vif_h[3], pl.vif_w[3], pyr[3][0], pyr[3][1], s)) != hipSuccess) return e;
-        if ((e = launch_moments<ME_F64, 3, EPI_VIF>(p3, t3, a.B, pl.vif_h[3], pl.vif_w[3], pl.vif_tiles[3], gaussian_taps(3, 3 / 5.0), a.sigma_n_sq,
+        if ((e = launch_down<EL_F64, 3>(p2, t2, a.B, pl.vif_h[3], pl.vif_w[3], pyr[3][0], pyr[3][1], s)) != hipSuccess) return e;
+        if ((e = launch_moments<EL_F64, 3, EPI_VIF>(p3, t3, a.B, pl.vif_h[3], pl.vif_w[3], pl.vif_tiles[3], gaussian_taps(3, 3 / 5.0), a.sigma_n_sq,
                                                     nullptr, (double*)(a.ws + pl.off_vif[3]), s)) != hipSuccess) return e;
     }
     if (a.which & (MET_SSIM | MET_VIF)) {
@@ -106,13 +106,7 @@ template <int E> static hipError_t launch_metrics_e(const MetricsArgs& a, hipStr
 }
 
 hipError_t launch_metrics(const MetricsArgs& a, hipStream_t s) {
-    switch (a.elem) {
-        case ME_F32: return launch_metrics_e<ME_F32>(a, s);
-        case ME_BF16: return launch_metrics_e<ME_BF16>(a, s);
-        case ME_F16: return launch_metrics_e<ME_F16>(a, s);
-        case ME_U8: return launch_metrics_e<ME_U8>(a, s);
-        default: return hipErrorInvalidValue;
-    }
+    return for_elem(a.elem, [&](auto e) { return launch_metrics_e<decltype(e)::value>(a, s); });
 }
 
 }  // namespace mz

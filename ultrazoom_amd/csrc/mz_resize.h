@@ -29,6 +29,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "mz_view.h"
+
 namespace mz {
 
 constexpr int kResizeTileH = 8;    // output pixels of one resize_kernel workgroup
@@ -38,7 +40,6 @@ constexpr int kResizeMaxRatio = 16;  // n_in / n_out beyond this is refused: bou
 constexpr int kResizeMaxTaps = 66;
 
 enum ResizeFilter : int { RF_BICUBIC = 0, RF_BILINEAR = 1 };
-enum ResizeElem : int { RE_F32 = 0, RE_BF16 = 1, RE_F16 = 2, RE_U8 = 3 };
 
 // f(u) of the table above
 __host__ __device__ inline double resize_filter(int filter, double u) {
@@ -110,13 +111,9 @@ inline ResizePlan resize_plan(int Hin, int Win, int Hout, int Wout, int filter) 
     return p;
 }
 
-struct ResizeView {
-    const void* data;  // element (image 0, channel 0, row 0, column 0); of the output: the window's first element
-    long long s[4];    // element strides: image, channel, row, column
-};
 struct ResizeArgs {
-    ResizeView x, out;
-    int elem;                  // ResizeElem
+    StridedView x, out;
+    int elem;                  // Elem 0..3
     int B, Hin, Win, Hout, Wout;
     int filter, clamp;
     int y0, x0, h, w;          // the window of the Hout x Wout result that is computed and stored
@@ -127,23 +124,6 @@ struct ResizeArgs {
 hipError_t launch_resize(const ResizeArgs& a, hipStream_t s);
 
 #ifdef MZ_RESIZE_KERNELS  // mz_resize.hip only: the host runtime includes the plan above without the device code
-
-template <int E> __device__ __forceinline__ float ld_resize(const void* base, long long i) {
-    if constexpr (E == RE_F32) return ((const float*)base)[i];
-    else if constexpr (E == RE_BF16) return __builtin_bit_cast(float, (uint32_t)((const uint16_t*)base)[i] << 16);
-    else if constexpr (E == RE_F16) return (float)((const _Float16*)base)[i];
-    else return (float)((const uint8_t*)base)[i] / 255.0f;  // a true division, as mz_forward_u8's read
-}
-template <int E> __device__ __forceinline__ void st_resize(void* base, long long i, float v, int clamp) {
-    if constexpr (E == RE_U8) {
-        ((uint8_t*)base)[i] = (uint8_t)fminf(fmaxf(v * 255.0f + 0.5f, 0.0f), 255.0f);  // exactly mz_forward_u8's store
-    } else {
-        if (clamp) v = fminf(fmaxf(v, 0.0f), 1.0f);
-        if constexpr (E == RE_F32) ((float*)base)[i] = v;
-        else if constexpr (E == RE_BF16) ((__bf16*)base)[i] = (__bf16)v;
-        else ((_Float16*)base)[i] = (_Float16)v;
-    }
-}
 
 // grid: ceil((Wout + Hout) / 256): thread t < Wout is output column t, the next Hout threads are the output rows
 __global__ __launch_bounds__(kResizeThreads) void resize_table_kernel(int Hin, int Win, int Hout, int Wout, int filter, int taps_x, int taps_y,
@@ -163,7 +143,7 @@ __global__ __launch_bounds__(kResizeThreads) void resize_table_kernel(int Hin, i
 
 // grid: tiles * 3 * B workgroups, tile fastest (tiles of the window, row by row); dynamic LDS: ResizePlan::lds_bytes
 template <int E>
-__global__ __launch_bounds__(kResizeThreads) void resize_kernel(const ResizeView x, const ResizeView out, int y0, int x0, int h, int w,
+__global__ __launch_bounds__(kResizeThreads) void resize_kernel(const StridedView x, const StridedView out, int y0, int x0, int h, int w,
                                                                   long long tiles, int tiles_x, int clamp, int taps_x, int taps_y, int rows_cap,
                                                                   const int* span_x, const double* w_x, const int* span_y, const double* w_y) {
     constexpr int TH = kResizeTileH, TW = kResizeTileW;
@@ -214,7 +194,7 @@ __global__ __launch_bounds__(kResizeThreads) void resize_kernel(const ResizeView
             const long long o = (long long)j * x.s[3];
             float v[4];
 #pragma unroll
-            for (int k = 0; k < 4; ++k) v[k] = ld_resize<E>(x.data, at[k] + o);
+            for (int k = 0; k < 4; ++k) v[k] = ld_f32<E>(x.data, at[k] + o);
 #pragma unroll
             for (int k = 0; k < 4; ++k) acc[k] = fma(wj, (double)v[k], acc[k]);
         }
@@ -229,7 +209,7 @@ __global__ __launch_bounds__(kResizeThreads) void resize_kernel(const ResizeView
         const float* col = hrow + (fy - row0) * TW + tx;
         double acc = 0.0;
         for (int j = 0; j < cy; ++j) acc = fma(wys[j * TH + ty], (double)col[j * TW], acc);
-        st_resize<E>((void*)out.data, b * out.s[0] + c * out.s[1] + (long long)wy_ * out.s[2] + (long long)wx_ * out.s[3], (float)acc, clamp);
+        st_f32<E>((void*)out.data, b * out.s[0] + c * out.s[1] + (long long)wy_ * out.s[2] + (long long)wx_ * out.s[3], (float)acc, clamp);
     }
 }
 

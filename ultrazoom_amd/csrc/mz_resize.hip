@@ -26,13 +26,7 @@ template <int E> static hipError_t launch_resize_e(const ResizeArgs& a, hipStrea
 }
 
 hipError_t launch_resize(const ResizeArgs& a, hipStream_t s) {
-    switch (a.elem) {
-        case RE_F32: return launch_resize_e<RE_F32>(a, s);
-        case RE_BF16: return launch_resize_e<RE_BF16>(a, s);
-        case RE_F16: return launch_resize_e<RE_F16>(a, s);
-        case RE_U8: return launch_resize_e<RE_U8>(a, s);
-        default: return hipErrorInvalidValue;
-    }
+    return for_elem(a.elem, [&](auto e) { return launch_resize_e<decltype(e)::value>(a, s); });
 }
 
 }  // namespace mz

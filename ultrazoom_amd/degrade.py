@@ -17,30 +17,9 @@ from torch import Tensor
 
 from . import _ffi
 
-_ELEM = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2, torch.uint8: 3}
 _M64 = 2**64 - 1
 BLUR_MAX_HALF = 15  # int(3 sigma) beyond this is refused (include/mewzoom_hip.h)
 PARAMETER_STREAM = _M64  # the stream id `Degradation.sample` draws from; noise uses stream ids offset + b
-
-
-def _check(x: Tensor, out: Optional[Tensor], what: str) -> Tuple[int, int, int]:
-    if x.dim() != 4 or x.shape[1] != 3:
-        raise ValueError(f"expected a [B, 3, H, W] tensor, got {tuple(x.shape)}")
-    if x.dtype not in _ELEM:
-        raise TypeError(f"unsupported dtype {x.dtype}; use float32, bfloat16, float16 or uint8")
-    if not x.is_cuda:
-        raise RuntimeError(f"ultrazoom_amd.{what} computes on an MI355X only: move the image to a 'cuda' device. There is no CPU path.")
-    B, _, H, W = x.shape
-    if B < 1 or H < 1 or W < 1:
-        raise ValueError(f"an empty batch or image: {tuple(x.shape)}")
-    if out is not None:
-        if out.device != x.device:
-            raise RuntimeError(f"the input is on {x.device} but the output is on {out.device}")
-        if out.dtype != x.dtype:
-            raise TypeError(f"x ({x.dtype}) and out ({out.dtype}) should have the same dtype")
-        if tuple(out.shape) != tuple(x.shape):
-            raise ValueError(f"the output has shape {tuple(out.shape)}, expected {tuple(x.shape)}")
-    return B, H, W
 
 
 def _per_image(value, B: int, name: str) -> Optional[list]:
@@ -69,7 +48,7 @@ def gaussian_blur(x: Tensor, sigma: Union[float, Sequence[float]], out: Optional
     [B, 3, H, W] CUDA tensor: reflect padding, weights and both passes in float64.  `sigma` is a scalar or one value per image (one
     call per image on a view of it).  Returns a new dense tensor of x's dtype, or `out` (any strides).  sigma < 1 / 3 copies;
     int(3 sigma) must stay below min(H, W) and at most 15.  x and out must not overlap."""
-    B, H, W = _check(x, out, "gaussian_blur")
+    elem, B, H, W = _ffi.check_image_batch(x, "gaussian_blur", out)
     sigmas = _per_image(sigma, B, "sigma")
     for s in ([sigma] if sigmas is None else sigmas):
         s = float(s)
@@ -81,7 +60,7 @@ def gaussian_blur(x: Tensor, sigma: Union[float, Sequence[float]], out: Optional
         stream = torch.cuda.current_stream(x.device).cuda_stream
         if out is None:
             out = torch.empty(x.shape, dtype=x.dtype, device=x.device)
-        _run(x, out, sigmas, lambda xv, ov, n, s, b: _ffi.blur(xv.data_ptr(), xv.stride(), ov.data_ptr(), ov.stride(), _ELEM[x.dtype], n, H, W,
+        _run(x, out, sigmas, lambda xv, ov, n, s, b: _ffi.blur(xv.data_ptr(), xv.stride(), ov.data_ptr(), ov.stride(), elem, n, H, W,
                                                               float(sigma if s is None else s), stream))
     return out
 
@@ -90,7 +69,7 @@ def gaussian_noise(x: Tensor, sigma: Union[float, Sequence[float]], *, seed: int
     """torchvision's `gaussian_noise(x, mean=0, sigma=sigma, clip=True)` on the [0, 1] scale: clamp(x + sigma n, 0, 1) in float64, n from
     the library's Philox stream: image b of the call draws from stream `offset + b` of `seed`, element by element, so a batch split
     into calls (image b with offset + b) gives the bits of the one call.  `out=x` works in place."""
-    B, H, W = _check(x, out, "gaussian_noise")
+    elem, B, H, W = _ffi.check_image_batch(x, "gaussian_noise", out)
     sigmas = _per_image(sigma, B, "sigma")
     for s in ([sigma] if sigmas is None else sigmas):
         if not 0.0 <= float(s) <= 1e6:
@@ -99,7 +78,7 @@ def gaussian_noise(x: Tensor, sigma: Union[float, Sequence[float]], *, seed: int
         stream = torch.cuda.current_stream(x.device).cuda_stream
         if out is None:
             out = torch.empty(x.shape, dtype=x.dtype, device=x.device)
-        _run(x, out, sigmas, lambda xv, ov, n, s, b: _ffi.noise(xv.data_ptr(), xv.stride(), ov.data_ptr(), ov.stride(), _ELEM[x.dtype], n, H, W,
+        _run(x, out, sigmas, lambda xv, ov, n, s, b: _ffi.noise(xv.data_ptr(), xv.stride(), ov.data_ptr(), ov.stride(), elem, n, H, W,
                                                                float(sigma if s is None else s), seed, int(offset) + b, stream))
     return out
 
@@ -108,7 +87,7 @@ def jpeg(x: Tensor, quality: Union[int, Sequence[int]], out: Optional[Tensor] = 
     """A baseline JPEG round trip (4:2:0, the Annex K tables scaled by `quality` 1..100) of a logical [B, 3, H, W] CUDA tensor, modelled in
     arithmetic on the device: what torchvision's `jpeg(x, quality)` does through a codec, without one.  `quality` is a scalar or one
     value per image.  x and out must not overlap."""
-    B, H, W = _check(x, out, "jpeg")
+    elem, B, H, W = _ffi.check_image_batch(x, "jpeg", out)
     qualities = _per_image(quality, B, "quality")
     for q in ([quality] if qualities is None else qualities):
         if int(q) != q or not 1 <= int(q) <= 100:
@@ -119,7 +98,7 @@ def jpeg(x: Tensor, quality: Union[int, Sequence[int]], out: Optional[Tensor] = 
         ws = torch.empty(need, dtype=torch.uint8, device=x.device)  # calls on one stream run one after the other: one workspace serves all
         if out is None:
             out = torch.empty(x.shape, dtype=x.dtype, device=x.device)
-        _run(x, out, qualities, lambda xv, ov, n, q, b: _ffi.jpeg(xv.data_ptr(), xv.stride(), ov.data_ptr(), ov.stride(), _ELEM[x.dtype], n, H, W,
+        _run(x, out, qualities, lambda xv, ov, n, q, b: _ffi.jpeg(xv.data_ptr(), xv.stride(), ov.data_ptr(), ov.stride(), elem, n, H, W,
                                                                  int(quality if q is None else q), ws.data_ptr(), need, stream))
     return out
 
@@ -182,16 +161,12 @@ class Degradation:
         and the normalised parameters as a float32 [B, 3] tensor on hr's device.  The noise of image b is stream index + b of `seed`."""
         from .evaluate import lr_from_hr
 
-        if hr.dim() != 4 or hr.shape[1] != 3:
-            raise ValueError(f"expected a [B, 3, H, W] tensor, got {tuple(hr.shape)}")
-        if not hr.is_cuda:
-            raise RuntimeError("ultrazoom_amd.Degradation.apply computes on an MI355X only: move the image to a 'cuda' device. There is no CPU path.")
+        _, B, H, W = _ffi.check_image_batch(hr, "Degradation.apply")
         ratio = int(ratio)
-        if ratio < 1 or hr.shape[-2] < ratio or hr.shape[-1] < ratio:
+        if ratio < 1 or H < ratio or W < ratio:
             raise ValueError(f"expected a [B, 3, H, W] tensor of at least {ratio} x {ratio} pixels, got {tuple(hr.shape)}")
-        B = hr.shape[0]
         params = self.sample(B, index)
-        h, w = hr.shape[-2] // ratio, hr.shape[-1] // ratio
+        h, w = H // ratio, W // ratio
         cropped = hr[..., : h * ratio, : w * ratio]
         x = gaussian_blur(cropped, [p[0] for p in params])
         gaussian_noise(x, [p[1] for p in params], seed=self.seed, offset=index, out=x)

@@ -16,7 +16,6 @@ from torch import Tensor
 from . import _ffi
 
 _BITS = {"psnr": _ffi.MZ_METRIC_PSNR, "ssim": _ffi.MZ_METRIC_SSIM, "vif": _ffi.MZ_METRIC_VIF}
-_ELEM = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2, torch.uint8: 3}
 
 
 def image_metrics(pred: Tensor, target: Tensor, *, which: Iterable[str] = ("psnr", "ssim", "vif"), data_range: Optional[float] = None,
@@ -30,19 +29,7 @@ def image_metrics(pred: Tensor, target: Tensor, *, which: Iterable[str] = ("psnr
     unknown = [w for w in which if w not in _BITS]
     if unknown or not which:
         raise ValueError(f"which holds names out of 'psnr', 'ssim', 'vif', got {which}")
-    if not pred.is_cuda or not target.is_cuda:
-        raise RuntimeError("ultrazoom_amd.metrics computes on an MI355X only: move both images to a 'cuda' device. There is no CPU path.")
-    if pred.device != target.device:
-        raise RuntimeError(f"pred is on {pred.device} but target is on {target.device}")
-    if pred.shape != target.shape or pred.dim() != 4 or pred.shape[1] != 3:
-        raise ValueError(f"expected two [B, 3, H, W] tensors of one shape, got {tuple(pred.shape)} and {tuple(target.shape)}")
-    if pred.dtype != target.dtype:
-        raise TypeError(f"pred ({pred.dtype}) and target ({target.dtype}) should have the same dtype")
-    if pred.dtype not in _ELEM:
-        raise TypeError(f"unsupported dtype {pred.dtype}; use float32, bfloat16, float16 or uint8")
-    B, _, H, W = pred.shape
-    if B < 1:
-        raise ValueError("an empty batch")
+    elem, B, H, W = _ffi.check_image_batch(pred, "metrics", target, names=("pred", "target"))
     if "ssim" in which and min(H, W) < 11:
         raise ValueError(f"SSIM needs images of at least 11 x 11 pixels, got {(H, W)}")
     if "vif" in which and min(H, W) < 41:
@@ -53,7 +40,7 @@ def image_metrics(pred: Tensor, target: Tensor, *, which: Iterable[str] = ("psnr
         need = _ffi.metrics_workspace_bytes(B, H, W, bits)
         ws = torch.empty(need, dtype=torch.uint8, device=pred.device)
         out = torch.zeros((B, _ffi.MZ_METRIC_SLOTS), dtype=torch.float64, device=pred.device)
-        _ffi.metrics(pred.data_ptr(), pred.stride(), target.data_ptr(), target.stride(), _ELEM[pred.dtype], B, H, W, bits,
+        _ffi.metrics(pred.data_ptr(), pred.stride(), target.data_ptr(), target.stride(), elem, B, H, W, bits,
                      -1.0 if data_range is None else float(data_range), float(sigma_n_sq), out.data_ptr(), ws.data_ptr(), need,
                      stream.cuda_stream)
     res = {}

@@ -16,7 +16,6 @@ from torch import Tensor
 from . import _ffi
 
 _FILTERS = {"bicubic": _ffi.MZ_RESIZE_BICUBIC, "bilinear": _ffi.MZ_RESIZE_BILINEAR}
-_ELEM = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2, torch.uint8: 3}
 MAX_RATIO = 16  # an axis shrinks at most this much in one call (include/mewzoom_hip.h)
 
 
@@ -30,18 +29,10 @@ def resize(x: Tensor, size: Tuple[int, int], *, filter: str = "bicubic", clamp: 
     axis may shrink by at most 16; enlarging is not bounded.  x and out must not overlap."""
     if filter not in _FILTERS:
         raise ValueError(f"filter is 'bicubic' or 'bilinear', got {filter!r}")
-    if x.dim() != 4 or x.shape[1] != 3:
-        raise ValueError(f"expected a [B, 3, H, W] tensor, got {tuple(x.shape)}")
-    if x.dtype not in _ELEM:
-        raise TypeError(f"unsupported dtype {x.dtype}; use float32, bfloat16, float16 or uint8")
-    if not x.is_cuda:
-        raise RuntimeError("ultrazoom_amd.resize computes on an MI355X only: move the image to a 'cuda' device. There is no CPU path.")
+    elem, B, H, W = _ffi.check_image_batch(x, "resize")
     size = tuple(int(v) for v in size)
     if len(size) != 2 or min(size) < 1:
         raise ValueError(f"size is (Hout, Wout) with both at least 1, got {size}")
-    B, _, H, W = x.shape
-    if B < 1 or H < 1 or W < 1:
-        raise ValueError(f"an empty batch or image: {tuple(x.shape)}")
     Hout, Wout = size
     if H > MAX_RATIO * Hout or W > MAX_RATIO * Wout:
         raise ValueError(f"{(H, W)} -> {size} shrinks an axis by more than {MAX_RATIO}: resize in two steps")
@@ -56,18 +47,13 @@ def resize(x: Tensor, size: Tuple[int, int], *, filter: str = "bicubic", clamp: 
             raise ValueError(f"window {window} is empty or not inside the {Hout} x {Wout} result")
         want = (B, 3, h, w)
     if out is not None:
-        if out.device != x.device:
-            raise RuntimeError(f"the input is on {x.device} but the output is on {out.device}")
-        if out.dtype != x.dtype:
-            raise TypeError(f"x ({x.dtype}) and out ({out.dtype}) should have the same dtype")
-        if tuple(out.shape) != want:
-            raise ValueError(f"the output has shape {tuple(out.shape)}, expected {want}")
+        _ffi.check_same_batch(x, out, want)
     with torch.cuda.device(x.device):
         stream = torch.cuda.current_stream(x.device)
         need = _ffi.resize_workspace_bytes(H, W, Hout, Wout, _FILTERS[filter])
         ws = torch.empty(need, dtype=torch.uint8, device=x.device)
         if out is None:
             out = torch.empty(want, dtype=x.dtype, device=x.device)
-        _ffi.resize(x.data_ptr(), x.stride(), out.data_ptr(), out.stride(), _ELEM[x.dtype], B, H, W, Hout, Wout, _FILTERS[filter], clamp,
+        _ffi.resize(x.data_ptr(), x.stride(), out.data_ptr(), out.stride(), elem, B, H, W, Hout, Wout, _FILTERS[filter], clamp,
                     window, ws.data_ptr(), need, stream.cuda_stream)
     return out
