@@ -1,0 +1,285 @@
+"""Exact-arithmetic test data (tests/test_exact_cpu.py, tests/test_exact_gpu.py).  Needs no GPU.
+
+Integer-valued activations and weights whose partial sums stay below 2^24 are added without error in fp32 in ANY order, so a kernel's
+output must equal the float64 result rounded ONCE to the storage type, bit for bit, whatever its tile walk or K order.  This module
+builds, for every row of the table below, the inputs, the float64 reference (torch.nn.functional on float64, the crop / zero border and
+the pixel shuffle from oracle.mewzoom_oracle), the expected storage-type tensor (round_once) and the figures the CPU test holds every
+row to (absolute-product sums, maxima, the census of roundings and ties, the excluded share).
+
+Where an operator contains a transcendental (the sigmoid of the mix's gate; SiLU in the one family that exists only with SiLU), the
+data SATURATE it: for an argument t >= SAT_HI, e^-t < 2^-46 vanishes beside 1 in fp32 and the sigmoid is exactly 1; for t <= SAT_LO,
+e^-t overflows fp32 and the sigmoid is exactly 0.  Elements in between are excluded from the equality (at most MAX_EXCLUDED of a row)
+and compared with the one-operator tolerance instead."""
+
+from __future__ import annotations
+
+import functools
+import math
+from collections import namedtuple
+
+import numpy as np
+import torch
+import torch.nn.functional as F
+
+from gpu_util import DTYPES
+from oracle import mewzoom_oracle as oracle
+from test_poison_ops_gpu import CASES
+
+SAT_HI, SAT_LO = 32.0, -100.0
+MAX_EXCLUDED = 0.02
+MIN_BRANCH = 0.30
+EXACT_SUM = float(2 ** 24)  # integers below it are fp32 values; a sum of absolute products below it bounds every partial sum
+F16_MAX_OUT = 32768.0
+AW = 7            # 3x3 / 2x2 weights: integers in [-AW, AW]
+GATE_SCALE = 16   # gate weights: integers times 16 (exact in bf16 and f16); the gate then leaves (SAT_LO, SAT_HI) almost everywhere
+# the largest integer magnitude below which EVERY integer is a value of the type (activations must be stored exactly)
+INT_MAX = {"f32": 2047, "bf16": 255, "f16": 2047}
+# f16 rounds integers only from 2048 on: rows of that type (and the SiLU row, whose window (SAT_LO, SAT_HI) must be a small share of
+# the output's spread) get activations large enough for an output standard deviation of about SIGMA; |max| stays below 32768 = 9 SIGMA
+SIGMA = 3600.0
+
+# (entry, arguments, environment knobs, dtype, expected mz_debug_last_kernel() or None, silu)
+Row = namedtuple("Row", "entry args env dt kernel silu")
+PERSISTENT = {"conv3p", "conv3s", "conv3s_fused", "conv3r", "conv3r_8x40", "conv3r_ragged", "conv3r_fused", "conv3t", "conv3t_fused", "mix16b"}
+
+
+def _rows():
+    """tests/test_poison_ops_gpu.CASES (the smallest shapes at which each family is chosen, pinned by the MZ_* knobs), conv and film
+    with silu = 0 -- SiLU is not exact --, plus two shapes of this table's own.  conv3r's ragged variant exists only as conv1 + SiLU
+    (choose_conv3, mz_host.cpp): its rows keep SiLU, on data that saturate it, and run once more without, on whatever family the host
+    then chooses."""
+    rows = []
+    for entry, args, env, dt, kernel in CASES:
+        if entry in ("conv", "film"):
+            if kernel == "conv3r_ragged":
+                rows.append(Row(entry, tuple(args[:5]) + (1,), env, dt, kernel, 1))
+                kernel = "conv3w"  # without SiLU: Cin = 48 pads a third of a second 32-channel chunk, too much for the 16x16x32 kernels
+            args = tuple(args[:5]) + (0,)
+        rows.append(Row(entry, tuple(args), env, dt, kernel, 0))
+    for dt in ("f32", "bf16", "f16"):
+        # Cin = 144: the last 32-channel chunk of the 16x16x32 kernels is half zero planes (the f32 row has no such chunk)
+        rows.append(Row("conv", (1, 20, 130, 144, 96, 0), {}, dt, "conv3w" if dt == "f32" else "conv3s", 0))
+        rows.append(Row("conv", (1, 5, 9, 160, 16, 0), {}, dt, "conv3w" if dt == "f32" else "conv3s", 0))
+    seen = {}
+    for r in rows:
+        seen.setdefault(row_id(r), r)
+    return list(seen.values())
+
+
+def row_id(r: Row) -> str:
+    return "-".join([r.entry, "x".join(str(v) for v in r.args), r.dt] + (["silu"] if r.silu else []) + [f"{k[3:]}={v}" for k, v in r.env.items()])
+
+
+# ---- integer tensors --------------------------------------------------------------------------------------------------------------
+def ints(shape, a: int, seed: int, scale: float = 1.0) -> torch.Tensor:
+    """Seeded integers of [-a, a] (times a power-of-two `scale`) as float32."""
+    g = torch.Generator().manual_seed(seed)
+    return torch.randint(-a, a + 1, tuple(shape), generator=g).float() * scale
+
+
+def choice(shape, values, seed: int) -> torch.Tensor:
+    g = torch.Generator().manual_seed(seed)
+    return torch.tensor(values, dtype=torch.float32)[torch.randint(0, len(values), tuple(shape), generator=g)]
+
+
+def conv_ax(nterms: int, dt: str, big: bool) -> int:
+    """Activation amplitude of a convolution over `nterms` products with weights of [-AW, AW].  ax = 15 where bf16 / f32 suffice
+    (outputs of a few hundred: bf16 rounds integers from 256 on).  `big` (f16, SiLU): the output's standard deviation, sqrt(nterms)
+    ax AW / 3 for uniform integers, reaches SIGMA."""
+    if not big:
+        return 15
+    return min(INT_MAX[dt], max(15, math.ceil(3.0 * SIGMA / (AW * math.sqrt(nterms)))))
+
+
+def gate_aw(c: int, mean_abs_x: float, mean_abs_z: float) -> int:
+    """Gate weights are GATE_SCALE * [-aw, aw]: the largest aw <= AW whose expected sum of absolute products over [x ; z] -- c terms each,
+    mean |w| = GATE_SCALE aw / 2 -- stays below half of 2^24: the largest sum over the pixels of a row lies well above the mean (the
+    CPU test checks the true maximum)."""
+    return max(1, min(AW, int(0.5 * EXACT_SUM / (c * GATE_SCALE * 0.5 * (mean_abs_x + mean_abs_z)))))
+
+
+# ---- one rounding, on the bit pattern -----------------------------------------------------------------------------------------------
+FORMAT = {"f32": (23, 127, 8), "bf16": (7, 127, 8), "f16": (10, 15, 5)}  # mantissa bits, exponent bias, exponent bits
+
+
+def _round_parts(y64: torch.Tensor, dt: str):
+    """(bit pattern of y rounded to nearest even in `dt`, inexact, exact tie, rounded away from zero) as numpy arrays.  Integer
+    arithmetic on the float64 bit pattern: 53-bit significand, shifted right by what the target cannot hold (more below its smallest
+    normal exponent), remainder against half."""
+    M, bias, ebits = FORMAT[dt]
+    emin = 1 - bias
+    a = np.ascontiguousarray(y64.detach().cpu().to(torch.float64).numpy())
+    assert np.isfinite(a).all()
+    bits = a.view(np.int64)
+    sign = (bits >> 63) & 1
+    e = (bits >> 52) & 0x7FF
+    assert not ((e == 0) & ((bits & ((1 << 52) - 1)) != 0)).any(), "float64 subnormals are not handled"
+    sig = (bits & ((1 << 52) - 1)) | (np.int64(1) << 52)
+    E = e - 1023
+    Et = np.maximum(E, emin)  # exponent of the target's leading bit position
+    shift = np.minimum(52 - M + (Et - E), 62)  # >= 54: everything is remainder, below half
+    q = sig >> shift
+    rem = sig & ((np.int64(1) << shift) - 1)
+    half = np.int64(1) << (shift - 1)
+    zero = e == 0
+    tie = (rem == half) & ~zero
+    up = ((rem > half) | (tie & ((q & 1) == 1))) & ~zero
+    inexact = (rem != 0) & ~zero
+    q = q + up
+    # normal: field = Et + bias, mantissa q - 2^M (q = 2^(M+1) carries into the field by itself); subnormal: field 0, mantissa q
+    normal = E >= emin
+    out = np.where(normal, ((Et + bias) << M) + (q - (1 << M)), q)
+    inf = ((1 << ebits) - 1) << M
+    out = np.where(out >= inf, inf, out)
+    out = np.where(zero, 0, out)
+    out = out | (sign << (M + ebits))
+    return out, inexact, tie, up
+
+
+def round_once(y64: torch.Tensor, dt: str) -> torch.Tensor:
+    """float64 -> `dt`, rounded to nearest even ONCE."""
+    out, _, _, _ = _round_parts(y64, dt)
+    if dt == "f32":
+        return torch.from_numpy(out.astype(np.uint32).view(np.int32)).view(torch.float32).reshape(y64.shape)
+    return torch.from_numpy(out.astype(np.uint16).view(np.int16)).view(DTYPES[dt]).reshape(y64.shape)
+
+
+def census(y64: torch.Tensor, dt: str):
+    """Shares of elements that (need rounding, are exact ties, round differently under truncation than under nearest-even)."""
+    _, inexact, tie, up = _round_parts(y64, dt)
+    n = max(1, inexact.size)
+    return inexact.sum() / n, tie.sum() / n, up.sum() / n
+
+
+def bits_of(t: torch.Tensor) -> torch.Tensor:
+    return t.contiguous().view(torch.int32 if t.dtype == torch.float32 else torch.int16)
+
+
+# ---- rows ---------------------------------------------------------------------------------------------------------------------------
+class Exact:
+    """One row's data: `inputs` (float32 CPU tensors by argument name, integer-valued or as the entry states), `alpha`, `C` (real
+    output channels; None: a dense image), `y64` (what is rounded), `want` (storage type), `keep` (None: every element is compared for
+    equality; else the mask of those that are), `soft64` (the float64 formula, for the excluded elements), `sums` (largest sum of
+    absolute products per accumulated quantity), `branches` (shares of the two saturated branches)."""
+
+    def __init__(self):
+        self.alpha, self.keep, self.soft64, self.sums, self.branches = 0.0, None, None, {}, None
+
+    @property
+    def excluded(self) -> float:
+        return 0.0 if self.keep is None else 1.0 - self.keep.double().mean().item()
+
+    def compared(self) -> torch.Tensor:
+        return self.y64 if self.keep is None else self.y64[self.keep]
+
+
+def _abs_sum(x, w, **kw):
+    return F.conv2d(x.abs(), w.abs(), **kw).max().item()
+
+
+def _saturate(ex: Exact, t64, one64, zero64, soft64):
+    """t: the transcendental's argument.  one64 / zero64: the result where the sigmoid is exactly 1 / exactly 0."""
+    hi, lo = t64 >= SAT_HI, t64 <= SAT_LO
+    ex.keep = hi | lo
+    ex.y64 = torch.where(hi, one64, zero64)
+    ex.soft64 = soft64
+    ex.branches = (hi.double().mean().item(), lo.double().mean().item())
+
+
+def _build(entry, args, dt, silu) -> Exact:
+    ex = Exact()
+    d = lambda t: t.double()
+    B, H, W = args[:3]
+    big = dt == "f16" or bool(silu)
+    if entry in ("conv", "film", "d2s", "crush"):
+        cin, cout = args[3:5]
+        k = 2 if entry == "crush" else 3
+        nterms = k * k * cin * (4 if entry == "film" else 1)  # film: |gamma| <= 2 doubles the spread, as four times the terms would
+        x, w = ints((B, cin, H, W), conv_ax(nterms, dt, big), 101), ints((cout, cin, k, k), AW, 102)
+        ex.inputs = {"in0": x, "w": w}
+        kw = {"stride": 2} if entry == "crush" else {"padding": 1}
+        ex.sums["conv"] = _abs_sum(d(x), d(w), **kw)
+        if entry == "d2s":
+            ex.C, ex.y64 = cout // 4, oracle.fit_to(oracle.subpixel_conv(d(x), d(w)), args[5:7])
+        elif entry == "film":
+            gamma, beta = choice((B, cout), [-1.0, 0.5, 1.0, 2.0], 103), ints((B, cout), 8, 104)
+            ex.inputs.update(gamma=gamma, beta=beta)
+            ex.C, ex.y64 = cout, oracle.film_conv(d(x), d(w), d(gamma), d(beta), False)
+            ex.sums["film"] = (F.conv2d(d(x).abs(), d(w).abs(), padding=1) * d(gamma).abs()[:, :, None, None] + d(beta).abs()[:, :, None, None]).max().item()
+        else:
+            ex.C, ex.y64 = cout, F.conv2d(d(x), d(w), **kw)
+            if silu:  # t >= SAT_HI: t * 1; t <= SAT_LO: t * 0
+                y = ex.y64
+                _saturate(ex, y, y, torch.zeros_like(y), F.silu(y))
+    elif entry == "stem":
+        c = args[3]
+        x = ints((B, 3, H, W), INT_MAX[dt], 105).abs()
+        w, b = choice((c, 3, 1, 1), [-2.0, -1.0, -0.5, 0.5, 1.0, 2.0], 106), ints((c,), 8, 107)
+        ex.inputs = {"x": x, "w": w, "b": b}
+        ex.C, ex.y64 = c, F.conv2d(d(x), d(w), d(b))
+        ex.sums["stem"] = F.conv2d(d(x), d(w).abs(), d(b).abs()).max().item()
+    elif entry == "final":
+        cin, R = args[3:5]
+        feat, w = ints((B, cin, H, W), conv_ax(9 * cin, dt, big), 108), ints((12, cin, 3, 3), AW, 109)
+        img = torch.zeros(B, 3, 2 * H // R, 2 * W // R)  # the bicubic term is exactly zero
+        ex.inputs = {"feat": feat, "img": img, "w": w}
+        ex.C, ex.y64 = None, oracle.bicubic_upsample(d(img), R) + oracle.subpixel_conv(d(feat), d(w))
+        ex.sums["conv"] = _abs_sum(d(feat), d(w), padding=1)
+    elif entry in ("mix", "conv_mix"):
+        ax = INT_MAX[dt]  # x: every integer the type holds
+        if entry == "mix":
+            c = args[3]
+            # z: multiples of 4, so that (x + z) / 2 = x / 2 + 2 zi needs rounding (exact, tie or neither by x mod 4) in both 16-bit types
+            az = 255 if dt == "bf16" else 511
+            x, z = ints((B, c, H, W), ax, 110), ints((B, c, H, W), az, 111, 4.0)
+            ex.inputs = {"in0": x, "in1": z}
+            z64, wname, mean_z = d(z), "w", 2.0 * az
+        else:
+            cin, c = args[3:5]
+            hid, x, w2 = ints((B, cin, H, W), conv_ax(9 * cin, dt, big), 112), ints((B, c, H, W), ax, 113), ints((c, cin, 3, 3), AW, 114)
+            ex.inputs = {"hid": hid, "x": x, "w2": w2}
+            ex.sums["conv"] = _abs_sum(d(hid), d(w2), padding=1)
+            ex.z64_unrounded = F.conv2d(d(hid), d(w2), padding=1)
+            # z is rounded to the storage type BEFORE the gate GEMM and the blend, as the unfused path stores it
+            z64, wname = round_once(ex.z64_unrounded, dt).double(), "wmix"
+            mean_z = 0.8 * math.sqrt(9 * cin) * conv_ax(9 * cin, dt, big) * AW / 3.0  # E|z| of a normal variable
+        wmix = ints((c, 2 * c, 1, 1), gate_aw(c, ax / 2.0, mean_z), 115, float(GATE_SCALE))
+        ex.inputs[wname] = wmix
+        ex.C = c
+        xz = torch.cat([d(x), z64], dim=1)
+        gate = F.conv2d(xz, d(wmix))
+        ex.sums["gate"] = _abs_sum(xz, d(wmix))
+        ex.sums["blend"] = (d(x).abs() + z64.abs()).max().item()
+        # alpha = 0: sigmoid(alpha) = 1/2 and the host's 1 + e^-alpha = 2 are exact
+        _saturate(ex, gate, (d(x) + z64) / 2, d(x), d(x) + 0.5 * torch.sigmoid(gate) * (z64 - d(x)))
+        ex.z64 = z64
+    else:
+        raise ValueError(entry)
+    ex.want = round_once(ex.y64, dt)
+    return ex
+
+
+@functools.lru_cache(maxsize=None)
+def _cached(entry, args, dt, silu):
+    return _build(entry, args, dt, silu)
+
+
+def exact(r: Row) -> Exact:
+    """The row's data, built once (rows that differ in their knobs share it) and never changed."""
+    return _cached(r.entry, r.args, r.dt, r.silu)
+
+
+ROWS = _rows()
+
+# Persistent families once more under MZ_PERSIST_WGS = 8 and 16 (on these shapes a workgroup then walks several tiles, in two different
+# splits).  Rows whose tiles do not outnumber the workgroups fall back to a per-tile family under that knob and are left out:
+# tests/test_exact_cpu.py checks that every walk listed here keeps its row's family.
+WALK_WGS = (8, 16)
+NOT_PERSISTENT_AT_16 = {(1, 20, 130, 112, 96, 0)}  # conv3p: nine 8 x 64 tiles do not outnumber 16 workgroups
+WALKS = [(r, n) for r in ROWS for n in WALK_WGS
+         if r.kernel in PERSISTENT and "MZ_NO_PERSIST" not in r.env and r.env.get("MZ_PERSIST_WGS") != str(n)
+         and not (n == 16 and r.kernel == "conv3p" and r.args in NOT_PERSISTENT_AT_16)]
+
+
+def walk_id(w) -> str:
+    return f"{row_id(w[0])}-walk{w[1]}"
