@@ -46,7 +46,7 @@ PERSISTENT = {"conv3p", "conv3s", "conv3s_fused", "conv3r", "conv3r_8x40", "conv
 def _rows():
     """tests/test_poison_ops_gpu.CASES (the smallest shapes at which each family is chosen, pinned by the MZ_* knobs), conv and film
     with silu = 0 -- SiLU is not exact --, plus two shapes of this table's own.  conv3r's ragged variant exists only as conv1 + SiLU
-    (choose_conv3, mz_host.cpp): its rows keep SiLU, on data that saturate it, and run once more without, on whatever family the host
+    (choose_conv3, mz_select.h): its rows keep SiLU, on data that saturate it, and run once more without, on whatever family the host
     then chooses."""
     rows = []
     for entry, args, env, dt, kernel in CASES:

@@ -103,8 +103,8 @@ def test_weights_cannot_be_set_without_a_gpu():
     ],
 )
 def test_tile_list_lists_every_tile_once(geom):
-    """The tile list the role-alternating kernels walk (mz_host.cpp: tile_list(), uploaded by Runner::tile_table(); the walk's groups_m and
-    grid come from set_walk(), which pick_order() uses for a launch): every (image, tile row, tile column, N tile) exactly once, tile
+    """The tile list the role-alternating kernels walk (mz_select.h: tile_list(), uploaded by Runner::tile_table(); the walk's groups_m and
+    grid come from group_walk(), which pick_order() uses for a launch): every (image, tile row, tile column, N tile) exactly once, tile
     origins on the tile grid, and the N tiles of a group's pixel tile next to each other."""
     B, ty, tx, ntiles, gm, gn, blk4, th, tw = geom
     lib = ctypes.CDLL(str(_ffi.LIB_PATH))

@@ -53,7 +53,7 @@ R_CASES = [
 
 
 def expected_r_kernel(H, W):
-    """The host's choice (mz_host.cpp, choose_conv3 on the Conv3Call of a plain 3x3 layer): conv3r_kernel in the tile geometry that pads
+    """The host's choice (mz_select.h, choose_conv3 on the Conv3Call of a plain 3x3 layer): conv3r_kernel in the tile geometry that pads
     fewer pixels (8 x 40 or 8 x 48), unless conv3s_kernel's 8 x 64 / 16 x 32 tiles pad fewer still."""
     up = lambda v, m: -(-v // m) * m
     pads = min(up(H, 8) * up(W, 64), up(H, 16) * up(W, 32))

@@ -103,9 +103,9 @@ def test_the_row_s_conditions(row):
 
 
 def test_the_table_names_every_kernel_family():
-    """Every literal kernel_name() (mz_host.cpp) can return is the pinned family of some row."""
-    src = (Path(__file__).resolve().parent.parent / "ultrazoom_amd" / "csrc" / "mz_host.cpp").read_text()
-    body = re.search(r"static const char\* kernel_name\(const KernelChoice& ch\) \{(.*?)\n\}\n", src, re.S).group(1)
+    """Every literal kernel_name() (mz_select.h) can return is the pinned family of some row."""
+    src = (Path(__file__).resolve().parent.parent / "ultrazoom_amd" / "csrc" / "mz_select.h").read_text()
+    body = re.search(r"inline const char\* kernel_name\(const KernelChoice& ch\) \{(.*?)\n\}\n", src, re.S).group(1)
     body = re.sub(r"//[^\n]*", "", body)
     names = set(re.findall(r'"([a-z0-9_]+)"', body))
     assert len(names) >= 15 and {"conv3r", "conv3t_fused", "mix16b", "conv_kernel_mix"} <= names, names

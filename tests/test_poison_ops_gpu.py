@@ -102,10 +102,10 @@ def case_id(case):
 
 
 def test_the_case_table_names_every_kernel_family():
-    """Needs no GPU: every literal kernel_name() (mz_host.cpp) can return is the expected kernel of some row, so that a family added
+    """Needs no GPU: every literal kernel_name() (mz_select.h) can return is the expected kernel of some row, so that a family added
     later cannot be forgotten here."""
-    src = (Path(__file__).resolve().parent.parent / "ultrazoom_amd" / "csrc" / "mz_host.cpp").read_text()
-    body = re.search(r"static const char\* kernel_name\(const KernelChoice& ch\) \{(.*?)\n\}\n", src, re.S).group(1)
+    src = (Path(__file__).resolve().parent.parent / "ultrazoom_amd" / "csrc" / "mz_select.h").read_text()
+    body = re.search(r"inline const char\* kernel_name\(const KernelChoice& ch\) \{(.*?)\n\}\n", src, re.S).group(1)
     body = re.sub(r"//[^\n]*", "", body)  # (a comment quotes names, too)
     names = set(re.findall(r'"([a-z0-9_]+)"', body))
     assert len(names) >= 15 and {"conv3r", "conv3t_fused", "mix16b", "conv_kernel_mix"} <= names, names

@@ -1,4 +1,4 @@
-"""Which kernel every 3x3 convolution and mix of the model gets (mz_host.cpp: choose_conv3 / choose_mix), read without a GPU through
+"""Which kernel every 3x3 convolution and mix of the model gets (mz_select.h: choose_conv3 / choose_mix), read without a GPU through
 mz_debug_select().  That entry only maps its op code to a layer role; the role functions (conv1_call, conv2_call, d2s_call, ..) then
 describe the call, a Conv3Call, exactly as they do for mz_forward and the mz_op_* entries, so a row here exercises the code the model
 runs.  The expected names are those mz_debug_last_kernel() reported for these layers when the selection was spread over the
@@ -358,3 +358,27 @@ def test_refusals_say_why(monkeypatch):
     # conv3r's tile list holds pixel coordinates in 16 bits
     got, err = _select(monkeypatch, BF16, CONV1, 96, 192, 1, 16, 70000)
     assert got is None and "16 bits" in err
+
+
+def test_planning_and_selection_survive_the_sanitizers(tmp_path):
+    """tests/select_main.cpp -- the layers of TABLE and channel counts around every tile and chunk boundary, 8 x 8 to 4320 x 7680 pixels,
+    1 to 64 images, 0 / 8 / 256 CUs: plans, choices, walks, tile lists (every tile exactly once) and workspace plans -- built from
+    mz_plan.h and mz_select.h alone with the address and undefined-behaviour sanitizers: a signed overflow in a tile count or an offset
+    guard ends it.  A stand-alone host program: nothing of it is loaded here, nothing of HIP is linked."""
+    import os
+    import shutil
+    import subprocess
+    from pathlib import Path
+
+    gxx = shutil.which("g++")
+    if gxx is None:
+        pytest.skip("no g++")
+    rocm_include = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "include")  # hipError_t / hipStream_t of mz_kernels.h: types only
+    src = Path(__file__).resolve().parent / "select_main.cpp"
+    exe = tmp_path / "select_main"
+    build = subprocess.run([gxx, "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-D__HIP_PLATFORM_AMD__", "-I" + rocm_include,
+                            "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", str(src), "-o", str(exe)],
+                           capture_output=True, text=True)
+    assert build.returncode == 0, build.stderr[-3000:]
+    run = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
+    assert run.returncode == 0 and "selection OK" in run.stdout and not run.stderr, (run.returncode, run.stdout[-2000:], run.stderr[-3000:])

@@ -5,16 +5,19 @@ set -euo pipefail
 tag=$1; shift
 here="$(cd "$(dirname "$0")/../ultrazoom_amd/csrc" && pwd)"
 mkdir -p "$here/build"
-# the -D flags reach the host file too: it reads the kernels' LDS geometry (mz_kernels.h: MZ_GEMM1_S)
-/opt/rocm/bin/hipcc -O2 -std=c++17 -fPIC "$@" -c "$here/mz_host.cpp" -o "$here/build/mz_host_$tag.o"
-units=(mz_kernels mz_conv32 mz_conv3s mz_mix16 mz_conv3r mz_conv3t mz_metrics mz_resize mz_degrade mz_probe)
+source "$here/units.sh"
 pids=()
-for u in "${units[@]}"; do
+for u in "${kernel_units[@]}"; do
     /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC "$@" -c "$here/$u.hip" -o "$here/build/${u}_$tag.o" &
     pids+=($!)
 done
+# the -D flags reach the host units too: they read the kernels' LDS geometry (mz_geo.h: MZ_GEMM1_S)
+for u in "${host_units[@]}"; do
+    /opt/rocm/bin/hipcc -O2 -std=c++17 -fPIC "$@" -c "$here/$u.cpp" -o "$here/build/${u}_$tag.o" &
+    pids+=($!)
+done
 for p in "${pids[@]}"; do wait "$p"; done
-objs=("$here/build/mz_host_$tag.o")
-for u in "${units[@]}"; do objs+=("$here/build/${u}_$tag.o"); done
+objs=()
+for u in "${kernel_units[@]}" "${host_units[@]}"; do objs+=("$here/build/${u}_$tag.o"); done
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC "${objs[@]}" -o "$here/../libmewzoom_hip_$tag.so"
 echo "built $tag"

@@ -5,17 +5,19 @@ here="$(cd "$(dirname "$0")" && pwd)"
 out="$here/../libmewzoom_hip.so"
 HIPCC="${HIPCC:-/opt/rocm/bin/hipcc}"
 mkdir -p "$here/build"
+source "$here/units.sh"
 # one compile per translation unit, in parallel; every PID is waited for on its own so that the FIRST broken unit fails the build
 # with its own compiler output (a bare `wait` returns 0 whatever the children did, and the failure surfaced only at link time)
-units=(mz_kernels mz_conv32 mz_conv3s mz_mix16 mz_conv3r mz_conv3t mz_metrics mz_resize mz_degrade mz_probe)
 pids=()
-for u in "${units[@]}"; do
+for u in "${kernel_units[@]}"; do
     "$HIPCC" --offload-arch=gfx950 -O3 -std=c++17 -fPIC -c "$here/$u.hip" -o "$here/build/$u.o" &
     pids+=($!)
 done
-"$HIPCC" -O2 -std=c++17 -fPIC -c "$here/mz_host.cpp" -o "$here/build/mz_host.o" &
-pids+=($!)
-names=("${units[@]}" mz_host)
+for u in "${host_units[@]}"; do
+    "$HIPCC" -O2 -std=c++17 -fPIC -c "$here/$u.cpp" -o "$here/build/$u.o" &
+    pids+=($!)
+done
+names=("${kernel_units[@]}" "${host_units[@]}")
 fail=0
 for i in "${!pids[@]}"; do
     if ! wait "${pids[$i]}"; then

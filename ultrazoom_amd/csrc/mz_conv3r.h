@@ -258,7 +258,7 @@ __global__ __launch_bounds__(512) void conv3r_kernel(const ConvArgs a) {
     const int nchunks = a.nchunks16;       // 32-channel chunks, >= 3 (RAG: exactly 2; the host guards)
     const uint32_t lds_base = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)smem;
 
-    // ---- tile walk: the host lists the launch's tiles in walk order (mz_host.cpp: tile_table(); a.grid entries of eight bytes, the
+    // ---- tile walk: the host lists the launch's tiles in walk order (mz_runner.h: Runner::tile_table(); a.grid entries of eight bytes, the
     // group walk of mz_device.h with the padding ids dropped).  XCD x owns the x-th eighth of the list, its workgroups stride through it.
     // Tile coordinates come out of the table with ONE scalar load per tile, requested two tiles ahead at the start of a helper phase:
     // the divisions of the group walk (three chains of ~50 scalar instructions per phase, at ~5 cycles each in the role that is the
@@ -487,7 +487,7 @@ __global__ __launch_bounds__(512) void conv3r_kernel(const ConvArgs a) {
     //   D: blend x + sigmoid(alpha) sigmoid(beta) (z - x) into the accumulator registers, then the three entries as usual.
     // The arithmetic is conv3s_kernel<.., FUSE>'s, operation for operation, EXCEPT the summation order of the x half of the gate inside a
     // 32-wide K step (accumulator-row order here, plane order there): equal to <= 1 ulp of the output, >= 98 % bit-equal
-    // (tests/test_conv3r_gpu.py); which of the two runs therefore depends on channel counts only, never on H or W (mz_host.cpp).
+    // (tests/test_conv3r_gpu.py); which of the two runs therefore depends on channel counts only, never on H or W (mz_select.h: choose_conv3).
     auto fuse_x = [&](auto pf_tag) __attribute__((always_inline)) {  // request x of pixel fragment pf
         constexpr int pf = decltype(pf_tag)::value;
         const bool inside = e_y + GG::dy(pf) < a.H && e_c + GG::dx(pf) < a.W;

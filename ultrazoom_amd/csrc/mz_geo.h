@@ -1,5 +1,5 @@
 // LDS geometry of the 256- and 512-pixel convolution kernels (conv_kernel, conv3w, conv3p, conv3s) and the LDS bytes their launches ask
-// for.  Plain constexpr C++: the kernels and the host (Runner::conv3, mz_host.cpp: a fused Conv3Call's x_via_lds) read the same constants.
+// for.  Plain constexpr C++: the kernels and the host (Runner::conv3, mz_runner.h: a fused Conv3Call's x_via_lds) read the same constants.
 #pragma once
 #include "mz_kernels.h"
 

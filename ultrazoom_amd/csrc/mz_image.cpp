@@ -1,0 +1,183 @@
+// Stateless image entry points of libmewzoom_hip.so: image-quality metrics, antialiased resizing, the degradation chain, and the
+// host-only mz_debug_* views of what their kernels are handed.  Every check comes before anything touches the GPU.
+#include <cstring>
+
+#include "mz_degrade.h"
+#include "mz_err.h"
+#include "mz_metrics.h"
+#include "mz_resize.h"
+
+using namespace mz;
+
+// the tail of every entry here: the device made ready, the launch, its error under the entry's name
+template <class Launch> static int launched(const char* what, Launch launch) {
+    if (int rc = device_cus(); rc < 0) return rc;
+    return hip_rc(launch(), what);
+}
+
+// ------------------------------------------------------------------------------------------------
+// image-quality metrics (mz_metrics.h): no reference counterpart in model.py; stands in for torchmetrics as the reference's
+// pretrain.py:209-211, 301-329 uses it.  Stateless like the mz_op_* entries.
+// ------------------------------------------------------------------------------------------------
+static int check_metrics_shape(int B, int H, int W, int which) {
+    if (which <= 0 || (which & ~(MET_PSNR | MET_SSIM | MET_VIF)))
+        return fail(MZ_ERR_INVALID_ARGUMENT, "which must be a non-empty combination of 1 (PSNR), 2 (SSIM), 4 (VIF), got %d", which);
+    if (B < 1 || H < 1 || W < 1) return fail(MZ_ERR_INVALID_ARGUMENT, "need B, H, W >= 1 (got %d, %d, %d)", B, H, W);
+    if (B > 65535 || H > (1 << 28) || W > (1 << 28))
+        return fail(MZ_ERR_INVALID_ARGUMENT, "at most 65535 images of at most 2^28 pixels a side (got %d, %d, %d)", B, H, W);
+    if ((which & MET_SSIM) && (H < 11 || W < 11))
+        return fail(MZ_ERR_INVALID_ARGUMENT, "SSIM needs images of at least 11 x 11 pixels, got %d x %d", H, W);
+    if ((which & MET_VIF) && (H < 41 || W < 41))
+        return fail(MZ_ERR_INVALID_ARGUMENT, "VIF needs images of at least 41 x 41 pixels, got %d x %d", H, W);
+    return MZ_OK;
+}
+
+extern "C" int mz_metrics_workspace_bytes(int B, int H, int W, int which, size_t* bytes) {
+    if (!bytes) return fail(MZ_ERR_INVALID_ARGUMENT, "null argument");
+    if (int rc = check_metrics_shape(B, H, W, which)) return rc;
+    *bytes = metrics_plan(B, H, W, which).total;
+    return MZ_OK;
+}
+
+extern "C" int mz_metrics(const mz_image_view* pred, const mz_image_view* target, int elem, int B, int H, int W, int which,
+                          double data_range, double sigma_n_sq, double* out_dev, void* workspace, size_t workspace_bytes,
+                          void* hip_stream) {
+    static const ViewRules rules = {3, MZ_ELEM_NAMES_0_3, /*second_is_output*/ false, /*batch_bound*/ false, /*side_bound*/ false};
+    MetricsArgs a = {};
+    if (const Refusal r = check_views(pred, target, rules, elem, B, H, W, &a.pred, &a.target)) return fail(r);
+    if (int rc = check_metrics_shape(B, H, W, which)) return rc;
+    if (!out_dev) return fail(MZ_ERR_INVALID_ARGUMENT, "null out_dev");
+    a.plan = metrics_plan(B, H, W, which);
+    if (const Refusal r = check_workspace(workspace, workspace_bytes, a.plan.total)) return fail(r);
+    a.elem = elem; a.B = B; a.H = H; a.W = W;
+    a.which = which;
+    a.data_range = data_range;
+    a.sigma_n_sq = sigma_n_sq;
+    a.out = out_dev;
+    a.ws = (char*)workspace;
+    return launched("metrics launch", [&] { return launch_metrics(a, (hipStream_t)hip_stream); });
+}
+
+// ------------------------------------------------------------------------------------------------
+// antialiased resampling to any size (mz_resize.h): no reference counterpart in model.py; stands in for torchvision's Resize as the
+// reference's data.py:91-108 uses it.  Stateless like mz_metrics.  Every check comes before anything touches the GPU.
+// ------------------------------------------------------------------------------------------------
+static int check_resize_shape(int Hin, int Win, int Hout, int Wout, int filter) {
+    if (filter != RF_BICUBIC && filter != RF_BILINEAR)
+        return fail(MZ_ERR_INVALID_ARGUMENT, "filter must be 0 (bicubic) or 1 (bilinear), got %d", filter);
+    if (Hin < 1 || Win < 1 || Hout < 1 || Wout < 1)
+        return fail(MZ_ERR_INVALID_ARGUMENT, "need sizes >= 1 (got %d x %d -> %d x %d)", Hin, Win, Hout, Wout);
+    if (Hin > (1 << 28) || Win > (1 << 28) || Hout > (1 << 28) || Wout > (1 << 28))
+        return fail(MZ_ERR_INVALID_ARGUMENT, "at most 2^28 pixels a side (got %d x %d -> %d x %d)", Hin, Win, Hout, Wout);
+    if ((long long)Hin > (long long)kResizeMaxRatio * Hout || (long long)Win > (long long)kResizeMaxRatio * Wout)
+        return fail(MZ_ERR_INVALID_ARGUMENT, "%d x %d -> %d x %d shrinks an axis by more than %d", Hin, Win, Hout, Wout, kResizeMaxRatio);
+    return MZ_OK;
+}
+
+extern "C" int mz_resize_workspace_bytes(int Hin, int Win, int Hout, int Wout, int filter, size_t* bytes) {
+    if (!bytes) return fail(MZ_ERR_INVALID_ARGUMENT, "null argument");
+    if (int rc = check_resize_shape(Hin, Win, Hout, Wout, filter)) return rc;
+    *bytes = resize_plan(Hin, Win, Hout, Wout, filter).total;
+    return MZ_OK;
+}
+
+extern "C" int mz_resize(const mz_image_view* x, const mz_image_view* out, int elem, int B, int Hin, int Win, int Hout, int Wout, int filter,
+                         int clamp, const int32_t window[4], void* workspace, size_t workspace_bytes, void* hip_stream) {
+    static const ViewRules rules = {3, MZ_ELEM_NAMES_0_3, /*second_is_output*/ true, /*batch_bound*/ true, /*side_bound*/ false};
+    ResizeArgs a = {};
+    if (const Refusal r = check_views(x, out, rules, elem, B, Hout, Wout, &a.x, &a.out)) return fail(r);
+    if (int rc = check_resize_shape(Hin, Win, Hout, Wout, filter)) return rc;
+    if (const Refusal r = check_window(window, Hout, Wout, &a.y0, &a.x0, &a.h, &a.w)) return fail(r);
+    a.plan = resize_plan(Hin, Win, Hout, Wout, filter);
+    if (const Refusal r = check_workspace(workspace, workspace_bytes, a.plan.total)) return fail(r);
+    a.elem = elem;
+    a.B = B;
+    a.Hin = Hin; a.Win = Win; a.Hout = Hout; a.Wout = Wout;
+    a.filter = filter;
+    a.clamp = clamp != 0;
+    a.ws = (char*)workspace;
+    return launched("resize launch", [&] { return launch_resize(a, (hipStream_t)hip_stream); });
+}
+
+// Host only: resize_taps() (mz_resize.h) of one output index, the source the device's table kernel compiles too
+extern "C" int mz_debug_resize_taps(int n_in, int n_out, int filter, int i, int* first, double* w, int cap) {
+    if (!first || !w || cap < 0) return fail(MZ_ERR_INVALID_ARGUMENT, "null argument or negative cap");
+    if (int rc = check_resize_shape(n_in, 1, n_out, 1, filter)) return rc;
+    if (i < 0 || i >= n_out) return fail(MZ_ERR_INVALID_ARGUMENT, "output index %d is not in [0, %d)", i, n_out);
+    const int count = resize_taps(n_in, n_out, filter, i, first, cap, [&](int j, double v) { w[j] = v; });
+    if (count > cap) return fail(MZ_ERR_INVALID_ARGUMENT, "output %d has %d taps, room for %d", i, count, cap);
+    return count;
+}
+
+// ------------------------------------------------------------------------------------------------
+// the degradation chain (mz_degrade.h): no reference counterpart in model.py; stands in for torchvision's gaussian_blur, gaussian_noise
+// and jpeg as the reference's transforms.py uses them.  Stateless like mz_resize.  Every check comes before anything touches the GPU.
+// ------------------------------------------------------------------------------------------------
+static int check_degrade_views(const mz_image_view* x, const mz_image_view* out, int elem, int B, int H, int W, int in_place_ok, DegradeArgs* a) {
+    static const ViewRules rules = {3, MZ_ELEM_NAMES_0_3, /*second_is_output*/ true, /*batch_bound*/ true, /*side_bound*/ true};
+    if (const Refusal r = check_views(x, out, rules, elem, B, H, W, &a->x, &a->out)) return fail(r);
+    if (const Refusal r = check_overlap(x, out, elem, B, H, W, in_place_ok != 0)) return fail(r);
+    a->elem = elem; a->B = B; a->H = H; a->W = W;
+    return MZ_OK;
+}
+
+extern "C" int mz_blur(const mz_image_view* x, const mz_image_view* out, int elem, int B, int H, int W, double sigma, void* hip_stream) {
+    DegradeArgs a = {};
+    if (int rc = check_degrade_views(x, out, elem, B, H, W, 0, &a)) return rc;
+    BlurWeights bw = {};
+    const int half = blur_weights(sigma, &bw);
+    if (half < 0) return fail(MZ_ERR_INVALID_ARGUMENT, "sigma %g: need 0 <= sigma and int(3 sigma) <= %d", sigma, kBlurMaxHalf);
+    if (half >= (H < W ? H : W))
+        return fail(MZ_ERR_INVALID_ARGUMENT, "sigma %g needs %d pixels of reflect padding, a %d x %d image has no such reflection", sigma, half, H, W);
+    return launched("blur launch", [&] { return launch_blur(a, bw, (hipStream_t)hip_stream); });
+}
+
+extern "C" int mz_noise(const mz_image_view* x, const mz_image_view* out, int elem, int B, int H, int W, double sigma, uint64_t seed,
+                        uint64_t offset, void* hip_stream) {
+    DegradeArgs a = {};
+    if (int rc = check_degrade_views(x, out, elem, B, H, W, 1, &a)) return rc;
+    if (!(sigma >= 0.0) || !(sigma <= 1e6)) return fail(MZ_ERR_INVALID_ARGUMENT, "sigma %g: need 0 <= sigma <= 1e6", sigma);
+    return launched("noise launch", [&] { return launch_noise(a, sigma, seed, offset, (hipStream_t)hip_stream); });
+}
+
+extern "C" int mz_jpeg_workspace_bytes(int B, int H, int W, size_t* bytes) {
+    if (!bytes) return fail(MZ_ERR_INVALID_ARGUMENT, "null argument");
+    if (B < 1 || B > 65535 || H < 1 || W < 1 || H > (1 << 28) || W > (1 << 28))
+        return fail(MZ_ERR_INVALID_ARGUMENT, "need 1 <= B <= 65535 and 1 <= H, W <= 2^28 (got %d, %d, %d)", B, H, W);
+    *bytes = jpeg_plan(B, H, W).total;
+    return MZ_OK;
+}
+
+extern "C" int mz_jpeg(const mz_image_view* x, const mz_image_view* out, int elem, int B, int H, int W, int quality, void* workspace,
+                       size_t workspace_bytes, void* hip_stream) {
+    DegradeArgs a = {};
+    if (int rc = check_degrade_views(x, out, elem, B, H, W, 0, &a)) return rc;
+    if (quality < 1 || quality > 100) return fail(MZ_ERR_INVALID_ARGUMENT, "quality must be 1..100, got %d", quality);
+    const JpegPlan plan = jpeg_plan(B, H, W);
+    if (const Refusal r = check_workspace(workspace, workspace_bytes, plan.total)) return fail(r);
+    JpegTables t;
+    jpeg_qtable(quality, &t);
+    return launched("jpeg launch", [&] { return launch_jpeg(a, t, plan, (char*)workspace, (hipStream_t)hip_stream); });
+}
+
+// Host only: what the kernels are handed and compile -- the blur weights of a sigma, the quantisation tables of a quality, one Philox block
+extern "C" int mz_debug_blur_weights(double sigma, double* w, int cap) {
+    BlurWeights bw = {};
+    const int half = blur_weights(sigma, &bw);
+    if (!w || half < 0 || 2 * half + 1 > cap) return fail(MZ_ERR_INVALID_ARGUMENT, "null argument, a bad sigma (%g) or room for fewer than k weights", sigma);
+    for (int j = 0; j <= 2 * half; ++j) w[j] = bw.w[j];
+    return 2 * half + 1;
+}
+extern "C" int mz_debug_jpeg_qtable(int quality, uint8_t* luma, uint8_t* chroma) {
+    if (!luma || !chroma || quality < 1 || quality > 100) return fail(MZ_ERR_INVALID_ARGUMENT, "null argument or quality %d outside 1..100", quality);
+    JpegTables t;
+    jpeg_qtable(quality, &t);
+    memcpy(luma, t.q[0], 64);
+    memcpy(chroma, t.q[1], 64);
+    return MZ_OK;
+}
+extern "C" int mz_debug_philox(const uint32_t counter[4], const uint32_t key[2], uint32_t out[4]) {
+    if (!counter || !key || !out) return fail(MZ_ERR_INVALID_ARGUMENT, "null argument");
+    philox4x32_10(counter[0], counter[1], counter[2], counter[3], key[0], key[1], out);
+    return MZ_OK;
+}

@@ -1,4 +1,4 @@
-// Internal interface between the host runtime (mz_host.cpp) and the gfx950 kernels (one family per header mz_<family>.h, launchers in the .hip units).
+// Internal interface between the host runtime (mz_plan.h, mz_select.h, mz_runner.h and the four host units) and the gfx950 kernels (one family per header mz_<family>.h, launchers in the .hip units).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -75,7 +75,7 @@ struct ConvArgs {
     const void* wpk16; // weights packed for it: [ntile][32-channel chunk][tap][2*nt][64 lanes][16 B]
     int nchunks16;     // 32-channel chunks
     const void* tile_tab;  // conv3r / conv3t: the launch's tiles in walk order, uint2 {y0 | x0 << 16, image | N tile << 16} each, padded with
-                           // 4 * persist / 8 + 8 entries; a.grid = its length (mz_host.cpp: tile_table())
+                           // 4 * persist / 8 + 8 entries; a.grid = its length (mz_runner.h: Runner::tile_table())
     int ragged_planes; // conv3r_kernel<.., RAG>: 16-byte planes that exist in the LAST 32-channel chunk (1..3; Cin = 48: 2): the pieces of the
                        // others are issued with every lane out of range (zeros into LDS); 0 = every chunk has its four planes
     int geo;           // conv3r_kernel: pixel-tile geometry, 0 = 8 x 48 (six pixel fragments per wave), 1 = 8 x 40 (five)
@@ -114,7 +114,7 @@ inline int choose_nt(int n_padded) {
     return best;
 }
 
-// ---- launchers: one per kernel family, next to the family's instantiations (mz_conv32.hip for the three 32x32-MFMA families, else mz_<family>.hip).  The host chooses the family (mz_host.cpp:
+// ---- launchers: one per kernel family, next to the family's instantiations (mz_conv32.hip for the three 32x32-MFMA families, else mz_<family>.hip).  The host chooses the family (mz_select.h:
 // choose_conv3 / choose_mix -> KernelChoice::kernel) and Runner::launch switches over it; a launcher launches ITS family and answers
 // hipErrorInvalidValue to arguments that do not fit it.  The first launch of an instantiation on a device raises its dynamic-LDS limit
 // (launch_lds(), mz_device.h).
@@ -161,7 +161,7 @@ hipError_t launch_conv3t(int dtype, const ConvArgs& a, hipStream_t s);
 
 // ---- weight packing ---------------------------------------------------------------------------
 enum OutMap : int { OUT_PLAIN = 0, OUT_D2S = 1, OUT_FINAL = 2 };
-// The packings of one layer's weights (mz_pack.h maps each element to its OIHW source; mz_host.cpp plans which layers have which).
+// The packings of one layer's weights (mz_pack.h maps each element to its OIHW source; mz_plan.h plans which layers have which).
 // PK_MAIN counts 32-channel fragments of the 32x32 MFMA and K chunks of chunk_channels(); every other layout holds fragments of the
 // 16x16x32 MFMA (16 channels x 32 K, 16-bit types) and counts K chunks of 32 channels.  Packed in this order.
 enum PackLayout : int {

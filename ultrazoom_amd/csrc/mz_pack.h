@@ -1,5 +1,5 @@
 // The weight packings (PackLayout, mz_kernels.h) as one map from a packed element to its OIHW source: pack_kernel (mz_kernels.hip)
-// runs it on the device, mz_debug_pack (mz_host.cpp) on the host.
+// runs it on the device, mz_debug_pack (mz_debug.cpp) on the host.
 #pragma once
 #include "mz_kernels.h"
 

@@ -1,6 +1,6 @@
 // What every entry that takes mz_image_view refuses (include/mewzoom_hip.h, next to mz_image_view), stated once and called by all six
 // before anything touches the GPU.  Host code without a HIP header (plain g++ compiles it: tests/view_check_main.cpp runs it under
-// the sanitizers); a check returns its code and message, the caller hands them to mz_host.cpp's fail().
+// the sanitizers); a check returns its code and message, the caller hands them to fail() (mz_err.h).
 #pragma once
 #include <stdarg.h>
 #include <stddef.h>
