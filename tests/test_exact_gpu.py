@@ -19,8 +19,7 @@ ACTIVATIONS = {"in0", "in1", "hid", "x", "feat"}  # plane-major activation tenso
 def launch(row, ex):
     """The row's operator on the row's data: (output on the GPU, its real channels [B, C, H, W] on the CPU, storage type)."""
     dtype = DTYPES[row.dt]
-    op = Op.__new__(Op)  # Op.run alone: the call of each entry as tests/test_poison_ops_gpu.py states it, on this table's tensors
-    op.entry, op.args, op.dt, op.dtype, op.alpha = row.entry, row.args, row.dt, dtype, ex.alpha
+    op = Op.call_only(row.entry, row.args, row.dt, ex.alpha)  # the call of each entry as tests/test_poison_ops_gpu.py states it, on this table's tensors
     t = {}
     for name, v in ex.inputs.items():
         if name in ACTIVATIONS and not (row.entry == "stem" and name == "x"):

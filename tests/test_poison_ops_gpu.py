@@ -225,6 +225,14 @@ class Op:
         else:
             raise ValueError(entry)
 
+    @classmethod
+    def call_only(cls, entry, args, dt, alpha=0.0):
+        """An Op that has no tensors or oracle of its own: run() alone, on tensors the caller brings (tests/test_exact_gpu.py,
+        tests/test_large_offsets_gpu.py).  Sets exactly what run() reads."""
+        op = cls.__new__(cls)
+        op.entry, op.args, op.dt, op.dtype, op.alpha = entry, tuple(args), dt, DTYPES[dt], alpha
+        return op
+
     def real(self, out):
         """The output's real channels as float32 [B, C, H, W] on the CPU."""
         return out.float().cpu() if self.C is None else from_act(out, self.C)
