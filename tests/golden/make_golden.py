@@ -75,6 +75,15 @@ MODEL_CASES = {
     "g7_cfg1_2x_c48": (cfg(2, (48, 96, 192, 384), (4, 4, 4, 8)), (1, 256, 256), 9, 11, False, True),
 }
 
+# g11: the lower edge of the domain (H, W >= 8: an 8 x 8 image has levels of 8 x 8, 4 x 4, 2 x 2 and 1 x 1; at 15 x 15 every level has
+# a floor and every up-conv a zero border), several small cases in ONE file, keys prefixed "<case>/"
+LOWER_EDGE_CONFIGS = {
+    "2x_c16": (cfg(2, (16, 32, 64, 128), (2, 2, 2, 2)), 11),            # config, weight seed
+    "4x_c24": (cfg(4, (24, 32, 48, 64), (2, 3, 2, 2)), 12),
+}
+LOWER_EDGE_SIZES = ((8, 8), (8, 9), (15, 15))
+LOWER_EDGE_B = 2
+
 N_SAMPLES = 4096
 
 
@@ -160,6 +169,42 @@ def run_model_case(ref, name, spec):
     print(f"{name}: sr {tuple(sr.shape)} range [{sr.min():.4f}, {sr.max():.4f}] qa {qa.flatten()[:3].tolist()}")
 
 
+def run_lower_edge_case(ref):
+    """g11_lower_edge.npz: sr, up, qa and the reference's own bf16 / f16 results and errors (as run_model_case stores them) of every
+    configuration of LOWER_EDGE_CONFIGS at every size of LOWER_EDGE_SIZES."""
+    out, cases = {}, {}
+    bits = (lambda t: t.contiguous().view(torch.int16).numpy().view(np.uint16))
+    for cname, (config, wseed) in LOWER_EDGE_CONFIGS.items():
+        model = ref.MewZoom(**config)
+        shapes = {k: tuple(v.shape) for k, v in model.state_dict().items()}
+        sd = synth_state_dict(shapes, wseed)
+        model.load_state_dict(sd)
+        model.eval()
+        for H, W in LOWER_EDGE_SIZES:
+            key, iseed = f"{cname}_{H}x{W}", 100 * H + W
+            x = synth_image(LOWER_EDGE_B, H, W, iseed)
+            with torch.inference_mode():
+                sr, qa = model.forward(x)
+                up = model.upscale(x)
+                out[f"{key}/sr"], out[f"{key}/up"], out[f"{key}/qa"] = sr.numpy(), up.numpy(), qa.numpy()
+                for tag, dt in (("bf16", torch.bfloat16), ("f16", torch.float16)):
+                    low = ref.MewZoom(**config)
+                    low.load_state_dict(sd)
+                    low = low.to(dt).eval()
+                    sr_l, qa_l = low.forward(x.to(dt))
+                    up_l = low.upscale(x.to(dt))
+                    out[f"{key}/ref_{tag}_err"] = np.array([(sr_l.float() - sr).abs().max().item(),
+                                                            (up_l.double() - up.double()).pow(2).mean().item(),
+                                                            (qa_l.float() - qa).abs().max().item()])
+                    out[f"{key}/ref_{tag}_sr"] = bits(sr_l)
+                    out[f"{key}/ref_{tag}_qa"] = bits(qa_l)
+            cases[key] = {"config": config, "input": [LOWER_EDGE_B, H, W], "weight_seed": wseed, "image_seed": iseed,
+                          "shapes": {k: list(v) for k, v in shapes.items()}, "num_params": int(model.num_params)}
+            print(f"g11 {key}: sr {tuple(sr.shape)} range [{sr.min():.4f}, {sr.max():.4f}]")
+    out["meta"] = np.array(json.dumps({"cases": cases}))
+    np.savez_compressed(HERE / "g11_lower_edge.npz", **out)
+
+
 def run_op_cases(ref):
     """Per-operator fixtures."""
     out = {}
@@ -223,6 +268,8 @@ def run_validation_cases(ref):
         "primary_channels_2": {"primary_channels": 2},
         "num_deg_features_0": {"num_deg_features": 0},
     }
+    # forward() on images below the minimum: the reference's PixelCrush raises on a 7 x 7 (and a 4 x 4) image and accepts 8 x 8
+    forward_trials = {"forward_8x8": (8, 8), "forward_7x7": (7, 7), "forward_4x4": (4, 4)}
     result = {}
     for name, delta in trials.items():
         kw = dict(base)
@@ -232,6 +279,14 @@ def run_validation_cases(ref):
             result[name] = {"kwargs": kw, "raises": None}
         except Exception as e:  # noqa: BLE001
             result[name] = {"kwargs": kw, "raises": type(e).__name__}
+    model = ref.MewZoom(**base).eval()
+    for name, (H, W) in forward_trials.items():
+        try:
+            with torch.inference_mode():
+                model.forward(synth_image(1, H, W, 1))
+            result[name] = {"kwargs": dict(base), "input": [1, H, W], "raises": None}
+        except Exception as e:  # noqa: BLE001
+            result[name] = {"kwargs": dict(base), "input": [1, H, W], "raises": type(e).__name__}
     (HERE / "validation.json").write_text(json.dumps(result, indent=1, sort_keys=True))
     print("validation:", {k: v["raises"] for k, v in result.items()})
 
@@ -277,6 +332,8 @@ def main():
         if only and name not in only:
             continue
         run_model_case(ref, name, spec)
+    if not only or "lower_edge" in only:
+        run_lower_edge_case(ref)
     if not only or "ops" in only:
         run_op_cases(ref)
     if not only or "validation" in only:

@@ -12,14 +12,40 @@ from ultrazoom_amd.synth import synth_image, synth_state_dict
 
 GOLDEN = Path(__file__).resolve().parent / "golden"
 
-MODEL_CASES = sorted(p.stem for p in GOLDEN.glob("g*.npz") if p.stem not in ("g6_ops", "g10_checkpoint"))
+LOWER_EDGE = "g11_lower_edge"  # several small cases in one file, keys prefixed "<case>/"; a case's name is "g11_lower_edge/<case>"
+
+
+def _lower_edge_cases():
+    whole = np.load(GOLDEN / f"{LOWER_EDGE}.npz", allow_pickle=False)
+    return [f"{LOWER_EDGE}/{key}" for key in json.loads(str(whole["meta"]))["cases"]]
+
+
+LOWER_EDGE_CASES = _lower_edge_cases()
+MODEL_CASES = sorted(p.stem for p in GOLDEN.glob("g*.npz") if p.stem not in ("g6_ops", "g10_checkpoint", LOWER_EDGE)) + LOWER_EDGE_CASES
+
+
+class _Prefixed:
+    """The arrays of one case of a several-case file, under the names a one-case file gives them."""
+
+    def __init__(self, data, prefix: str):
+        self._data, self._prefix = data, prefix
+        self.files = [k[len(prefix):] for k in data.files if k.startswith(prefix)]
+
+    def __getitem__(self, key):
+        return self._data[self._prefix + key]
 
 
 class GoldenCase:
     def __init__(self, name: str):
         self.name = name
-        self.data = np.load(GOLDEN / f"{name}.npz", allow_pickle=False)
-        self.meta = json.loads(str(self.data["meta"]))
+        if "/" in name:  # one case of a several-case file (the reference at the smallest images it accepts)
+            stem, key = name.split("/")
+            whole = np.load(GOLDEN / f"{stem}.npz", allow_pickle=False)
+            self.data = _Prefixed(whole, key + "/")
+            self.meta = json.loads(str(whole["meta"]))["cases"][key]
+        else:
+            self.data = np.load(GOLDEN / f"{name}.npz", allow_pickle=False)
+            self.meta = json.loads(str(self.data["meta"]))
         self.config = self.meta["config"]
         self.B, self.H, self.W = self.meta["input"]
 

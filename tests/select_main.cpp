@@ -1,5 +1,5 @@
 // Host-only driver of ultrazoom_amd/csrc/mz_plan.h and mz_select.h: layer plans, kernel choices, tile walks, tile lists and workspace
-// plans over the layers of tests/test_select_cpu.py's table, channel counts around every tile and chunk boundary, shapes from 8 x 8 to
+// plans over the layers of tests/test_select_cpu.py's table, channel counts around every tile and chunk boundary, shapes from 1 x 1 to
 // 4320 x 7680 and 1 to 64 images.  tests/test_select_cpu.py compiles it with g++ -fsanitize=address,undefined
 // -fno-sanitize-recover=undefined and runs it: exit status 0 and no sanitizer report (a signed overflow in a tile count, an offset guard
 // or a workspace size would abort it).  Nothing of the library is linked: the two headers call nothing in HIP.
@@ -46,7 +46,7 @@ static const int kTableLayers[][4] = {
     {2, 7, 768, 384}, {2, 7, 1536, 768},
 };
 static const int kChannels[] = {1, 15, 16, 17, 31, 32, 33, 48, 96, 191, 192, 193, 384, 768, 1536, 2047, 2048};
-static const int kShapes[][2] = {{8, 8}, {9, 11}, {37, 45}, {67, 120}, {135, 240}, {540, 960}, {1080, 1920}, {2160, 3840}, {4320, 7680}};
+static const int kShapes[][2] = {{1, 1}, {1, 2}, {2, 1}, {2, 3}, {8, 8}, {9, 11}, {37, 45}, {67, 120}, {135, 240}, {540, 960}, {1080, 1920}, {2160, 3840}, {4320, 7680}};
 static const int kBatches[] = {1, 3, 16, 64};
 static const int kCus[] = {0, 8, 256};
 // tile lists are built (once per geometry, as Runner::tile_table keeps them) where they have at most this many entries
@@ -168,7 +168,7 @@ int main() {
                 for (int op = 0; op < 8; ++op)
                     for (int cin : kChannels)
                         for (int cout : kChannels)
-                            for (int si : {0, 2, 4, 8})
+                            for (int si : {0, 3, 4, 6, 8, 12})
                                 for (int B : {1, 64}) run_layer(k, dtype, op, op == 7 ? 2 * cout : cin, cout, B, kShapes[si][0], kShapes[si][1], cus);
         }
     // refusals name themselves

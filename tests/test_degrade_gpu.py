@@ -316,3 +316,63 @@ def test_evaluate_hr_with_a_degradation():
     assert evaluate_hr(m, batches, backend="hip") == evaluate(m, [lr_from_hr(hr, m.upscale_ratio, backend="hip") for hr in batches], backend="hip")
     with pytest.raises(ValueError, match="backend='hip'"):
         evaluate_hr(m, batches, degrade=deg)
+
+
+# ---- the lower edge ----------------------------------------------------------------------------------------------------------------------
+# One pixel, a single row, a single column, 2 x 3, one whole MCU and 9 x 15 (partial MCUs in both directions).  A list of its own: SHAPES
+# is shared with sigma 2.5, whose reflection needs eight pixels.
+SMALL_SHAPES = [(1, 1), (1, 9), (7, 1), (2, 3), (8, 8), (9, 15)]
+
+
+@pytest.mark.parametrize("dt", sorted(DTYPES))
+@pytest.mark.parametrize("shape", SMALL_SHAPES, ids=shape_id)
+def test_noise_at_the_smallest_images(shape, dt):
+    x = image(BATCH, *shape, dt)
+    xg = x.cuda()
+    for sigma in NOISE_SIGMAS:
+        got = hip().gaussian_noise(xg, sigma, seed=SEED, offset=OFFSET)
+        assert_noise_gate(got, R.noise_ref(x, sigma, SEED, OFFSET), dt, f"noise {shape_id(shape)} {dt} sigma {sigma}")
+    whole = hip().gaussian_noise(xg, 0.05, seed=SEED, offset=OFFSET)
+    for b in range(BATCH):
+        assert torch.equal(hip().gaussian_noise(xg[b:b + 1], 0.05, seed=SEED, offset=OFFSET + b)[0], whole[b]), b
+
+
+@pytest.mark.parametrize("dt", sorted(DTYPES))
+@pytest.mark.parametrize("shape", SMALL_SHAPES, ids=shape_id)
+def test_jpeg_at_the_smallest_images_is_the_checker_bit_for_bit(shape, dt):
+    xg = image(BATCH, *shape, dt).cuda()
+    for q in QUALITIES:
+        want, unsure, share = jpeg_checker(BATCH, shape, dt, q)
+        got = hip().jpeg(xg, q).cpu()
+        assert got.dtype == want.dtype and got.shape == want.shape
+        keep = ~unsure.expand_as(want)
+        wrong = int(((got != want) & keep).sum())
+        print(f"jpeg {shape_id(shape)} {dt} q {q}: {wrong} elements differ outside near-tie blocks; near-tie share {share:.2e}")
+        assert share < 0.01, (q, share)
+        assert wrong == 0, (q, wrong)
+
+
+@pytest.mark.parametrize("dt", sorted(DTYPES))
+@pytest.mark.parametrize("shape", SMALL_SHAPES, ids=shape_id)
+def test_blur_at_the_smallest_images(shape, dt):
+    """Every sigma whose reflection fits (int(3 sigma) < min(H, W)) against the checker; every other one is refused with its message, by
+    the Python layer and by the C entry, and the call after a refusal is unaffected."""
+    from test_resize_gpu import assert_within_gate
+
+    x = image(BATCH, *shape, dt)
+    xg = x.cuda()
+    refused = 0
+    for sigma in BLUR_SIGMAS:
+        if int(3 * sigma) < min(shape):
+            got = hip().gaussian_blur(xg, sigma)
+            assert_within_gate(got, R.blur_ref(x, sigma), dt, f"blur {shape_id(shape)} {dt} sigma {sigma}")
+            continue
+        refused += 1
+        with pytest.raises(ValueError, match="reflect"):
+            hip().gaussian_blur(xg, sigma)
+        out = torch.empty_like(xg)
+        with pytest.raises(_ffi.MewZoomHipError, match="reflect"):
+            raw_blur(xg.data_ptr(), xg.stride(), out, ELEM[dt], BATCH, *shape, sigma)
+        assert torch.equal(hip().gaussian_blur(xg, 0.2).cpu(), x), "the call after a refusal"
+    assert refused == sum(int(3 * s) >= min(shape) for s in BLUR_SIGMAS) and (refused > 0) == (min(shape) < 8)
+    assert torch.equal(hip().gaussian_blur(xg, 0.2).cpu(), x), "sigma < 1 / 3 copies"

@@ -10,7 +10,7 @@ import torch.nn.functional as F
 from golden_util import GoldenCase
 from gpu_util import DTYPES, assert_op_close, alloc_act, from_act, op_conv, q, to_act
 from ultrazoom_amd import MewZoom, _ffi
-from ultrazoom_amd.synth import hash_uniform
+from ultrazoom_amd.synth import hash_uniform, synth_image
 
 pytestmark = pytest.mark.gpu
 
@@ -34,6 +34,43 @@ def test_bad_calls_raise():
     with pytest.raises(_ffi.MewZoomHipError, match="workspace too small"):
         engine.handle.forward(x.data_ptr(), out.data_ptr(), 0, 1, 32, 32, True, ws.data_ptr(), ws.numel(), 0,
                               torch.cuda.current_stream().cuda_stream)
+
+
+@pytest.mark.parametrize("dt", ["f32", "bf16"])
+def test_images_below_8_pixels_are_refused_and_8x8_is_accepted(dt):
+    """7 x 8 and 8 x 7 through every entry that takes a size: refused with the H, W >= 8 message before anything is launched; the
+    handle then runs 8 x 8 as if nothing had happened (the reference's PixelCrush raises below 8 x 8, tests/golden/validation.json)."""
+    dtype = DTYPES[dt]
+    case = GoldenCase("g1_2x_c16")
+    m = MewZoom(**case.config)
+    m.load_state_dict(case.weights())
+    m = m.to("cuda", dtype).eval()
+    x8 = synth_image(2, 8, 8, 5).to("cuda", dtype)
+    want = m.upscale(x8)
+    engine = m._get_engine(x8)
+    h, stream = engine.handle, torch.cuda.current_stream().cuda_stream
+    need = h.workspace_bytes(2, 8, 8)
+    assert need > 0
+    ws = torch.empty(need, dtype=torch.uint8, device="cuda")
+    out = torch.full((2, 3, 16, 16), -3.0, dtype=dtype, device="cuda")
+    out8 = torch.full((2, 3, 16, 16), 5, dtype=torch.uint8, device="cuda")
+    xu = torch.zeros(2, 3, 8, 8, dtype=torch.uint8, device="cuda")
+    for H, W in ((7, 8), (8, 7)):
+        with pytest.raises(_ffi.MewZoomHipError, match="H, W >= 8"):
+            h.workspace_bytes(2, H, W)
+        with pytest.raises(_ffi.MewZoomHipError, match="H, W >= 8"):
+            h.forward(x8.data_ptr(), out.data_ptr(), 0, 2, H, W, True, ws.data_ptr(), need, 0, stream)
+        with pytest.raises(_ffi.MewZoomHipError, match="H, W >= 8"):
+            h.forward_u8(xu.data_ptr(), out8.data_ptr(), 0, 2, H, W, ws.data_ptr(), need, 0, stream)
+        with pytest.raises(_ffi.MewZoomHipError, match="H, W >= 8"):
+            h.forward_view(x8.data_ptr(), x8.stride(), out.data_ptr(), out.stride(), 0, 2, H, W, True, 0, None, ws.data_ptr(), need, 0, stream)
+        with pytest.raises(_ffi.MewZoomHipError, match="H, W >= 8"):
+            m.upscale(x8[:, :, :H, :W])
+    torch.cuda.synchronize()
+    assert bool((out == -3.0).all()) and bool((out8 == 5).all()), "a refused call wrote to its output"
+    h.forward(x8.data_ptr(), out.data_ptr(), 0, 2, 8, 8, True, ws.data_ptr(), need, 0, stream)
+    torch.cuda.synchronize()
+    assert torch.equal(out, want) and torch.equal(m.upscale(x8), want)
 
 
 def _rnd(shape, seed, scale=1.0):

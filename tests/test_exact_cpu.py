@@ -8,7 +8,7 @@ from pathlib import Path
 import pytest
 import torch
 
-from exact_util import (EXACT_SUM, F16_MAX_OUT, MAX_EXCLUDED, MIN_BRANCH, PERSISTENT, ROWS, WALK_WGS, WALKS, bits_of, census, exact, round_once, row_id,
+from exact_util import (CENSUS_MIN, CENSUS_MIN_SHARE, EXACT_SUM, F16_MAX_OUT, MAX_EXCLUDED, MIN_BRANCH, PERSISTENT, ROWS, WALK_WGS, WALKS, bits_of, census, exact, lower_edge, round_once, row_id,
                         walk_id)
 from gpu_util import DTYPES
 from test_poison_ops_gpu import FAMILY_OF_UNREPORTED, KNOBS, SELECT_OP
@@ -89,7 +89,14 @@ def test_the_row_s_conditions(row):
         if hasattr(ex, "z64_unrounded"):
             assert ex.z64_unrounded.abs().max().item() < F16_MAX_OUT
     y = ex.compared()
-    if dt != "f32":
+    if dt != "f32" and lower_edge(row) and y.numel() < CENSUS_MIN:
+        # too few elements for 100 ties (exact_util.LOWER_EDGE): the family's ties are pinned by a row of ordinary size, held to them below
+        assert any(r.kernel == row.kernel and r.dt == dt and r.entry == row.entry and not lower_edge(r) for r in ROWS), "no row of ordinary size"
+        if y.numel() >= CENSUS_MIN_SHARE:
+            need, _, up = census(y, dt)
+            assert need >= (0.20 if dt == "bf16" else 0.01), f"need rounding: {need:.4f}"
+            assert up > 0, "no element tells truncation from rounding"
+    elif dt != "f32":
         need, tie, up = census(y, dt)
         assert tie >= 0.01 and tie * y.numel() >= 100, f"ties: {tie:.4f} of {y.numel()}"
         assert need >= (0.20 if dt == "bf16" else 0.01), f"need rounding: {need:.4f}"

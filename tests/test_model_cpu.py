@@ -26,6 +26,8 @@ def test_state_dict_layout_matches_reference():
 def test_constructor_raises_like_the_reference():
     trials = json.loads((GOLDEN / "validation.json").read_text())
     for name, t in trials.items():
+        if "input" in t:  # a trial of forward() on a small image (tests/test_cabi_cpu.py, tests/test_errors_gpu.py), not of the constructor
+            continue
         if t["raises"] is None:
             MewZoom(**t["kwargs"])
         else:

@@ -13,6 +13,7 @@ Gates
             rounded where the GPU rounds it), whose own error tests/test_oracle_golden.py ties to the reference's.
 """
 
+import functools
 import os
 
 import pytest
@@ -381,3 +382,118 @@ def test_conv3r_and_tile_walk_knobs_leave_the_bits_unchanged(dtype, monkeypatch)
         want = oracle.upscale(cfg, sd, x.float().cpu())
         matched = oracle.upscale(cfg, sd, x.float().cpu(), storage=dtype)
     lowp_gate_vs_matched(outs["default"], want, matched, f"conv3r model {TAG[dtype]}")
+
+
+# ---- the lower edge: every model at the smallest images ------------------------------------------------------------------------------
+# mz_forward takes H, W >= 8.  An 8 x 8 image has levels of 8 x 8, 4 x 4, 2 x 2 and 1 x 1: every family a model uses runs on tiles that
+# hold a handful of real pixels, one at level 4.  8 x 9 / 9 x 8 / 11 x 13 / 15 x 15 add floors and zero borders (15 -> 7 -> 3 -> 1: the
+# up-conv's 3 x 3 target is mostly border), 8 x 40 / 40 x 8 a 1 x 5 row and a 5 x 1 column at level 4.
+LOWER_SIZES = [(8, 8), (8, 9), (9, 8), (11, 13), (15, 15), (8, 40), (40, 8)]
+LOWER_B = 24  # different images: the three statistics of lowp_gate_vs_matched need samples (2X, 8 x 8: 18 432 output elements)
+
+
+def _config(r, ch, layers, hr):
+    cfg = {"upscale_ratio": r, "hidden_ratio": hr, "num_deg_features": 3}
+    for n, c, l in zip(("primary", "secondary", "tertiary", "quaternary"), ch, layers):
+        cfg[f"{n}_channels"] = c
+        cfg[f"{n}_layers"] = l
+    return cfg
+
+
+# a thin, wide 2X model (76 M parameters): conv3r, mix16b (C = 192) and mix16 (C = 384, 768) on the 4 x 4, 2 x 2 and 1 x 1 levels
+WIDE_CONFIG = _config(2, (96, 192, 384, 768), (2, 2, 2, 2), 2)
+LOWER_MODELS = {
+    "g1": "g1_2x_c16", "g3": "g3_4x_c16", "g4": "g4_8x_c16", "g8": "g8_c24_f5",  # 2X, 4X, 8X; pad channels
+    "g7": "g7_cfg1_2x_c48",                                                       # 48 channels: conv3t, conv3r_ragged
+    "c96": next(_config(r, ch, l, hr) for r, ch, l, hr, _ in FUZZ_CONFIGS if ch == (96, 96, 96, 96)),
+    "wide": WIDE_CONFIG,
+}
+
+
+@functools.lru_cache(maxsize=None)
+def lower_model(name):
+    """(config, state dict) of a model of LOWER_MODELS: a fixture's own weights, or hash-initialised ones."""
+    spec = LOWER_MODELS[name]
+    if isinstance(spec, str):
+        case = GoldenCase(spec)
+        return case.config, case.weights()
+    return spec, synth_state_dict(oracle.parameter_shapes(spec), seed=sum(ord(c) for c in name))
+
+
+@functools.lru_cache(maxsize=None)
+def lower_built(name, dtype):
+    cfg, sd = lower_model(name)
+    return build(cfg, sd, dtype)
+
+
+def lower_image(H, W, B=LOWER_B):
+    return synth_image(B, H, W, seed=1000 * H + W)
+
+
+@functools.lru_cache(maxsize=None)
+def lower_oracle(name, H, W, storage=None):
+    """(sr, qa) of the oracle on the LOWER_B images, computed once per model, size and mode and never changed."""
+    cfg, sd = lower_model(name)
+    with torch.inference_mode():
+        return oracle.forward(cfg, sd, lower_image(H, W)) if storage is None else oracle.forward(cfg, sd, lower_image(H, W), storage=storage)
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16, torch.float16], ids=["f32", "bf16", "f16"])
+@pytest.mark.parametrize("size", LOWER_SIZES, ids=lambda s: f"{s[0]}x{s[1]}")
+@pytest.mark.parametrize("name", list(LOWER_MODELS))
+def test_the_smallest_images_against_oracle(name, size, dtype):
+    """sr, up and qa of 24 different images of the smallest sizes: f32 at F32_TOL, 16-bit through lowp_gate_vs_matched; then batch
+    independence on that run: images 0, 11 and 23 equal their single-image runs bit for bit, and micro-batches of five (four full
+    ones and a ragged one of four) equal the whole."""
+    H, W = size
+    m = lower_built(name, dtype)
+    assert m.max_images_in_flight == 0
+    xg = lower_image(H, W).to("cuda", dtype)
+    want_sr, want_qa = lower_oracle(name, H, W)
+    sr, qa = m.forward(xg)
+    up = m.upscale(xg)
+    r = m.upscale_ratio
+    assert sr.shape == (LOWER_B, 3, r * H, r * W) and sr.dtype == dtype and qa.dtype == dtype
+    err = (sr.float().cpu() - want_sr).abs().max().item()
+    err_up = (up.float().cpu() - want_sr.clamp(0, 1)).abs().max().item()
+    qa_err = (qa.float().cpu() - want_qa).abs().max().item()
+    print(f"{name} {H}x{W} {dtype}: max-abs sr {err:.3e} up {err_up:.3e} qa {qa_err:.3e}")
+    if dtype == torch.float32:
+        assert err <= F32_TOL and err_up <= F32_TOL and qa_err <= F32_TOL, (err, err_up, qa_err)
+    else:
+        m_sr, m_qa = lower_oracle(name, H, W, dtype)
+        lowp_gate_vs_matched(sr, want_sr, m_sr, f"{name} {H}x{W} {TAG[dtype]} sr")
+        lowp_gate_vs_matched(up, want_sr.clamp(0, 1), m_sr.clamp(0, 1), f"{name} {H}x{W} {TAG[dtype]} up")
+        assert qa_err <= MATCHED_MAX_RATIO * (m_qa - want_qa).abs().max().item() + HALF_ULP_AT_1[dtype], qa_err
+    assert up.min().item() >= 0.0 and up.max().item() <= 1.0
+    for b in (0, 11, 23):
+        sr1, qa1 = m.forward(xg[b : b + 1])
+        assert torch.equal(sr1, sr[b : b + 1]) and torch.equal(qa1, qa[b : b + 1]), f"image {b} alone differs from image {b} of the batch"
+    try:
+        m.max_images_in_flight = 5
+        sr5, qa5 = m.forward(xg)
+    finally:
+        m.max_images_in_flight = 0
+    assert torch.equal(sr5, sr) and torch.equal(qa5, qa), "micro-batches of five differ from the whole batch"
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+def test_uint8_io_at_8x8_matches_float_path(dtype):
+    """test_uint8_io_matches_float_path_with_save_image_rounding's rule on 8 x 8 images."""
+    case = GoldenCase("g9_4x_c32")
+    m = build(case, case.weights(), dtype)
+    xu = (synth_image(LOWER_B, 8, 8, 92) * 255).round().to(torch.uint8)
+    got = m.upscale_uint8(xu.cuda())
+    assert got.dtype == torch.uint8 and got.shape == (LOWER_B, 3, 32, 32)
+    with torch.inference_mode():
+        want = oracle.upscale(case.config, case.weights(), xu.float() / 255)
+    want_u8 = (want * 255 + 0.5).clamp(0, 255).to(torch.uint8)
+    diff = (got.cpu().int() - want_u8.int()).abs()
+    print(f"uint8 I/O 8x8 {dtype}: max LSB diff {diff.max().item()}, mismatching {100.0 * (diff > 0).float().mean().item():.3f} %")
+    if dtype == torch.float32:
+        assert diff.max().item() <= 1 and (diff > 0).float().mean().item() < 1e-3  # only exact .5 ties may flip
+    else:
+        assert diff.max().item() <= 3
+    y = m.upscale((xu.float() / 255).to("cuda", dtype)).float()
+    if dtype == torch.float32:
+        assert torch.equal(got.cpu(), (y * 255 + 0.5).clamp(0, 255).to(torch.uint8).cpu())

@@ -10,7 +10,7 @@ import pytest
 import torch
 
 from oracle import mewzoom_oracle as oracle
-from golden_util import GOLDEN, MODEL_CASES, GoldenCase
+from golden_util import GOLDEN, LOWER_EDGE_CASES, MODEL_CASES, GoldenCase
 from ultrazoom_amd.synth import hash_uniform, synth_image, synth_state_dict
 
 # fp32 CPU vs fp32 CPU of the same maths in a different op order: round-off only.
@@ -64,6 +64,15 @@ def test_rounding_matched_mode_is_no_worse_than_the_reference_in_reduced_precisi
     assert got_max <= ref_max + 1e-9 and (case.sampled or abs(got_max - ref_max) < 1e-9)
 
 
+def test_the_lower_edge_fixture_covers_the_smallest_images():
+    """g11_lower_edge.npz (among MODEL_CASES above): 2X and 4X at 8 x 8 (a 1 x 1 level 4), 8 x 9 and 15 x 15 (a floor at every level, a
+    zero border at every up-conv), two images each."""
+    cases = [GoldenCase(n) for n in LOWER_EDGE_CASES]
+    assert set(LOWER_EDGE_CASES) <= set(MODEL_CASES)
+    assert {(c.config["upscale_ratio"], c.H, c.W) for c in cases} == {(r, h, w) for r in (2, 4) for h, w in ((8, 8), (8, 9), (15, 15))}
+    assert all(c.B == 2 and not c.sampled for c in cases)
+
+
 def test_ops():
     g = np.load(GOLDEN / "g6_ops.npz")
     x = synth_image(1, 9, 11, 21)
@@ -90,7 +99,19 @@ def test_ops():
 
 def test_validation_matches_reference():
     trials = json.loads((GOLDEN / "validation.json").read_text())
+    sizes = {name: t for name, t in trials.items() if "input" in t}
+    assert sizes["forward_8x8"]["raises"] is None and sizes["forward_7x7"]["raises"] == "RuntimeError"  # the 8-pixel minimum
+    for name, t in sizes.items():  # forward() on an image of that size: the reference's PixelCrush raises below 8 x 8
+        cfg = t["kwargs"]
+        sd, x = synth_state_dict(oracle.parameter_shapes(cfg), 1), synth_image(*t["input"], 1)
+        if t["raises"] is None:
+            oracle.forward(cfg, sd, x)
+        else:
+            with pytest.raises(RuntimeError):
+                oracle.forward(cfg, sd, x)
     for name, t in trials.items():
+        if name in sizes:
+            continue
         if t["raises"] is None:
             oracle.validate_config(t["kwargs"])
         else:

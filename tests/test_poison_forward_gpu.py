@@ -14,7 +14,7 @@ import torch
 
 from golden_util import GoldenCase
 from poison_util import Arena, room
-from test_model_gpu import FUZZ_CONFIGS
+from test_model_gpu import FUZZ_CONFIGS, lower_built, lower_image
 from ultrazoom_amd import MewZoom
 from ultrazoom_amd.synth import synth_image, synth_state_dict
 
@@ -88,10 +88,34 @@ MODELS = [
 ]
 
 
+# the smallest images (test_model_gpu.LOWER_MODELS): 8 x 8 has a 1 x 1 level 4; at 15 x 15 (7 x 7, 3 x 3, 1 x 1) every level has a floor
+# and every up-conv a zero border that is larger than the data
+LOWER = [
+    ("g1", ("f32", "bf16")),
+    ("g8", ("f32", "bf16")),          # pad channels at every level
+    ("g7", ("f32", "bf16")),          # conv3t_kernel, conv3r's ragged variant
+    ("c96", ("f32", "bf16", "f16")),  # conv3r_kernel and its fused variant
+    ("wide", ("f32", "bf16", "f16")),  # mix16b, mix16
+]
+LOWER_SIZES = [(8, 8), (15, 15)]
+
+
 @pytest.mark.parametrize("clamp", [0, 1])
 @pytest.mark.parametrize("name,dt", [(n, dt) for n, dts in MODELS for dt in dts])
 def test_forward_does_not_depend_on_the_workspace_s_contents(name, dt, clamp):
     m, engine, x = model_and_image(name, dt)
+    check_forward(m, engine, x, dt, clamp)
+
+
+@pytest.mark.parametrize("clamp", [0, 1])
+@pytest.mark.parametrize("size", LOWER_SIZES, ids=lambda s: f"{s[0]}x{s[1]}")
+@pytest.mark.parametrize("name,dt", [(n, dt) for n, dts in LOWER for dt in dts])
+def test_forward_of_the_smallest_images_does_not_depend_on_the_workspace_s_contents(name, dt, size, clamp):
+    m = lower_built(name, DTYPES[dt])
+    check_forward(m, m._get_engine(torch.empty(0, dtype=DTYPES[dt], device="cuda")), lower_image(*size, B=3), dt, clamp)
+
+
+def check_forward(m, engine, x, dt, clamp):
     dtype = DTYPES[dt]
     B, _, H, W = x.shape
     r, F = engine.config["upscale_ratio"], engine.config["num_deg_features"]

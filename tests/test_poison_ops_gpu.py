@@ -8,7 +8,8 @@ row of CASES runs three times:
   (c) for B = 3: images 0 and 2 of every activation / image input are NaN throughout, pad channels included: image 1 of the output
       has the bits of (a).  A halo, unit or plane read that crosses into a neighbouring image meets zero padding weights in (a),
       where garbage x 0 = 0 hides it; NaN x 0 = NaN does not.
-Every comparison between runs is an equality.  mz_op_final runs with clamp = 0: a clamp built from min / max may swallow a NaN."""
+Every comparison between runs is an equality.  mz_op_final runs with clamp = 0: a clamp built from min / max may swallow a NaN.
+TINY_CASES are the same row groups on the smallest images: 1 x 1, a single row, a single column, 2 x 3, and sixteen one-pixel images."""
 
 import ctypes
 import re
@@ -91,6 +92,59 @@ for s in [(2, 9, 11, 16), (1, 8, 8, 24)]:
 for s in [(2, 9, 11, 16, 2), (1, 16, 24, 32, 8)]:                                      # B, H, W (conv grid), cin, R
     add("final", s, {"f32": "conv3w", "bf16": "conv_kernel", "f16": "conv_kernel"}, dts=ALL)
 add("film", (3, 9, 33, 64, 40, 1), "conv3s")                                           # B, H, W, cin, cout, silu
+
+# ---- the lower edge: the same channel counts, knobs and dtypes on the smallest images ------------------------------------------------
+# 1 x 1 (a tile of one real pixel inside a halo that is out of range everywhere else), a single row, a single column and 2 x 3, B = 3
+# for the NaN-neighbour run; 1 x 1 once more with B = 16: sixteen one-pixel tiles outnumber eight workgroups, a tile list names sixteen
+# images and one 32-pixel unit of mix16 spans them all.  Every expected name is the host's choice at that size:
+#   - 8 x 40 tiles pad fewer pixels than 8 x 48 ones on every image this small, so the rows of conv3r's 8 x 48 variant run conv3r_8x40;
+#   - a 9 x 1 column would take two 8 x 40 tiles, more padding than one 16 x 32 tile of conv3s: the plain conv3r rows (and their D2S)
+#     run conv3s there.  The choice of conv3r_ragged, conv3r_fused, conv3t and conv3t_fused does not depend on H and W;
+#   - Cin = 112 reaches conv3p only where the tiles outnumber the eight workgroups (B = 16); the B = 3 rows run conv3w.
+TINY = [(3, 1, 1), (16, 1, 1), (3, 1, 9), (3, 9, 1), (3, 2, 3)]
+COLUMN = (3, 9, 1)
+
+
+def add_tiny(entry, rest, kernel, dts=LOW, env=None, other=None, geos=TINY, tail=lambda H, W: ()):
+    """One row per geometry and dtype (no twin: B = 3 is in the list).  `other`: geometry -> the family chosen there instead."""
+    for g in geos:
+        k = (other or {}).get(g, kernel)
+        for dt in dts:
+            CASES.append((entry, g + tuple(rest) + tuple(tail(g[1], g[2])), dict(env or {}), dt, k[dt] if isinstance(k, dict) else k))
+
+
+N_TINY_START = len(CASES)
+add_tiny("conv", (96, 96, 0), "conv3r_8x40", other={COLUMN: "conv3s"})
+add_tiny("conv", (96, 96, 0), "conv3s", env={"MZ_NO_R": "1"})
+add_tiny("conv", (128, 96, 1), "conv3r_8x40", other={COLUMN: "conv3s"})
+add_tiny("conv", (48, 192, 1), "conv3r_ragged")
+add_tiny("d2s", (96, 192), "conv3r_8x40", other={COLUMN: "conv3s"}, tail=lambda H, W: (2 * H, 2 * W))
+add_tiny("d2s", (96, 192), "conv3r_8x40", other={COLUMN: "conv3s"}, tail=lambda H, W: (2 * H + 1, 2 * W + 1))  # 1 x 1 -> 3 x 3
+add_tiny("d2s", (96, 192), "conv3s", env={"MZ_NO_R": "1"}, tail=lambda H, W: (2 * H + 1, 2 * W + 1))
+add_tiny("conv_mix", (192, 96), "conv3r_fused")
+add_tiny("conv_mix", (192, 96), "conv3s_fused", env={"MZ_NO_R": "1"})
+add_tiny("conv", (96, 48, 0), "conv3t")
+add_tiny("conv", (96, 48, 0), "conv3s", env={"MZ_NO_T": "1"})
+add_tiny("conv_mix", (96, 40), "conv3t_fused")
+add_tiny("conv_mix", (96, 40), "conv3s_fused", env={"MZ_NO_T": "1"})
+add_tiny("conv", (16, 288, 1), "conv3p", dts=ALL, env={"MZ_PERSIST_WGS": "8"})
+add_tiny("conv", (112, 96, 0), "conv3w", dts=ALL, env={"MZ_PERSIST_WGS": "8"}, other={(16, 1, 1): "conv3p"})
+add_tiny("conv", (16, 48, 1), "conv3w", dts=ALL, env={"MZ_NO_PERSIST": "1"})
+add_tiny("conv_mix", (192, 96), "conv3w_fused", env={"MZ_NO_S16": "1"})
+add_tiny("conv", (24, 40, 0), "conv_kernel", dts=ALL, env={"MZ_NO_WIDE": "1"})
+add_tiny("crush", (24, 40), None, dts=ALL, geos=[(3, 2, 2), (3, 3, 3), (3, 2, 9)])      # floors land on 1 x 1 (and 1 x 4)
+add_tiny("mix", (24,), "conv_kernel_mix", dts=ALL)
+add_tiny("mix", (384,), {"f32": "conv_kernel_mix", "bf16": "mix16", "f16": "mix16"}, dts=ALL)
+add_tiny("mix", (192,), "mix16", env={"MZ_NO_MIX16B": "1"})
+add_tiny("mix", (192,), "mix16b")
+add_tiny("mix", (192,), "mix16b", env={"MZ_PERSIST_WGS": "8"})
+add_tiny("stem", (16,), None, dts=ALL, geos=[(3, 1, 1), (3, 2, 3)])
+# the head at the model's own minimum (an 8 x 8 conv grid at R = 2), and a 4 x 4 grid at R = 8: the skip image is 1 x 1, every bicubic
+# tap clamps to that one pixel
+add_tiny("final", (16, 2), {"f32": "conv3w", "bf16": "conv_kernel", "f16": "conv_kernel"}, dts=ALL, geos=[(3, 8, 8)])
+add_tiny("final", (32, 8), {"f32": "conv3w", "bf16": "conv_kernel", "f16": "conv_kernel"}, dts=ALL, geos=[(3, 4, 4)])
+add_tiny("film", (64, 40, 1), "conv3s", geos=[(3, 1, 1), (3, 2, 3)])
+TINY_CASES = CASES[N_TINY_START:]
 
 # the family a row is there for, where the library does not report one (conv_kernel in its 2x2 gather mode)
 FAMILY_OF_UNREPORTED = {"crush": "conv_kernel"}

@@ -54,6 +54,27 @@ def test_tap_tables_are_torchs_weight_matrix(axis, filt):
     assert worst <= 1e-14
 
 
+@pytest.mark.parametrize("filt", sorted(MODES))
+@pytest.mark.parametrize("shape", [((5, 1), (2, 1)), ((9, 7), (4, 1)), ((1, 7), (2, 3)), ((16, 16), (1, 1)), ((2, 2), (7, 9)), ((9, 7), (4, 3))],
+                         ids=lambda s: f"{s[0][0]}x{s[0][1]}to{s[1][0]}x{s[1][1]}")
+def test_the_gpu_tests_checker_is_torchs_weight_matrices(shape, filt):
+    """tests/test_resize_gpu.want64_of at the smallest shapes, outputs of one column included (which it runs transposed, around a fault
+    of torch's kernel), against out = My^T x Mx with torch's own weight matrices (interpolate of an identity, as above)."""
+    from test_resize_gpu import want64_of
+
+    (hin, win), (hout, wout) = shape
+
+    def matrix(n_in, n_out):  # [n_in, n_out]; n_out = 1: from the transposed identity as ONE ROW, so that no output of one column is asked for
+        eye = torch.eye(n_in, dtype=torch.float64)[None, None]
+        if n_out == 1:
+            return F.interpolate(eye.transpose(-1, -2), size=(1, n_in), mode=MODES[filt], antialias=True, align_corners=False)[0, 0].transpose(0, 1)
+        return F.interpolate(eye, size=(n_in, n_out), mode=MODES[filt], antialias=True, align_corners=False)[0, 0]
+
+    x = torch.rand((3, 3, hin, win), generator=torch.Generator().manual_seed(hin * win), dtype=torch.float64)
+    want = matrix(hin, hout).transpose(0, 1) @ x @ matrix(win, wout)
+    assert float((want64_of(x, (hout, wout), MODES[filt]) - want).abs().max()) <= 1e-14
+
+
 def test_the_formula_of_the_header_at_one_index():
     """64 -> 16 bicubic, i = 5: scale 4, support 8, center 22, first 14, count 16."""
     first, w = _ffi.resize_taps(64, 16, 0, 5)

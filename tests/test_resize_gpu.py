@@ -57,7 +57,14 @@ def as_double(x: torch.Tensor) -> torch.Tensor:
 
 
 def want64_of(x: torch.Tensor, size, filt: str) -> torch.Tensor:
-    return F.interpolate(as_double(x), size=tuple(size), mode=filt, antialias=True, align_corners=False)
+    """torch's float64 antialiased interpolate.  Its CPU kernel gives an output of ONE column and several rows wrong (5 x 1 -> 2 x 1: both
+    rows come out equal; it disagrees with its own weight matrices and with its own result for the transposed image, by 0.2 - 0.4 on
+    [0, 1] data), so such a size runs transposed: the filter is separable and the same on both axes, the function and the float64
+    arithmetic are the same.  tests/test_resize_cpu.py holds this checker to torch's weight matrices at those sizes."""
+    xd = as_double(x)
+    if size[1] == 1 and size[0] > 1:
+        return F.interpolate(xd.transpose(-1, -2).contiguous(), size=(1, size[0]), mode=filt, antialias=True, align_corners=False).transpose(-1, -2)
+    return F.interpolate(xd, size=tuple(size), mode=filt, antialias=True, align_corners=False)
 
 
 @lru_cache(maxsize=None)
@@ -101,6 +108,20 @@ def assert_within_gate(got: torch.Tensor, want64: torch.Tensor, dt: str, what: s
 @pytest.mark.parametrize("dt", sorted(DTYPES))
 @pytest.mark.parametrize("shape", SHAPES, ids=shape_id)
 def test_against_torchs_float64_interpolate(shape, dt, filt):
+    for B in (1, 3):
+        x = image(B, *shape[0], dt)
+        got = hip_resize(x.cuda(), shape[1], filter=filt)
+        assert_within_gate(got, checker(B, shape, dt, filt), dt, f"{shape_id(shape)} B={B} {dt} {filt}")
+
+
+# the lower edge: one pixel in, one pixel out, a single row, a single column, every tap clamped to one or two pixels
+SMALL_SHAPES = [((1, 1), (1, 1)), ((1, 1), (3, 5)), ((1, 7), (2, 3)), ((5, 1), (2, 1)), ((16, 16), (1, 1)), ((2, 2), (7, 9))]
+
+
+@pytest.mark.parametrize("filt", FILTERS)
+@pytest.mark.parametrize("dt", sorted(DTYPES))
+@pytest.mark.parametrize("shape", SMALL_SHAPES, ids=shape_id)
+def test_the_smallest_shapes_against_torchs_float64_interpolate(shape, dt, filt):
     for B in (1, 3):
         x = image(B, *shape[0], dt)
         got = hip_resize(x.cuda(), shape[1], filter=filt)

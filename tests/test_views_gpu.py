@@ -137,6 +137,17 @@ def test_window_of_2x_equals_that_part_of_dense(kind, window):
 
 
 @pytest.mark.parametrize("kind", KINDS)
+def test_one_pixel_window_at_the_last_output_pixel_of_an_8x9_image(kind):
+    """The smallest image the model takes but for one column (levels 8 x 9, 4 x 4, 2 x 2, 1 x 1), the smallest window, the largest origin."""
+    x, dense = pixels_and_dense("g1_2x_c16", kind, 2, 8, 9, 43)
+    assert dense.shape == (2, 3, 16, 18)
+    check_window(model("g1_2x_c16", kind), x, dense, (15, 17, 1, 1))
+    out = sentinel_like(dense, dense.shape)
+    model("g1_2x_c16", kind).upscale_into(x, out)
+    assert torch.equal(out, dense)
+
+
+@pytest.mark.parametrize("kind", KINDS)
 def test_window_of_4x_with_an_odd_origin(kind):
     case = GoldenCase("g3_4x_c16")
     x, dense = pixels_and_dense("g3_4x_c16", kind, case.B, case.H, case.W, 42)
