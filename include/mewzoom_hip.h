@@ -127,7 +127,8 @@ int mz_forward_u8(mz_handle* h, const uint8_t* x, uint8_t* out_sr, float* out_qa
  * and out, or between elements of out, is the caller's responsibility and is not checked (beyond refusing an output stride of 0;
  * mz_blur, mz_noise and mz_jpeg also compare the two byte ranges).
  *
- * THE VIEW REFUSALS.  Every entry that takes views (mz_forward_view, mz_metrics, mz_resize, mz_blur, mz_noise, mz_jpeg) returns
+ * THE VIEW REFUSALS.  Every entry that takes views (mz_forward_view, mz_metrics, mz_resize, mz_blur, mz_noise, mz_jpeg, mz_dihedral,
+ * mz_ensemble_add, mz_ensemble_finish) returns
  * MZ_ERR_INVALID_ARGUMENT, before anything touches the GPU, for: a null view or null data; an `elem` outside the entry's codes; a view
  * that is WRITTEN whose channel, row or column stride is 0, or whose image stride is 0 when B > 1 (strides of a view that is only read
  * may be 0, and any stride may be negative); where the entry takes a window: one that is empty or not inside the result.  Each entry
@@ -290,6 +291,52 @@ int mz_jpeg(const mz_image_view* x, const mz_image_view* out, int elem, int B, i
 int mz_debug_blur_weights(double sigma, double* w, int cap);
 int mz_debug_jpeg_qtable(int quality, uint8_t* luma, uint8_t* chroma);
 int mz_debug_philox(const uint32_t counter[4], const uint32_t key[2], uint32_t out[4]);
+
+/* ---- the dihedral transforms and the geometric self-ensemble: no reference counterpart in `model.py`; the flip is the reference's
+ *      `RandomHorizontalFlip` augmentation (pretrain.py:148), the ensemble the "+" variant of the super-resolution papers: the model runs
+ *      on the 8 orientations of the input, each result is turned back, the results are averaged (ultrazoom_amd/ensemble.py:
+ *      upscale_ensemble; MewZoom.upscale_ensemble) ------------------------------------------------------------------------------------
+ * Stateless like mz_resize: every call enqueues on the given stream, never synchronises, allocates nothing and uses no atomics.  Images
+ * are VIEWS (mz_image_view above) of one element type, elem 0..2 = mz_dtype, 3 = uint8.  All element offsets are 64-bit: there is no
+ * size guard beyond the bounds below.  The touch contract of the workspace paragraph above holds.
+ *
+ * THE TRANSFORM.  Orientation k = 0..7 has three bits: bit 0 reverses columns, bit 1 reverses rows, bit 2 exchanges rows and columns and
+ * is applied LAST.  For x of [B,3,H,W]:   T(x, k)[b, c, i, j] = x[b, c, si, sj]   with (p, q) = (j, i) if k & 4 else (i, j),
+ * si = H - 1 - p if k & 2 else p,   sj = W - 1 - q if k & 1 else q;   T(x, k) is [B,3,W,H] when k & 4.  In torch: flip(2) if k & 2,
+ * flip(3) if k & 1, then transpose(2, 3) if k & 4.  inverse(k) = k for k < 4, else 4 | (k & 1) << 1 | (k & 2) >> 1, and
+ * T(T(x, k), inverse(k)) == x.  The transform moves elements and never changes them: bit patterns survive, NaN payloads and -0
+ * included.  (ultrazoom_amd/csrc/mz_dihedral.h is the one statement of it, compiled by the kernels and the host alike.)
+ *
+ * mz_dihedral          out, a view of [B,3,H',W'], receives T(x, k) of x, a view of [B,3,H,W].  Dense and strided views give the same
+ *                      bits.  Refuses the view refusals above (elem outside 0..3), and: B < 1 or > 65535; H or W < 1 or > 2^28; k outside
+ *                      0..7; x and out whose byte ranges (each from its own shape) overlap or do not fit in signed 64-bit addresses.
+ *
+ * THE ENSEMBLE.  The workspace is the accumulator: a dense float32 [B,3,H,W], 12 B H W bytes, where H x W is the size of the RESULT (the
+ * orientation-0 shape).  One ensemble is: mz_ensemble_add for each pass result in call order, the first with first != 0; then
+ * mz_ensemble_finish.
+ *
+ * mz_ensemble_add      y is a view of a pass result in ITS orientation: [B,3,W,H] when k & 4, else [B,3,H,W].  acc (+)= value(T(y,
+ *                      inverse(k))); first != 0 stores instead of adding, so the workspace may hold anything beforehand, NaN bytes included.
+ * mz_ensemble_finish   out, a view of the window {y0, x0, h, w} of the [B,3,H,W] result (or of all of it when window is NULL; as for
+ *                      mz_resize), receives the mean of the n = 1, 2, 4 or 8 results added.
+ *
+ * The arithmetic, fixed so that a torch restatement gives the same bits.  Float types: value = the element as float32; the accumulator is
+ * float32, acc_0 = v_0, acc_i = acc_(i-1) + v_i in call order; finish = acc * (1.0f / n) (exact: n is a power of two), then the clamp to
+ * [0, 1] when clamp != 0, then one rounding to the stored type.  uint8: value = the raw sample 0..255 as float32 (not v / 255: sums up to
+ * 2040 are exact integers); finish = (2 sum + n) / (2 n) in integer arithmetic, which rounds half up; clamp has nothing to do.
+ *
+ * Both refuse the view refusals above (elem outside 0..3; y is only read, out is written), and: B < 1 or > 65535; H or W < 1 or > 2^28;
+ * an accumulator beyond 2^62 bytes; a view whose byte range overlaps the accumulator's or does not fit in signed 64-bit addresses;
+ * mz_ensemble_add: k outside 0..7; mz_ensemble_finish: n outside {1, 2, 4, 8}.  A null or short workspace is MZ_ERR_WORKSPACE_TOO_SMALL. */
+/* Host only: inverse(k), negative outside 0..7. */
+int mz_dihedral_inverse(int k);
+int mz_dihedral(const mz_image_view* x, const mz_image_view* out, int elem, int B, int H, int W, int k, void* hip_stream);
+/* Host only. */
+int mz_ensemble_workspace_bytes(int B, int H, int W, size_t* bytes);
+int mz_ensemble_add(const mz_image_view* y, int elem, int B, int H, int W, int k, int first, void* workspace, size_t workspace_bytes,
+                    void* hip_stream);
+int mz_ensemble_finish(const mz_image_view* out, int elem, int B, int H, int W, int n, int clamp, const int32_t window[4],
+                       void* workspace, size_t workspace_bytes, void* hip_stream);
 
 /* ---- introspection ------------------------------------------------------------------------ */
 const char* mz_last_error(void);

@@ -98,6 +98,17 @@ def _declare(lib) -> None:
     lib.mz_debug_jpeg_qtable.restype = c_int
     lib.mz_debug_philox.argtypes = [POINTER(c_uint32), POINTER(c_uint32), POINTER(c_uint32)]
     lib.mz_debug_philox.restype = c_int
+    lib.mz_dihedral_inverse.argtypes = [c_int]
+    lib.mz_dihedral_inverse.restype = c_int
+    lib.mz_dihedral.argtypes = [POINTER(MzImageView), POINTER(MzImageView), c_int, c_int, c_int, c_int, c_int, c_void_p]
+    lib.mz_dihedral.restype = c_int
+    lib.mz_ensemble_workspace_bytes.argtypes = [c_int, c_int, c_int, POINTER(c_size_t)]
+    lib.mz_ensemble_workspace_bytes.restype = c_int
+    lib.mz_ensemble_add.argtypes = [POINTER(MzImageView), c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p]
+    lib.mz_ensemble_add.restype = c_int
+    lib.mz_ensemble_finish.argtypes = [POINTER(MzImageView), c_int, c_int, c_int, c_int, c_int, c_int, POINTER(c_int32), c_void_p, c_size_t,
+                                       c_void_p]
+    lib.mz_ensemble_finish.restype = c_int
     lib.mz_padded_channels.argtypes = [c_int]
     lib.mz_op_conv.argtypes = [c_int, c_int, c_void_p, c_void_p, c_void_p, c_float, c_void_p] + [c_int] * 8 + [c_void_p]
     lib.mz_op_conv_film.argtypes = [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p] + [c_int] * 6 + [c_void_p]
@@ -287,6 +298,37 @@ def philox(counter, key):
     out = (c_uint32 * 4)()
     check(lib().mz_debug_philox((c_uint32 * 4)(*counter), (c_uint32 * 2)(*key), out))
     return [int(v) for v in out]
+
+
+def dihedral_inverse(k: int) -> int:
+    """mz_dihedral_inverse (host only): the orientation that undoes orientation k; negative outside 0..7."""
+    return int(lib().mz_dihedral_inverse(int(k)))
+
+
+def dihedral(x_ptr, x_strides, out_ptr, out_strides, elem, B, H, W, k, stream) -> None:
+    """mz_dihedral: out, a view of [B,3,H',W'], receives T(x, k) of the [B,3,H,W] view x; the views as for `resize`."""
+    xv, ov = view(x_ptr, x_strides), view(out_ptr, out_strides)
+    check(lib().mz_dihedral(byref(xv), byref(ov), int(elem), B, H, W, int(k), c_void_p(stream)))
+
+
+def ensemble_workspace_bytes(B: int, H: int, W: int) -> int:
+    out = c_size_t()
+    check(lib().mz_ensemble_workspace_bytes(B, H, W, byref(out)))
+    return int(out.value)
+
+
+def ensemble_add(y_ptr, y_strides, elem, B, H, W, k, first, ws_ptr, ws_bytes, stream) -> None:
+    """mz_ensemble_add: the pass result y, a view in ITS orientation ([B,3,W,H] when k & 4), turned back and stored in (`first`) or added
+    to the float32 accumulator of the [B,3,H,W] result."""
+    yv = view(y_ptr, y_strides)
+    check(lib().mz_ensemble_add(byref(yv), int(elem), B, H, W, int(k), int(bool(first)), c_void_p(ws_ptr), ws_bytes, c_void_p(stream)))
+
+
+def ensemble_finish(out_ptr, out_strides, elem, B, H, W, n, clamp, window, ws_ptr, ws_bytes, stream) -> None:
+    """mz_ensemble_finish: the mean of the n results added, into out (a view of the window, as for `resize`)."""
+    ov = view(out_ptr, out_strides)
+    win = (c_int32 * 4)(*[int(v) for v in window]) if window is not None else None
+    check(lib().mz_ensemble_finish(byref(ov), int(elem), B, H, W, int(n), int(bool(clamp)), win, c_void_p(ws_ptr), ws_bytes, c_void_p(stream)))
 
 
 class Handle:

@@ -1,8 +1,10 @@
-// Stateless image entry points of libmewzoom_hip.so: image-quality metrics, antialiased resizing, the degradation chain, and the
+// Stateless image entry points of libmewzoom_hip.so: image-quality metrics, antialiased resizing, the degradation chain, the dihedral
+// transforms with the self-ensemble accumulator, and the
 // host-only mz_debug_* views of what their kernels are handed.  Every check comes before anything touches the GPU.
 #include <cstring>
 
 #include "mz_degrade.h"
+#include "mz_dihedral.h"
 #include "mz_err.h"
 #include "mz_metrics.h"
 #include "mz_resize.h"
@@ -180,4 +182,88 @@ extern "C" int mz_debug_philox(const uint32_t counter[4], const uint32_t key[2],
     if (!counter || !key || !out) return fail(MZ_ERR_INVALID_ARGUMENT, "null argument");
     philox4x32_10(counter[0], counter[1], counter[2], counter[3], key[0], key[1], out);
     return MZ_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// the dihedral transforms and the self-ensemble accumulator (mz_dihedral.h): no reference counterpart in model.py; the flip is the
+// reference's RandomHorizontalFlip (pretrain.py:148).  Stateless like mz_resize.  Every check comes before anything touches the GPU.
+// ------------------------------------------------------------------------------------------------
+static const ViewRules kDihedralOut = {3, MZ_ELEM_NAMES_0_3, /*second_is_output*/ true, /*batch_bound*/ true, /*side_bound*/ true};
+static const ViewRules kDihedralIn = {3, MZ_ELEM_NAMES_0_3, /*second_is_output*/ false, /*batch_bound*/ true, /*side_bound*/ true};
+
+static int check_orientation(int k) {
+    return dihedral_valid(k) ? MZ_OK : fail(MZ_ERR_INVALID_ARGUMENT, "orientation k must be 0..7, got %d", k);
+}
+
+// the two byte ranges of a call, each from its own shape
+static int check_ranges_apart(const mz_image_view* a, int elem_a, int Ha, int Wa, const mz_image_view* b, int elem_b, int Hb, int Wb, int B,
+                              const char* what) {
+    long long al, ah, bl, bh;
+    if (!view_extent(a, elem_a, B, Ha, Wa, &al, &ah) || !view_extent(b, elem_b, B, Hb, Wb, &bl, &bh))
+        return fail(MZ_ERR_INVALID_ARGUMENT, "a view's byte range does not fit in 63 bits");
+    if (al < bh && bl < ah) return fail(MZ_ERR_INVALID_ARGUMENT, "%s overlap: this entry does not work in place", what);
+    return MZ_OK;
+}
+
+// the accumulator of a B x H x W result as a dense float32 view, after the workspace check
+static int ensemble_accumulator(int B, int H, int W, void* workspace, size_t workspace_bytes, mz_image_view* acc) {
+    size_t need = 0;
+    if (!ensemble_workspace_bytes(B, H, W, &need)) return fail(MZ_ERR_INVALID_ARGUMENT, "an accumulator of %d x 3 x %d x %d float32 is beyond 2^62 bytes", B, H, W);
+    if (const Refusal r = check_workspace(workspace, workspace_bytes, need)) return fail(r);
+    acc->data = workspace;
+    acc->stride[0] = 3LL * H * W; acc->stride[1] = (long long)H * W; acc->stride[2] = W; acc->stride[3] = 1;
+    return MZ_OK;
+}
+
+extern "C" int mz_dihedral_inverse(int k) { return dihedral_inverse(k); }
+
+extern "C" int mz_dihedral(const mz_image_view* x, const mz_image_view* out, int elem, int B, int H, int W, int k, void* hip_stream) {
+    DihedralArgs a = {};
+    if (const Refusal r = check_views(x, out, kDihedralOut, elem, B, H, W, &a.src, &a.dst)) return fail(r);
+    if (int rc = check_orientation(k)) return rc;
+    int Ho, Wo;
+    dihedral_shape(k, H, W, &Ho, &Wo);
+    if (int rc = check_ranges_apart(x, elem, H, W, out, elem, Ho, Wo, B, "x and out")) return rc;
+    a.elem = elem; a.mode = DM_COPY; a.B = B; a.Hs = H; a.Ws = W; a.k = k;
+    return launched("dihedral launch", [&] { return (hipError_t)launch_dihedral(a, hip_stream); });
+}
+
+extern "C" int mz_ensemble_workspace_bytes(int B, int H, int W, size_t* bytes) {
+    if (!bytes) return fail(MZ_ERR_INVALID_ARGUMENT, "null argument");
+    if (B < 1 || B > 65535 || H < 1 || W < 1 || H > (1 << 28) || W > (1 << 28))
+        return fail(MZ_ERR_INVALID_ARGUMENT, "need 1 <= B <= 65535 and 1 <= H, W <= 2^28 (got %d, %d, %d)", B, H, W);
+    if (!ensemble_workspace_bytes(B, H, W, bytes)) return fail(MZ_ERR_INVALID_ARGUMENT, "an accumulator of %d x 3 x %d x %d float32 is beyond 2^62 bytes", B, H, W);
+    return MZ_OK;
+}
+
+extern "C" int mz_ensemble_add(const mz_image_view* y, int elem, int B, int H, int W, int k, int first, void* workspace, size_t workspace_bytes,
+                               void* hip_stream) {
+    DihedralArgs a = {};
+    StridedView unused;
+    if (const Refusal r = check_views(y, y, kDihedralIn, elem, B, H, W, &a.src, &unused)) return fail(r);
+    if (int rc = check_orientation(k)) return rc;
+    mz_image_view acc;
+    if (int rc = ensemble_accumulator(B, H, W, workspace, workspace_bytes, &acc)) return rc;
+    int Hy, Wy;  // y lies in ITS orientation: T(result, k)
+    dihedral_shape(k, H, W, &Hy, &Wy);
+    if (int rc = check_ranges_apart(y, elem, Hy, Wy, &acc, EL_F32, H, W, B, "y and the workspace")) return rc;
+    a.dst.data = acc.data;
+    for (int i = 0; i < 4; ++i) a.dst.s[i] = acc.stride[i];
+    a.elem = elem; a.mode = DM_ACC; a.B = B; a.Hs = Hy; a.Ws = Wy; a.k = dihedral_inverse(k); a.first = first != 0;
+    return launched("ensemble add launch", [&] { return (hipError_t)launch_dihedral(a, hip_stream); });
+}
+
+extern "C" int mz_ensemble_finish(const mz_image_view* out, int elem, int B, int H, int W, int n, int clamp, const int32_t window[4],
+                                  void* workspace, size_t workspace_bytes, void* hip_stream) {
+    FinishArgs a = {};
+    StridedView unused;
+    if (const Refusal r = check_views(out, out, kDihedralOut, elem, B, H, W, &unused, &a.out)) return fail(r);
+    if (n != 1 && n != 2 && n != 4 && n != 8) return fail(MZ_ERR_INVALID_ARGUMENT, "n must be 1, 2, 4 or 8 orientations, got %d", n);
+    if (const Refusal r = check_window(window, H, W, &a.y0, &a.x0, &a.h, &a.w)) return fail(r);
+    mz_image_view acc;
+    if (int rc = ensemble_accumulator(B, H, W, workspace, workspace_bytes, &acc)) return rc;
+    if (int rc = check_ranges_apart(out, elem, a.h, a.w, &acc, EL_F32, H, W, B, "out and the workspace")) return rc;
+    a.acc = (const float*)workspace;
+    a.elem = elem; a.B = B; a.H = H; a.W = W; a.n = n; a.clamp = clamp != 0;
+    return launched("ensemble finish launch", [&] { return (hipError_t)launch_ensemble_finish(a, hip_stream); });
 }

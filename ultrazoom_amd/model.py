@@ -403,6 +403,16 @@ class MewZoom(nn.Module, PyTorchModelHubMixin):
         sr = self.upscale_uint8(x) if x.dtype == torch.uint8 else self.upscale(x)
         return resize(sr, size, filter=filter, clamp=True, out=out)
 
+    @torch.inference_mode()
+    def upscale_ensemble(self, x: Tensor, n: int = 8, out: Optional[Tensor] = None, tile: Optional[Tuple[int, int]] = None) -> Tensor:
+        """The geometric self-ensemble of ``upscale`` (``upscale_uint8`` for uint8 tensors): the mean, clamped to [0, 1], of the results
+        of the orientations ``k = 0 .. n - 1`` of ``x`` (n = 2: with the mirror, 4: the four flips, 8: with their transpositions), each
+        turned back -- ``ultrazoom_amd.ensemble.upscale_ensemble(self, x, n, out, tile)``, which states the arithmetic.  ``n = 1`` is
+        ``upscale(x)`` itself.  No reference counterpart (the "+" variant of the super-resolution papers)."""
+        from .ensemble import upscale_ensemble
+
+        return upscale_ensemble(self, x, n=n, out=out, tile=tile)
+
     # ---- checkpoint ingestion (test_compare.py:32-45 of the reference) -------------------------
     def load_training_checkpoint(self, state_dict: Dict[str, Tensor], lora_alpha: Optional[float] = None) -> None:
         """Loads a raw training checkpoint: strips ``_orig_mod.`` prefixes left by torch.compile, bakes weight-norm

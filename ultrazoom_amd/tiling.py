@@ -37,7 +37,7 @@ def receptive_field(config: dict) -> int:
 
 
 @torch.inference_mode()
-def upscale_tiled(model, x: Tensor, tile: Tuple[int, int] = (512, 512), halo: Optional[int] = None) -> Tensor:
+def upscale_tiled(model, x: Tensor, tile: Tuple[int, int] = (512, 512), halo: Optional[int] = None, out: Optional[Tensor] = None) -> Tensor:
     """`model.upscale(x)` computed tile by tile.  `tile` = core size in low-resolution pixels (rounded up to multiples
     of 8); `halo` defaults to `receptive_field(config)`; a smaller halo is refused, because the result would no
     longer equal the untiled one.
@@ -45,7 +45,10 @@ def upscale_tiled(model, x: Tensor, tile: Tuple[int, int] = (512, 512), halo: Op
     A model that offers `upscale_into` (MewZoom) gets one call per tile with the haloed slice of `x` as an input view,
     the tile's core as the output window and the core's place in the result as the output view: no slice is copied, no
     haloed tile is written anywhere, and uint8 input gives `model.upscale_uint8(x)`.  Any other object with `upscale`
-    is called on contiguous slices and the cores are copied out, as before."""
+    is called on contiguous slices and the cores are copied out, as before.
+
+    `out` ([B, 3, rH, rW], any strides, x's dtype and device) receives the result in place of a new tensor (`upscale_ensemble` passes
+    its one pass scratch)."""
     if x.dim() != 4 or x.shape[1] != 3:
         raise ValueError("expected a [B, 3, H, W] tensor")
     cfg = model._cfg
@@ -56,7 +59,10 @@ def upscale_tiled(model, x: Tensor, tile: Tuple[int, int] = (512, 512), halo: Op
     th, tw = (max(8, (int(t) + 7) // 8 * 8) for t in tile)
     B, _, H, W = x.shape
     r = cfg["upscale_ratio"]
-    out = torch.empty((B, 3, H * r, W * r), dtype=x.dtype, device=x.device)
+    if out is None:
+        out = torch.empty((B, 3, H * r, W * r), dtype=x.dtype, device=x.device)
+    elif tuple(out.shape) != (B, 3, H * r, W * r) or out.dtype != x.dtype or out.device != x.device:
+        raise ValueError(f"out should be a {(B, 3, H * r, W * r)} {x.dtype} tensor on {x.device}, got {tuple(out.shape)} {out.dtype} on {out.device}")
     into = getattr(model, "upscale_into", None)
     for y0 in range(0, H, th):
         y1 = min(H, y0 + th)
