@@ -9,6 +9,8 @@
 
 from __future__ import annotations
 
+from functools import lru_cache
+
 import numpy as np
 import torch
 import torch.nn.functional as F
@@ -207,3 +209,30 @@ def jpeg_expected(x: torch.Tensor, quality: int, dtype: torch.dtype):
     t = torch.from_numpy(out)
     want = t.to(torch.uint8) if dtype == torch.uint8 else (t.float() / 255.0).to(dtype)
     return want, torch.from_numpy(unsure)[:, None], share
+
+
+# ---- the cases of tests/test_degrade_gpu.py, shared with tests/test_degrade_cpu.py and tests/test_poison_degrade_gpu.py ---------------------
+SHAPES = [(16, 16), (17, 33), (31, 15), (37, 45), (64, 80)]
+DTYPES = {"f32": torch.float32, "bf16": torch.bfloat16, "f16": torch.float16, "u8": torch.uint8}
+ELEM = {"f32": 0, "bf16": 1, "f16": 2, "u8": 3}
+BLUR_SIGMAS = (0.2, 0.34, 1.0, 2.5)
+NOISE_SIGMAS = (0.05, 0.3)
+QUALITIES = (20, 50, 90, 100)
+BATCH, SEED, OFFSET = 3, 1234, 5
+
+
+def shape_id(s):
+    return f"{s[0]}x{s[1]}"
+
+
+@lru_cache(maxsize=None)
+def image(B: int, H: int, W: int, dt: str, seed: int = 21) -> torch.Tensor:
+    """uniform noise in [0, 1], rounded to the element type, on the CPU"""
+    x = torch.rand((B, 3, H, W), generator=torch.Generator().manual_seed(seed + 1000 * B + H * W), dtype=torch.float32)
+    return (x * 255.0).round().to(torch.uint8) if dt == "u8" else x.to(DTYPES[dt])
+
+
+def hip():
+    from ultrazoom_amd import degrade
+
+    return degrade

@@ -22,8 +22,8 @@ import torch
 import torch.nn.functional as F
 
 from gpu_util import DTYPES
+from op_cases import CASES, TINY_CASES, fields
 from oracle import mewzoom_oracle as oracle
-from test_poison_ops_gpu import CASES, TINY_CASES
 
 SAT_HI, SAT_LO = 32.0, -100.0
 MAX_EXCLUDED = 0.02
@@ -44,7 +44,7 @@ PERSISTENT = {"conv3p", "conv3s", "conv3s_fused", "conv3r", "conv3r_8x40", "conv
 
 
 def _rows():
-    """tests/test_poison_ops_gpu.CASES (the smallest shapes at which each family is chosen, pinned by the MZ_* knobs), conv and film
+    """tests/op_cases.CASES (the smallest shapes at which each family is chosen, pinned by the MZ_* knobs), conv and film
     with silu = 0 -- SiLU is not exact --, plus two shapes of this table's own.  conv3r's ragged variant exists only as conv1 + SiLU
     (choose_conv3, mz_select.h): its rows keep SiLU, on data that saturate it, and run once more without, on whatever family the host
     then chooses."""
@@ -210,10 +210,11 @@ def _saturate(ex: Exact, t64, one64, zero64, soft64):
 def _build(entry, args, dt, silu) -> Exact:
     ex = Exact()
     d = lambda t: t.double()
-    B, H, W = args[:3]
+    a = fields(entry, args)
+    B, H, W = a.B, a.H, a.W
     big = dt == "f16" or bool(silu)
     if entry in ("conv", "film", "d2s", "crush"):
-        cin, cout = args[3:5]
+        cin, cout = a.cin, a.cout
         k = 2 if entry == "crush" else 3
         nterms = taps_inside(H, W, k) * cin * (4 if entry == "film" else 1)  # film: |gamma| <= 2 doubles the spread, as four times the terms would
         full = k * k * cin * (4 if entry == "film" else 1)
@@ -222,7 +223,7 @@ def _build(entry, args, dt, silu) -> Exact:
         kw = {"stride": 2} if entry == "crush" else {"padding": 1}
         ex.sums["conv"] = _abs_sum(d(x), d(w), **kw)
         if entry == "d2s":
-            ex.C, ex.y64 = cout // 4, oracle.fit_to(oracle.subpixel_conv(d(x), d(w)), args[5:7])
+            ex.C, ex.y64 = cout // 4, oracle.fit_to(oracle.subpixel_conv(d(x), d(w)), (a.Hout, a.Wout))
         elif entry == "film":
             gamma, beta = choice((B, cout), [-1.0, 0.5, 1.0, 2.0], 103), ints((B, cout), 8, 104)
             ex.inputs.update(gamma=gamma, beta=beta)
@@ -234,14 +235,14 @@ def _build(entry, args, dt, silu) -> Exact:
                 y = ex.y64
                 _saturate(ex, y, y, torch.zeros_like(y), F.silu(y))
     elif entry == "stem":
-        c = args[3]
+        c = a.C
         x = ints((B, 3, H, W), INT_MAX[dt], 105).abs()
         w, b = choice((c, 3, 1, 1), [-2.0, -1.0, -0.5, 0.5, 1.0, 2.0], 106), ints((c,), 8, 107)
         ex.inputs = {"x": x, "w": w, "b": b}
         ex.C, ex.y64 = c, F.conv2d(d(x), d(w), d(b))
         ex.sums["stem"] = F.conv2d(d(x), d(w).abs(), d(b).abs()).max().item()
     elif entry == "final":
-        cin, R = args[3:5]
+        cin, R = a.cin, a.R
         feat, w = ints((B, cin, H, W), conv_ax(taps_inside(H, W) * cin, dt, big, 9 * cin), 108), ints((12, cin, 3, 3), AW, 109)
         img = torch.zeros(B, 3, 2 * H // R, 2 * W // R)  # the bicubic term is exactly zero
         ex.inputs = {"feat": feat, "img": img, "w": w}
@@ -250,14 +251,14 @@ def _build(entry, args, dt, silu) -> Exact:
     elif entry in ("mix", "conv_mix"):
         ax = INT_MAX[dt]  # x: every integer the type holds
         if entry == "mix":
-            c = args[3]
+            c = a.C
             # z: multiples of 4, so that (x + z) / 2 = x / 2 + 2 zi needs rounding (exact, tie or neither by x mod 4) in both 16-bit types
             az = 255 if dt == "bf16" else 511
             x, z = ints((B, c, H, W), ax, 110), ints((B, c, H, W), az, 111, 4.0)
             ex.inputs = {"in0": x, "in1": z}
             z64, wname, mean_z = d(z), "w", 2.0 * az
         else:
-            cin, c = args[3:5]
+            cin, c = a.cin, a.cout
             nterms = taps_inside(H, W) * cin
             hid, x, w2 = ints((B, cin, H, W), conv_ax(nterms, dt, big, 9 * cin), 112), ints((B, c, H, W), ax, 113), ints((c, cin, 3, 3), AW, 114)
             ex.inputs = {"hid": hid, "x": x, "w2": w2}

@@ -91,19 +91,6 @@ def stream_ptr() -> int:
     return torch.cuda.current_stream().cuda_stream
 
 
-def op_conv(dtype, kind, in0, in1, w, alpha, out, B, H, W, cin, cout, Hout=0, Wout=0, silu=0):
-    wd = w.to("cuda", torch.float32).contiguous()
-    _ffi.check(
-        _ffi.lib().mz_op_conv(
-            _ffi.dtype_code(dtype), kind, ctypes.c_void_p(in0.data_ptr()),
-            ctypes.c_void_p(in1.data_ptr()) if in1 is not None else None, ctypes.c_void_p(wd.data_ptr()),
-            ctypes.c_float(alpha), ctypes.c_void_p(out.data_ptr()), B, H, W, cin, cout, Hout, Wout, silu,
-            ctypes.c_void_p(stream_ptr()),
-        )
-    )
-    torch.cuda.synchronize()
-
-
 def last_kernel() -> str:
     """Kernel family of the most recent convolution / mix launch of this thread (mz_debug_last_kernel)."""
     lib = _ffi.lib()

@@ -20,6 +20,7 @@ import torch.nn.functional as F
 
 from exact_util import AW, EXACT_SUM, F16_MAX_OUT, GATE_SCALE, INT_MAX, SAT_HI, SAT_LO, choice, conv_ax, gate_aw, ints, round_once
 from gpu_util import DTYPES, F32_OP_TOL, op_excess, pad16, planes_per, ulp_of
+from op_cases import ARGS
 from oracle import mewzoom_oracle as oracle
 
 LIMIT = 1 << 32
@@ -82,27 +83,11 @@ FINAL_R = 2
 FINAL_W_SCALE = 2.0 ** -10  # the head's weights: integers times 2^-10, so that the conv term does not bury the bicubic skip in [0, 1]
 
 
-def op_args(c: Case):
-    """The argument tuple of tests/test_poison_ops_gpu.Op.run (and of exact_util's rows)."""
-    if c.entry == "conv":
-        return (c.B, c.H, c.W, c.cin, c.cout, c.silu)
-    if c.entry == "d2s":
-        return (c.B, c.H, c.W, c.cin, c.cout, 2 * c.H, 2 * c.W)
-    if c.entry in ("conv_mix", "crush"):
-        return (c.B, c.H, c.W, c.cin, c.cout)
-    if c.entry == "final":
-        return (c.B, c.H, c.W, c.cin, FINAL_R)
-    return (c.B, c.H, c.W, c.cout)  # mix, stem
-
-
-def select_args(c):
-    """(op, cin, cout) of mz_debug_select for a Case or an LRow; None where the entry chooses no 3x3 / mix family."""
-    if c.entry == "conv":
-        return (0 if c.silu else 1, c.cin, c.cout)
-    if c.entry == "mix":
-        return (7, 2 * c.cout, c.cout)
-    op = {"d2s": 2, "conv_mix": 6, "final": 3}.get(c.entry)
-    return None if op is None else (op, c.cin, c.cout)
+def op_args(c, H=None):
+    """The argument tuple (op_cases.ARGS) of a Case, or of an LRow at height H."""
+    H = c.H if H is None else H
+    v = dict(B=c.B, H=H, W=c.W, cin=c.cin, cout=c.cout, C=c.cout, silu=c.silu, Hout=2 * H, Wout=2 * c.W, R=FINAL_R)
+    return tuple(v[n] for n in ARGS[c.entry] if n in v)
 
 
 # ---- offset spaces and blocks ---------------------------------------------------------------------------------------------------------

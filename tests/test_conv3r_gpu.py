@@ -8,23 +8,11 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from gpu_util import DTYPES, alloc_act, assert_op_close, from_act, last_kernel, op_conv, op_excess, op_excess_map, pad_part, q, to_act
+from gpu_util import DTYPES, alloc_act, assert_op_close, from_act, last_kernel, pad_part, q, to_act, ulp_of
+from op_util import op_conv, op_conv_mix, rnd, set_knobs, wrnd
 from oracle import mewzoom_oracle as oracle
-from ultrazoom_amd.synth import hash_uniform
 
 pytestmark = pytest.mark.gpu
-
-
-def rnd(shape, seed, scale=1.0):
-    n = 1
-    for s in shape:
-        n *= s
-    return torch.from_numpy(((2.0 * hash_uniform(n, seed) - 1.0) * scale).reshape(shape))
-
-
-def wrnd(shape, seed):
-    fan_in = shape[1] * shape[2] * shape[3]
-    return rnd(shape, seed, (3.0 / fan_in) ** 0.5 * 1.7)
 
 
 R_CASES = [
@@ -62,18 +50,6 @@ def expected_r_kernel(H, W):
     return ("conv3r_8x40" if geo1 else "conv3r") if (pad40 if geo1 else pad48) <= pads else "conv3s"
 
 
-def run(dtype, kind, x_act, w, out_shape, args, env, monkeypatch, wgs):
-    for k in ("MZ_NO_R", "MZ_PERSIST_WGS"):
-        monkeypatch.delenv(k, raising=False)
-    for k, v in env.items():
-        monkeypatch.setenv(k, v)
-    if wgs:
-        monkeypatch.setenv("MZ_PERSIST_WGS", str(wgs))
-    out = alloc_act(*out_shape, dtype)
-    op_conv(dtype, kind, x_act, None, w, 0.0, out, *args)
-    return out
-
-
 @pytest.mark.parametrize("dt", ["bf16", "f16"])
 @pytest.mark.parametrize("case", R_CASES)
 def test_conv3r_matches_oracle_and_conv3s(dt, case, monkeypatch):
@@ -85,12 +61,7 @@ def test_conv3r_matches_oracle_and_conv3s(dt, case, monkeypatch):
     outs = {}
     for name, env in {"r": {}, "s": {"MZ_NO_R": "1"}}.items():
         out = alloc_act(B, cout, H, W, dtype)
-        for k in ("MZ_NO_R", "MZ_PERSIST_WGS"):
-            monkeypatch.delenv(k, raising=False)
-        for k, v in env.items():
-            monkeypatch.setenv(k, v)
-        if wgs:
-            monkeypatch.setenv("MZ_PERSIST_WGS", str(wgs))
+        set_knobs(monkeypatch, env, wgs)
         op_conv(dtype, 0, xa, None, w, 0.0, out, B, H, W, cin, cout, silu=silu)
         outs[name] = out
         if name == "s":  # (Cin = 112 pads K by 14 %: the 32x32x16 kernel with exact 16-channel chunks takes it)
@@ -130,12 +101,7 @@ def test_conv3r_ragged_cin48(dt, case, monkeypatch):
     xa = to_act(x, dtype)
     outs = {}
     for name, env in {"r": {}, "s": {"MZ_NO_R2": "1", "MZ_KPAD_PCT": "34"}}.items():
-        for k in ("MZ_NO_R", "MZ_NO_R2", "MZ_KPAD_PCT", "MZ_PERSIST_WGS"):
-            monkeypatch.delenv(k, raising=False)
-        for k, v in env.items():
-            monkeypatch.setenv(k, v)
-        if wgs:
-            monkeypatch.setenv("MZ_PERSIST_WGS", str(wgs))
+        set_knobs(monkeypatch, env, wgs)
         out = alloc_act(B, cout, H, W, dtype)
         op_conv(dtype, 0, xa, None, w, 0.0, out, B, H, W, cin, cout, silu=1)
         outs[name] = out
@@ -145,7 +111,7 @@ def test_conv3r_ragged_cin48(dt, case, monkeypatch):
     assert torch.equal(outs["r"], outs["s"]), "conv3r (ragged Cin) and conv3s (K padded) must agree bit for bit"
     assert (pad_part(outs["r"], cout) == 0).all(), "pad channels must stay zero"
     # without the activation the host keeps the layer off the ragged variant (it exists for conv1 + SiLU)
-    monkeypatch.delenv("MZ_NO_R2", raising=False); monkeypatch.delenv("MZ_KPAD_PCT", raising=False)
+    set_knobs(monkeypatch, wgs=wgs)
     out = alloc_act(B, cout, H, W, dtype)
     op_conv(dtype, 0, xa, None, w, 0.0, out, B, H, W, cin, cout, silu=0)
     assert last_kernel() != "conv3r_ragged"
@@ -165,11 +131,7 @@ def test_conv3r_subpixel(dt, shape, monkeypatch):
     xa = to_act(x, dtype)
     outs = {}
     for name, env in {"r": {}, "s": {"MZ_NO_R": "1"}}.items():
-        for k in ("MZ_NO_R",):
-            monkeypatch.delenv(k, raising=False)
-        for k, v in env.items():
-            monkeypatch.setenv(k, v)
-        monkeypatch.setenv("MZ_PERSIST_WGS", "8")
+        set_knobs(monkeypatch, env, wgs=8)
         out = alloc_act(B, cq, Hout, Wout, dtype)
         op_conv(dtype, 1, xa, None, w, 0.0, out, B, H, W, cin, cout, Hout, Wout)
         outs[name] = out
@@ -180,19 +142,6 @@ def test_conv3r_subpixel(dt, shape, monkeypatch):
 
 # ---- fused conv2 + AdaptiveResidualMix (model.py:773-778, 826-839) on conv3r_kernel: one pixel fragment's gate GEMM + blend per chunk
 #      under the partner's K loop; identical bits to conv3s_kernel<.., FUSE> ----
-def op_conv_mix(dtype, hid, x, w2, wmix, alpha, out, B, H, W, cin, cout):
-    import ctypes
-    from ultrazoom_amd import _ffi
-    from gpu_util import stream_ptr
-    w2d = w2.to("cuda", torch.float32).contiguous()
-    wmd = wmix.to("cuda", torch.float32).contiguous()
-    _ffi.check(_ffi.lib().mz_op_conv_mix(
-        _ffi.dtype_code(dtype), ctypes.c_void_p(hid.data_ptr()), ctypes.c_void_p(x.data_ptr()), ctypes.c_void_p(w2d.data_ptr()),
-        ctypes.c_void_p(wmd.data_ptr()), ctypes.c_float(alpha), ctypes.c_void_p(out.data_ptr()), B, H, W, cin, cout,
-        ctypes.c_void_p(stream_ptr())))
-    torch.cuda.synchronize()
-
-
 FUSE_CASES = [
     # B, H, W, cin, cout, persistent workgroups
     (1, 8, 48, 192, 96, 0),      # one tile: the final epilogue without a partner
@@ -219,12 +168,7 @@ def test_conv3r_fused_mix(dt, case, monkeypatch):
     ha, xa = to_act(hid, dtype), to_act(x, dtype)
     outs = {}
     for name, env in {"r": {}, "s": {"MZ_NO_R": "1"}}.items():
-        for k in ("MZ_NO_R", "MZ_PERSIST_WGS"):
-            monkeypatch.delenv(k, raising=False)
-        for k, v in env.items():
-            monkeypatch.setenv(k, v)
-        if wgs:
-            monkeypatch.setenv("MZ_PERSIST_WGS", str(wgs))
+        set_knobs(monkeypatch, env, wgs)
         out = alloc_act(B, cout, H, W, dtype)
         op_conv_mix(dtype, ha, xa, w2, wmix, alpha, out, B, H, W, cin, cout)
         outs[name] = out
@@ -234,7 +178,6 @@ def test_conv3r_fused_mix(dt, case, monkeypatch):
     got = from_act(outs["r"], cout)
     # one rounding of the output, plus one rounding step of z where its fp32 sum sits on a rounding boundary (the blend passes
     # sigmoid(alpha) * beta <= 1 of it on): element-wise |got - want| <= ulp(want) + ulp(z) + 1e-5
-    from gpu_util import ulp_of
     tol = ulp_of(want, dt) + ulp_of(z, dt) + 1e-5
     ex = ((got - want).abs() / tol).max().item()
     assert ex <= 1.0, f"fused conv2 + mix {dt}: {ex:.2f} x (ulp(out) + ulp(z) + 1e-5)"
@@ -273,12 +216,7 @@ def test_conv3r_shape_sweep_equals_conv3s(case, monkeypatch):
     outs = {}
     for name, env in {"r": {}, "s": {"MZ_NO_R": "1"}}.items():
         out = alloc_act(B, cout, H, W, dtype)
-        for k in ("MZ_NO_R", "MZ_PERSIST_WGS"):
-            monkeypatch.delenv(k, raising=False)
-        for k, v in env.items():
-            monkeypatch.setenv(k, v)
-        if wgs:
-            monkeypatch.setenv("MZ_PERSIST_WGS", str(wgs))
+        set_knobs(monkeypatch, env, wgs)
         op_conv(dtype, 0, xa, None, w, 0.0, out, B, H, W, cin, cout, silu=silu)
         outs[name] = out
     assert torch.equal(outs["r"], outs["s"]), f"conv3r and conv3s differ on {case}"

@@ -6,39 +6,15 @@ Plain / SiLU: against the oracle (1 ulp of the storage type) and bit for bit aga
 accumulate in the same order (chunk, tap, one 32-channel MFMA).  Fused: against the oracle within ulp(out) + ulp(z), and against
 conv3s_kernel<.., FUSE>, whose gate sums its products in another order inside a K step (>= 98 % of the outputs bit-equal)."""
 
-import ctypes
-
 import pytest
 import torch
 import torch.nn.functional as F
 
-from gpu_util import DTYPES, alloc_act, assert_op_close, from_act, last_kernel, op_conv, pad_part, q, stream_ptr, to_act, ulp_of
+from gpu_util import DTYPES, alloc_act, assert_op_close, from_act, last_kernel, pad_part, q, to_act, ulp_of
+from op_util import op_conv, op_conv_mix, rnd, set_knobs, wrnd
 from oracle import mewzoom_oracle as oracle
-from ultrazoom_amd import _ffi
-from ultrazoom_amd.synth import hash_uniform
 
 pytestmark = pytest.mark.gpu
-
-
-def rnd(shape, seed, scale=1.0):
-    n = 1
-    for s in shape:
-        n *= s
-    return torch.from_numpy(((2.0 * hash_uniform(n, seed) - 1.0) * scale).reshape(shape))
-
-
-def wrnd(shape, seed):
-    fan_in = shape[1] * shape[2] * shape[3]
-    return rnd(shape, seed, (3.0 / fan_in) ** 0.5 * 1.7)
-
-
-def set_env(monkeypatch, env, wgs):
-    for k in ("MZ_NO_T", "MZ_PERSIST_WGS"):
-        monkeypatch.delenv(k, raising=False)
-    for k, v in env.items():
-        monkeypatch.setenv(k, v)
-    if wgs:
-        monkeypatch.setenv("MZ_PERSIST_WGS", str(wgs))
 
 
 T_CASES = [
@@ -68,7 +44,7 @@ def test_conv3t_matches_oracle_and_conv3s(dt, case, monkeypatch):
     xa = to_act(x, dtype)
     outs = {}
     for name, env in {"t": {}, "s": {"MZ_NO_T": "1"}}.items():
-        set_env(monkeypatch, env, wgs)
+        set_knobs(monkeypatch, env, wgs)
         out = alloc_act(B, cout, H, W, dtype)
         op_conv(dtype, 0, xa, None, w, 0.0, out, B, H, W, cin, cout, silu=silu)
         outs[name] = out
@@ -80,16 +56,6 @@ def test_conv3t_matches_oracle_and_conv3s(dt, case, monkeypatch):
     assert torch.equal(outs["t"], outs["s"]), "conv3t and conv3s must agree bit for bit"
     if cout < 48:
         assert (pad_part(outs["t"], cout) == 0).all(), "pad channels must be written as zeros"
-
-
-def op_conv_mix(dtype, hid, x, w2, wmix, alpha, out, B, H, W, cin, cout):
-    w2d = w2.to("cuda", torch.float32).contiguous()
-    wmd = wmix.to("cuda", torch.float32).contiguous()
-    _ffi.check(_ffi.lib().mz_op_conv_mix(
-        _ffi.dtype_code(dtype), ctypes.c_void_p(hid.data_ptr()), ctypes.c_void_p(x.data_ptr()), ctypes.c_void_p(w2d.data_ptr()),
-        ctypes.c_void_p(wmd.data_ptr()), ctypes.c_float(alpha), ctypes.c_void_p(out.data_ptr()), B, H, W, cin, cout,
-        ctypes.c_void_p(stream_ptr())))
-    torch.cuda.synchronize()
 
 
 FUSE_CASES = [
@@ -118,7 +84,7 @@ def test_conv3t_fused_mix(dt, case, monkeypatch):
     ha, xa = to_act(hid, dtype), to_act(x, dtype)
     outs = {}
     for name, env in {"t": {}, "s": {"MZ_NO_T": "1"}}.items():
-        set_env(monkeypatch, env, wgs)
+        set_knobs(monkeypatch, env, wgs)
         out = alloc_act(B, cout, H, W, dtype)
         op_conv_mix(dtype, ha, xa, w2, wmix, alpha, out, B, H, W, cin, cout)
         outs[name] = out
@@ -161,7 +127,7 @@ def test_conv3t_shape_sweep_equals_conv3s(case, monkeypatch):
     ha = to_act(hid, dtype)
     outs = {}
     for name, env in {"t": {}, "s": {"MZ_NO_T": "1"}}.items():
-        set_env(monkeypatch, env, wgs)
+        set_knobs(monkeypatch, env, wgs)
         out = alloc_act(B, cout, H, W, dtype)
         op_conv(dtype, 0, ha, None, w, 0.0, out, B, H, W, cin, cout, silu=silu)
         outs[name] = out
@@ -173,7 +139,7 @@ def test_conv3t_shape_sweep_equals_conv3s(case, monkeypatch):
     xa = to_act(x, dtype)
     fo = {}
     for name, env in {"t": {}, "s": {"MZ_NO_T": "1"}}.items():
-        set_env(monkeypatch, env, wgs)
+        set_knobs(monkeypatch, env, wgs)
         out = alloc_act(B, cout, H, W, dtype)
         op_conv_mix(dtype, ha, xa, w, wmix, -0.4, out, B, H, W, cin, cout)
         fo[name] = from_act(out, cout)

@@ -146,16 +146,14 @@ def test_the_jpeg_model_against_a_real_codec(codec):
 def test_the_gpu_tests_seeds_stay_under_their_caps():
     """What tests/test_degrade_gpu.py assumes of its inputs, checked with the checker alone: JPEG near-tie blocks under 1 % per case
     (expected: about 1e-4), and for uint8 noise fewer than 0.1 % of the elements within 1e-6 of a rounding tie."""
-    import test_degrade_gpu as G
-
-    for shape in G.SHAPES:
-        for q in G.QUALITIES:
+    for shape in R.SHAPES:
+        for q in R.QUALITIES:
             for dt in ("u8", "f32"):
-                _, _, share = R.jpeg_ref(G.image(G.BATCH, *shape, dt), q)
+                _, _, share = R.jpeg_ref(R.image(R.BATCH, *shape, dt), q)
                 assert share < 0.01, (shape, q, dt, share)
-    for shape in G.SHAPES:
-        for sigma in G.NOISE_SIGMAS:
-            scaled = R.noise_ref(G.image(G.BATCH, *shape, "u8"), sigma, G.SEED, G.OFFSET) * 255
+    for shape in R.SHAPES:
+        for sigma in R.NOISE_SIGMAS:
+            scaled = R.noise_ref(R.image(R.BATCH, *shape, "u8"), sigma, R.SEED, R.OFFSET) * 255
             near = ((scaled - torch.floor(scaled)) - 0.5).abs() <= 1e-6
             assert float(near.double().mean()) < 1e-3, (shape, sigma)
 

@@ -22,36 +22,14 @@ import pytest
 import torch
 
 import degrade_ref as R
+from degrade_ref import BATCH, BLUR_SIGMAS, DTYPES, ELEM, NOISE_SIGMAS, OFFSET, QUALITIES, SEED, SHAPES, hip, image, shape_id
 from gpu_util import ulp_of
+from resize_util import assert_within_gate, model_and_input
 from ultrazoom_amd import _ffi
 
 pytestmark = pytest.mark.gpu
 
-SHAPES = [(16, 16), (17, 33), (31, 15), (37, 45), (64, 80)]
-DTYPES = {"f32": torch.float32, "bf16": torch.bfloat16, "f16": torch.float16, "u8": torch.uint8}
-ELEM = {"f32": 0, "bf16": 1, "f16": 2, "u8": 3}
-BLUR_SIGMAS = (0.2, 0.34, 1.0, 2.5)
-NOISE_SIGMAS = (0.05, 0.3)
-QUALITIES = (20, 50, 90, 100)
-BATCH, SEED, OFFSET = 3, 1234, 5
 GOLDEN = Path(__file__).resolve().parent / "golden"
-
-
-def shape_id(s):
-    return f"{s[0]}x{s[1]}"
-
-
-@lru_cache(maxsize=None)
-def image(B: int, H: int, W: int, dt: str, seed: int = 21) -> torch.Tensor:
-    """uniform noise in [0, 1], rounded to the element type, on the CPU"""
-    x = torch.rand((B, 3, H, W), generator=torch.Generator().manual_seed(seed + 1000 * B + H * W), dtype=torch.float32)
-    return (x * 255.0).round().to(torch.uint8) if dt == "u8" else x.to(DTYPES[dt])
-
-
-def hip():
-    from ultrazoom_amd import degrade
-
-    return degrade
 
 
 def stream():
@@ -67,8 +45,6 @@ def blur_checker(B, shape, dt, sigma):
 @pytest.mark.parametrize("dt", sorted(DTYPES))
 @pytest.mark.parametrize("shape", SHAPES, ids=shape_id)
 def test_blur_against_the_float64_checker(shape, dt):
-    from test_resize_gpu import assert_within_gate
-
     x = image(BATCH, *shape, dt)
     xg = x.cuda()
     for sigma in BLUR_SIGMAS:
@@ -132,8 +108,6 @@ def test_a_blur_wider_than_the_image_is_refused():
         raw_blur(small.data_ptr(), small.stride(), torch.empty_like(small), 0, 1, 5, 5, 1.7)
     with pytest.raises(_ffi.MewZoomHipError, match="overlap"):
         raw_blur(x.data_ptr(), x.stride(), x, 0, 1, 37, 45, 1.0)
-    from test_resize_gpu import assert_within_gate
-
     assert_within_gate(hip().gaussian_blur(small, 1.6), R.blur_ref(small, 1.6), "f32", "5x5 sigma 1.6 (half 4), after the refusals")
 
 
@@ -290,7 +264,6 @@ def test_degradation_apply():
 
 
 def test_evaluate_hr_with_a_degradation():
-    from test_resize_gpu import model_and_input
     from ultrazoom_amd import Degradation
     from ultrazoom_amd.evaluate import evaluate, evaluate_hr, lr_from_hr
     from ultrazoom_amd.synth import synth_image
@@ -357,8 +330,6 @@ def test_jpeg_at_the_smallest_images_is_the_checker_bit_for_bit(shape, dt):
 def test_blur_at_the_smallest_images(shape, dt):
     """Every sigma whose reflection fits (int(3 sigma) < min(H, W)) against the checker; every other one is refused with its message, by
     the Python layer and by the C entry, and the call after a refusal is unaffected."""
-    from test_resize_gpu import assert_within_gate
-
     x = image(BATCH, *shape, dt)
     xg = x.cuda()
     refused = 0

@@ -10,7 +10,7 @@ from pathlib import Path
 
 import pytest
 
-from test_kernel_resources import HIPCC, LISTINGS, TOOLS, resource_usage
+from listing_util import HIPCC, LISTINGS, TOOLS, resource_usage
 
 FAMILIES = ("blur_kernelILi", "noise_kernelILi", "jpeg_code_kernelILi", "jpeg_image_kernelILi")
 

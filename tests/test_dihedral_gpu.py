@@ -8,48 +8,17 @@ one.  Layouts at both ends: dense (the 16-byte path where the width allows it), 
 padded to an aligned pitch (flipped tiles start misaligned: both paths inside one launch), a transposed view (unit ROW stride), and --
 through _ffi -- a negative channel stride."""
 
-import functools
-
 import pytest
 import torch
 
 import ensemble_ref as ref
+from ensemble_ref import DTYPES, INT_OF, pass_results, random_bits, shape_id, stream
 from ultrazoom_amd import _ffi, dihedral
 
 pytestmark = pytest.mark.gpu
 
-DTYPES = {"f32": torch.float32, "bf16": torch.bfloat16, "f16": torch.float16, "u8": torch.uint8}
-INT_OF = {4: torch.int32, 2: torch.int16, 1: torch.uint8}
 SHAPES = [(1, 1, 1), (2, 1, 7), (2, 7, 1), (3, 31, 33), (1, 64, 64), (2, 65, 127), (1, 8, 200)]
 SENTINEL = 0x5A
-
-
-def shape_id(s):
-    return "x".join(str(v) for v in s)
-
-
-def stream():
-    return torch.cuda.current_stream().cuda_stream
-
-
-@functools.lru_cache(maxsize=None)
-def random_bits(dt: str, B: int, H: int, W: int, seed: int = 0) -> torch.Tensor:
-    """[B, 3, H, W] of DTYPES[dt] holding random bit patterns; the first elements are NaN, a NaN with a payload, -0, +inf, -inf.
-    Shared between the tests and never written to."""
-    dtype = DTYPES[dt]
-    size = torch.empty((), dtype=dtype).element_size()
-    g = torch.Generator(device="cuda").manual_seed(1000 * seed + 31 * H + W)
-    raw = torch.randint(0, 256, (B * 3 * H * W * size,), dtype=torch.uint8, device="cuda", generator=g)
-    x = raw.view(dtype).view(B, 3, H, W)
-    if dt != "u8":
-        special = torch.tensor([float("nan"), float("nan"), -0.0, float("inf"), float("-inf")], dtype=dtype, device="cuda")
-        n = min(5, W)
-        x[0, 0, 0, :n] = special[:n]
-        if W > 1:
-            x.view(INT_OF[size])[0, 0, 0, 1] |= 0x15  # a payload in the second NaN
-    else:
-        x.view(-1)[: min(2, x.numel())] = torch.tensor([0, 255], dtype=torch.uint8, device="cuda")[: min(2, x.numel())]
-    return x
 
 
 def assert_same_bits(got: torch.Tensor, want: torch.Tensor, what):
@@ -150,23 +119,6 @@ def test_dihedral_round_trip_and_the_python_refusals():
 
 
 # ---- the accumulator ---------------------------------------------------------------------------------------------------------------
-@functools.lru_cache(maxsize=None)
-def pass_results(dt: str, B: int, H: int, W: int):
-    """Eight pass results of a [B, 3, H, W] ensemble, result k in orientation k's shape.  Float data: normal(0.5, 1), so a good part lies
-    outside [0, 1]; uint8: every sample value, 0 and 255 planted."""
-    g = torch.Generator(device="cuda").manual_seed(7 * H + W)
-    out = []
-    for k in range(8):
-        h, w = (W, H) if k & 4 else (H, W)
-        if dt == "u8":
-            y = torch.randint(0, 256, (B, 3, h, w), dtype=torch.uint8, device="cuda", generator=g)
-            y.view(-1)[0] = 255 if k & 1 else 0
-        else:
-            y = (torch.randn((B, 3, h, w), device="cuda", generator=g) + 0.5).to(DTYPES[dt])
-        out.append(y)
-    return out
-
-
 ORDERS = {1: [5], 2: [6, 0], 4: [3, 7, 4, 1], 8: [2, 5, 0, 7, 1, 6, 3, 4]}  # call orders: every k, as first and as a later add
 
 

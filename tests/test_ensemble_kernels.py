@@ -9,7 +9,7 @@ from pathlib import Path
 
 import pytest
 
-from test_kernel_resources import HIPCC, LISTINGS, TOOLS, resource_usage
+from listing_util import HIPCC, LISTINGS, TOOLS, resource_usage
 
 
 @pytest.mark.skipif(not Path(HIPCC).exists(), reason="hipcc not installed")

@@ -8,7 +8,8 @@ import torch
 import torch.nn.functional as F
 
 from golden_util import GoldenCase
-from gpu_util import DTYPES, assert_op_close, alloc_act, from_act, op_conv, q, to_act
+from gpu_util import DTYPES, assert_op_close, alloc_act, from_act, q, to_act
+from op_util import op_conv
 from ultrazoom_amd import MewZoom, _ffi
 from ultrazoom_amd.synth import hash_uniform, synth_image
 

@@ -1,18 +1,14 @@
 """The exact-arithmetic table (tests/exact_util.py) held to the conditions that keep tests/test_exact_gpu.py from being vacuous, with
 the float64 reference alone: no GPU.  These are conditions on the test data, not measurements of a kernel."""
 
-import ctypes
-import re
-from pathlib import Path
-
 import pytest
 import torch
 
 from exact_util import (CENSUS_MIN, CENSUS_MIN_SHARE, EXACT_SUM, F16_MAX_OUT, MAX_EXCLUDED, MIN_BRANCH, PERSISTENT, ROWS, WALK_WGS, WALKS, bits_of, census, exact, lower_edge, round_once, row_id,
                         walk_id)
 from gpu_util import DTYPES
-from test_poison_ops_gpu import FAMILY_OF_UNREPORTED, KNOBS, SELECT_OP
-from ultrazoom_amd import _ffi
+from op_cases import FAMILY_OF_UNREPORTED, select_args
+from op_util import kernel_names, selected, set_knobs
 
 
 def as_torch(y64, dt):
@@ -111,11 +107,7 @@ def test_the_row_s_conditions(row):
 
 def test_the_table_names_every_kernel_family():
     """Every literal kernel_name() (mz_select.h) can return is the pinned family of some row."""
-    src = (Path(__file__).resolve().parent.parent / "ultrazoom_amd" / "csrc" / "mz_select.h").read_text()
-    body = re.search(r"inline const char\* kernel_name\(const KernelChoice& ch\) \{(.*?)\n\}\n", src, re.S).group(1)
-    body = re.sub(r"//[^\n]*", "", body)
-    names = set(re.findall(r'"([a-z0-9_]+)"', body))
-    assert len(names) >= 15 and {"conv3r", "conv3t_fused", "mix16b", "conv_kernel_mix"} <= names, names
+    names = kernel_names()
     covered = {r.kernel for r in ROWS if r.kernel} | {FAMILY_OF_UNREPORTED[r.entry] for r in ROWS if r.entry in FAMILY_OF_UNREPORTED}
     assert names <= covered, f"no row runs {sorted(names - covered)}"
     assert PERSISTENT <= names
@@ -125,37 +117,21 @@ def test_the_table_names_every_kernel_family():
     assert gated <= {r.kernel for r in ROWS if r.entry in ("mix", "conv_mix")}
 
 
-def selected(row, monkeypatch, wgs=None):
-    for k in KNOBS:
-        monkeypatch.delenv(k, raising=False)
-    for k, v in row.env.items():
-        monkeypatch.setenv(k, v)
-    if wgs is not None:
-        monkeypatch.setenv("MZ_PERSIST_WGS", str(wgs))
-    lib = _ffi.lib()
-    lib.mz_debug_select.restype = ctypes.c_char_p
-    B, H, W = row.args[:3]
-    if row.entry == "mix":
-        op, cin, cout = 7, 2 * row.args[3], row.args[3]
-    elif row.entry == "final":
-        op, cin, cout = 3, row.args[3], 12
-    else:
-        cin, cout = row.args[3:5]
-        op = SELECT_OP[row.entry] if row.entry != "conv" else (0 if row.silu else 1)
-    got = lib.mz_debug_select(_ffi.dtype_code(DTYPES[row.dt]), op, cin, cout, B, H, W, 256)
-    return got.decode() if got is not None else None
+def choice_of(row, monkeypatch, wgs=None):
+    set_knobs(monkeypatch, row.env, wgs)
+    return selected(row.entry, row.args, row.dt, row.silu)
 
 
-@pytest.mark.parametrize("row", [r for r in ROWS if r.entry in SELECT_OP], ids=row_id)
+@pytest.mark.parametrize("row", [r for r in ROWS if select_args(r.entry, r.args) is not None], ids=row_id)
 def test_the_pinned_families_are_the_host_s_choice(row, monkeypatch):
     """With SiLU off, and for this table's own shapes: the name of every row is what the host chooses on an MI355X (256 CUs)."""
-    assert selected(row, monkeypatch) == row.kernel
+    assert choice_of(row, monkeypatch) == row.kernel
 
 
 @pytest.mark.parametrize("walk", WALKS, ids=walk_id)
 def test_the_walks_keep_their_row_s_family(walk, monkeypatch):
     row, wgs = walk
-    assert selected(row, monkeypatch, wgs) == row.kernel
+    assert choice_of(row, monkeypatch, wgs) == row.kernel
 
 
 def test_every_persistent_family_is_walked_both_ways():

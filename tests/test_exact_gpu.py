@@ -9,7 +9,7 @@ import torch
 
 from exact_util import MAX_EXCLUDED, ROWS, WALKS, bits_of, exact, row_id, walk_id
 from gpu_util import DTYPES, alloc_act, assert_op_close, last_kernel, pad_part, to_act
-from test_poison_ops_gpu import KNOBS, Op
+from op_util import run_entry, set_knobs
 
 pytestmark = pytest.mark.gpu
 
@@ -19,7 +19,6 @@ ACTIVATIONS = {"in0", "in1", "hid", "x", "feat"}  # plane-major activation tenso
 def launch(row, ex):
     """The row's operator on the row's data: (output on the GPU, its real channels [B, C, H, W] on the CPU, storage type)."""
     dtype = DTYPES[row.dt]
-    op = Op.call_only(row.entry, row.args, row.dt, ex.alpha)  # the call of each entry as tests/test_poison_ops_gpu.py states it, on this table's tensors
     t = {}
     for name, v in ex.inputs.items():
         if name in ACTIVATIONS and not (row.entry == "stem" and name == "x"):
@@ -33,7 +32,7 @@ def launch(row, ex):
         out = torch.full(tuple(ex.want.shape), 7.0, dtype=dtype, device="cuda")
     else:
         out = alloc_act(B, ex.C, ex.want.shape[2], ex.want.shape[3], dtype)
-    op.run(t, out)
+    run_entry(row.entry, row.args, row.dt, t, out, ex.alpha)
     if ex.C is None:
         return out, out.cpu()
     Bo, P, H, W, ppu = out.shape
@@ -64,13 +63,6 @@ def check(row, ex, out, got):
         assert bool((pad_part(out, ex.C) == 0).all()), "pad channels must be written as zeros"
 
 
-def set_knobs(monkeypatch, env):
-    for k in KNOBS:
-        monkeypatch.delenv(k, raising=False)
-    for k, v in env.items():
-        monkeypatch.setenv(k, v)
-
-
 @pytest.mark.parametrize("row", ROWS, ids=row_id)
 def test_bit_for_bit(row, monkeypatch):
     set_knobs(monkeypatch, row.env)
@@ -83,7 +75,7 @@ def test_bit_for_bit(row, monkeypatch):
 def test_bit_for_bit_persistent_walks(walk, monkeypatch):
     """The same row with 8 and with 16 persistent workgroups: each run equals the expectation, not merely the other run."""
     row, wgs = walk
-    set_knobs(monkeypatch, dict(row.env, MZ_PERSIST_WGS=str(wgs)))
+    set_knobs(monkeypatch, row.env, wgs)
     ex = exact(row)
     out, got = launch(row, ex)
     check(row, ex, out, got)

@@ -1,35 +1,21 @@
 """a17: the optional per-channel affine ("FiLM") epilogue of the 3x3 kernel.  NO REFERENCE: the snapshot has
 no ControlModule, so this is checked against the build's own CPU statement of the operator (oracle.film_conv) -- parity unpinned."""
 
-import ctypes
-
 import pytest
 import torch
 
-from gpu_util import DTYPES, alloc_act, assert_op_close, from_act, pad16, pad_part, q, stream_ptr, to_act
+from gpu_util import DTYPES, alloc_act, assert_op_close, from_act, pad16, pad_part, q, to_act
+from op_util import dev_w, rnd, run_entry
 from oracle import mewzoom_oracle as oracle
 from ultrazoom_amd import _ffi
-from ultrazoom_amd.synth import hash_uniform
 
 pytestmark = pytest.mark.gpu
 
 
-def rnd(shape, seed, scale=1.0):
-    n = 1
-    for s in shape:
-        n *= s
-    return torch.from_numpy(((2.0 * hash_uniform(n, seed) - 1.0) * scale).reshape(shape))
-
-
 def film(dtype, x, w, gamma, beta, B, H, W, cin, cout, silu):
     out = alloc_act(B, cout, H, W, dtype)
-    xd = to_act(x, dtype)
-    wd, gd, bd = w.cuda().float().contiguous(), gamma.cuda().float().contiguous(), beta.cuda().float().contiguous()
-    rc = _ffi.lib().mz_op_conv_film(
-        _ffi.dtype_code(dtype), ctypes.c_void_p(xd.data_ptr()), ctypes.c_void_p(wd.data_ptr()), ctypes.c_void_p(gd.data_ptr()),
-        ctypes.c_void_p(bd.data_ptr()), ctypes.c_void_p(out.data_ptr()), B, H, W, cin, cout, silu, ctypes.c_void_p(stream_ptr()))
-    torch.cuda.synchronize()
-    return rc, out
+    t = {"in0": to_act(x, dtype), "w": dev_w(w), "gamma": dev_w(gamma), "beta": dev_w(beta)}
+    return run_entry("film", (B, H, W, cin, cout, silu), dtype, t, out, check=False), out
 
 
 @pytest.mark.parametrize("dt", ["bf16", "f16"])

@@ -5,20 +5,13 @@ cap; nothing failed when that happened.  This test compi
 (device code only, no GPU needed) with -Rpass-analysis=kernel-resource-usage and fails if a persistent 3x3 kernel, the mix
 kernel or the image head reports ScratchSize != 0 or VGPR spills."""
 
-import os
 import re
-import shutil
-import subprocess
 import sys
-import tempfile
 from pathlib import Path
 
 import pytest
 
-CSRC = Path(__file__).resolve().parent.parent / "ultrazoom_amd" / "csrc"
-TOOLS = Path(__file__).resolve().parent.parent / "tools"
-LISTINGS = {}
-HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+from listing_util import HIPCC, LISTINGS, TOOLS, resource_usage
 
 # kernels the execution plans of the 16-bit modes use (name prefix of the demangled-ish symbol)
 HOT = ("conv3r_kernel", "conv3t_kernel", "conv3s_kernel", "mix16_kernel", "mix16b_kernel", "conv3w_kernel")
@@ -27,27 +20,6 @@ HOT = ("conv3r_kernel", "conv3t_kernel", "conv3s_kernel", "mix16_kernel", "mix16
 #                                      or more chunks (hidden_ratio >= 2), so this one only runs for hidden_ratio 1 or MZ_NO_R=1
 #   conv3w_kernel<T16, NT = 3, ..>:    per-tile wide kernels of the 16-bit types, reachable with MZ_NO_PERSIST=1 / MZ_NO_FUSE16=1 only
 EXEMPT = (re.compile(r"conv3s_kernelINS_\w+ELi3ELi\dELb1E"), re.compile(r"conv3w_kernelINS_\w+ELi3ELi\dELb[01]E"))
-
-
-def resource_usage(src: str):
-    """One device-only compile per translation unit: the resource remarks on stderr, the assembly listing kept for the hazard scan."""
-    asm = Path(tempfile.gettempdir()) / f"mz_guard_{os.getpid()}_{src}.s"
-    p = subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "--cuda-device-only", "-S", "-Rpass-analysis=kernel-resource-usage",
-                        str(CSRC / src), "-o", str(asm)], capture_output=True, text=True, timeout=1500)
-    assert p.returncode == 0, p.stderr[-2000:]
-    LISTINGS[src] = asm
-    out = {}
-    name = None
-    for line in p.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-            out[name] = {}
-            continue
-        m = re.search(r"remark:\s+([A-Za-z ]+?)(?: \[bytes/lane\])?: (\d+)", line)
-        if m and name:
-            out[name][m.group(1).strip()] = int(m.group(2))
-    return out
 
 
 @pytest.mark.skipif(not Path(HIPCC).exists(), reason="hipcc not installed")

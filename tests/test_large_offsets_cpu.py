@@ -3,33 +3,25 @@ guard, the block picker against brute force, the data's worst-case bounds, and t
 shapes -- against exact_util's float64 expectation, bit for bit.  tests/test_large_offsets_gpu.py lets these helpers judge kernels; here
 they are shown to agree with an independent computation and to report a wrong or an unwritten element."""
 
-import ctypes
-
 import pytest
 import torch
 
 import large_util as lu
 from exact_util import AW, EXACT_SUM, F16_MAX_OUT, INT_MAX, MAX_EXCLUDED, Row, bits_of, exact
 from gpu_util import DTYPES
+from op_util import selected, set_knobs
 from oracle import mewzoom_oracle as oracle
-from test_poison_ops_gpu import KNOBS
-from ultrazoom_amd import _ffi
 
 LIMIT = 1 << 32
 
 
-def chosen(dt, c, B, H, W):
-    lib = _ffi.lib()
-    lib.mz_debug_select.restype = ctypes.c_char_p
-    op, cin, cout = lu.select_args(c)
-    got = lib.mz_debug_select(_ffi.dtype_code(DTYPES[dt]), op, cin, cout, B, H, W, 256)
-    return None if got is None else got.decode()
+def chosen(dt, c, H):
+    return selected(c.entry, lu.op_args(c, H), dt)
 
 
 @pytest.fixture
 def no_knobs(monkeypatch):
-    for k in KNOBS:
-        monkeypatch.delenv(k, raising=False)
+    set_knobs(monkeypatch)
 
 
 @pytest.mark.parametrize("row", lu.TABLE, ids=lambda r: f"row{r.n}")
@@ -40,10 +32,10 @@ def test_the_table_sits_on_the_host_s_guards(row, no_knobs):
     H = lu.h_fit(row)
     assert row.planes * pixels(H) * 16 < LIMIT <= row.planes * pixels(H + 1) * 16
     assert H > 16 and pixels(H) * 16 > (1 << 31) // row.planes  # offsets between 2^31 and 2^32 exist
-    assert chosen(row.dt, row, row.B, H, row.W) == row.edge
-    assert chosen(row.dt, row, row.B, H + 1, row.W) == row.past
+    assert chosen(row.dt, row, H) == row.edge
+    assert chosen(row.dt, row, H + 1) == row.past
     if row.n in lu.F16_TOO:
-        assert chosen("f16", row, row.B, H, row.W) == row.edge
+        assert chosen("f16", row, H) == row.edge
     # the plane count is the tensor's own where the guard is about stores (and about x, z for the mix)
     u = torch.empty((), dtype=DTYPES[row.dt]).element_size()
     if row.planes not in (2, 4):  # 4: conv3s's halo planes; 2: a stage of conv3p
@@ -85,7 +77,7 @@ def meta_tensors(c):
 
 def test_the_head_s_case_runs_the_256_pixel_kernel(no_knobs):
     c = next(c for c in lu.CASES if c.entry == "final")
-    assert chosen(c.dt, c, c.B, c.H, c.W) == c.kernel
+    assert chosen(c.dt, c, c.H) == c.kernel
 
 
 @pytest.mark.parametrize("space", [(1, 3, 5, 16), (4, 7, 9, 16), (3, 6, 4, 2), (5, 1, 11, 16), (2, 9, 1, 4)])

@@ -17,7 +17,7 @@ import torch
 import large_util as lu
 from exact_util import MAX_EXCLUDED
 from gpu_util import DTYPES, alloc_act, last_kernel
-from test_poison_ops_gpu import KNOBS, Op
+from op_util import run_entry, set_knobs
 
 pytestmark = pytest.mark.gpu
 
@@ -35,8 +35,7 @@ def release_device_memory():
 
 @pytest.mark.parametrize("case", lu.CASES, ids=lambda c: c.name)
 def test_large_offsets(case, monkeypatch):
-    for k in KNOBS:
-        monkeypatch.delenv(k, raising=False)
+    set_knobs(monkeypatch)
     torch.cuda.empty_cache()
     torch.cuda.reset_peak_memory_stats()
     started = time.perf_counter()
@@ -46,7 +45,7 @@ def test_large_offsets(case, monkeypatch):
     out = torch.full(shape, float("nan"), dtype=dtype, device="cuda")
     sums = {k: lu.checksum(v) for k, v in t.items()}
 
-    Op.call_only(case.entry, lu.op_args(case), case.dt, 0.0).run(t, out)  # the call of each entry as tests/test_poison_ops_gpu.py states it
+    run_entry(case.entry, lu.op_args(case), case.dt, t, out)
     if case.kernel is not None:
         assert last_kernel() == case.kernel, (last_kernel(), case.kernel)
     for k, v in t.items():

@@ -30,3 +30,20 @@ def test_gpu_side_files_do_not_read_the_reference():
         if p.name == "test_layout.py":
             continue
         assert "/root/reference" not in p.read_text(), p
+
+
+def test_no_file_under_tests_imports_a_test_module():
+    """What test modules share lives in a *_util.py / *_ref.py / op_cases.py: a CPU test never stands on a GPU test file, and a kernel
+    family is registered in a table, not in a test (conftest is no test module)."""
+    for p in sorted((REPO / "tests").rglob("*.py")):
+        found = re.findall(r"^\s*(?:from|import)\s+test_\w+.*", p.read_text(), re.M)
+        assert not found, f"{p} imports from a test module: {found}"
+
+
+def test_the_knob_list_is_what_read_knobs_reads():
+    """op_util.set_knobs clears op_cases.KNOBS: a knob read_knobs() (mz_plan.h) reads and the list does not name would leak from the
+    environment into every test that pins a kernel."""
+    from op_cases import KNOBS
+    from op_util import knob_names
+
+    assert len(KNOBS) == len(set(KNOBS)) and set(KNOBS) == knob_names(), (sorted(KNOBS), sorted(knob_names()))

@@ -8,7 +8,7 @@ from pathlib import Path
 
 import pytest
 
-from test_kernel_resources import HIPCC, LISTINGS, TOOLS, resource_usage
+from listing_util import HIPCC, LISTINGS, TOOLS, resource_usage
 
 LDS_PER_CU = 160 * 1024
 

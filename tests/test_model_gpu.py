@@ -21,8 +21,9 @@ import torch
 
 from conftest import host_cores
 from golden_util import MODEL_CASES, GoldenCase, psnr
+from model_util import FUZZ_CONFIGS, LOWER_B, LOWER_MODELS, build, lower_built, lower_image, lower_model
+from op_util import set_knobs
 from oracle import mewzoom_oracle as oracle
-from ultrazoom_amd import MewZoom
 from ultrazoom_amd.synth import synth_image, synth_state_dict
 
 pytestmark = pytest.mark.gpu
@@ -55,13 +56,6 @@ def psnr_of(mse: float) -> float:
     import math
 
     return float("inf") if mse <= 0 else 10.0 * math.log10(1.0 / mse)
-
-
-def build(case_or_cfg, weights, dtype):
-    cfg = case_or_cfg.config if isinstance(case_or_cfg, GoldenCase) else case_or_cfg
-    m = MewZoom(**cfg)
-    m.load_state_dict(weights)
-    return m.to("cuda", dtype).eval()
 
 
 @pytest.mark.parametrize("name", MODEL_CASES)
@@ -282,20 +276,6 @@ def test_uint8_io_matches_float_path_with_save_image_rounding(dtype):
         assert torch.equal(got.cpu(), (y * 255 + 0.5).clamp(0, 255).to(torch.uint8).cpu())
 
 
-# Channel counts chosen to reach every kernel variant: (primary channels, hidden ratio) -> fused mix on the 16x16x32 kernel
-# with NT = 1, 2, 3 (C = 32, 64, 96), K that pads to 32-channel chunks with a half-zero last chunk (C = 80 -> conv2 K = 160),
-# K that does not fit the 16x16x32 kernel (C = 24, 48 with hidden ratio 1 -> 32x32x16 kernels), two N tiles (hidden 4 x 48).
-FUZZ_CONFIGS = [
-    # ratio, channels (4 levels), layers, hidden ratio, (B, H, W)
-    (2, (32, 64, 96, 128), (2, 2, 2, 2), 2, (2, 40, 72)),
-    (2, (96, 96, 96, 96), (2, 2, 2, 2), 2, (1, 33, 47)),
-    (2, (80, 48, 24, 16), (2, 2, 2, 2), 2, (1, 48, 64)),
-    (4, (48, 24, 32, 64), (2, 2, 2, 2), 4, (1, 24, 40)),
-    (2, (48, 96, 16, 32), (2, 3, 2, 2), 1, (3, 17, 29)),
-    (2, (32, 64, 192, 192), (2, 2, 2, 2), 2, (2, 64, 104)),  # C = 192 levels: conv3r_kernel (96-channel N tiles)
-]
-
-
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16, torch.float16])
 @pytest.mark.parametrize("spec", FUZZ_CONFIGS)
 def test_mixed_channel_configs_against_oracle(spec, dtype):
@@ -337,10 +317,7 @@ def test_kernel_variants_agree(dtype, monkeypatch):
     outs = {}
     for name, env in {"default": {}, "no_fuse16": {"MZ_NO_FUSE16": "1"}, "no_fuse": {"MZ_NO_FUSE": "1"}, "no_r": {"MZ_NO_R": "1"},
                       "no_s16": {"MZ_NO_S16": "1"}, "no_persist": {"MZ_NO_PERSIST": "1"}, "no_wide": {"MZ_NO_WIDE": "1"}}.items():
-        for k in ("MZ_NO_FUSE16", "MZ_NO_FUSE", "MZ_NO_S16", "MZ_NO_PERSIST", "MZ_NO_WIDE", "MZ_NO_R"):
-            monkeypatch.delenv(k, raising=False)
-        for k, v in env.items():
-            monkeypatch.setenv(k, v)
+        set_knobs(monkeypatch, env)
         m.refresh_weights()  # the knobs are read when the library handle is created
         outs[name] = m.upscale(xg).float().cpu()
     with torch.inference_mode():
@@ -370,10 +347,7 @@ def test_conv3r_and_tile_walk_knobs_leave_the_bits_unchanged(dtype, monkeypatch)
     outs = {}
     for name, env in {"default": {}, "no_r": {"MZ_NO_R": "1"}, "no_blk4": {"MZ_NO_BLK4": "1"},
                       "few_wgs": {"MZ_PERSIST_WGS": "8"}, "few_wgs_no_r": {"MZ_PERSIST_WGS": "8", "MZ_NO_R": "1"}}.items():
-        for k in ("MZ_NO_R", "MZ_NO_BLK4", "MZ_PERSIST_WGS"):
-            monkeypatch.delenv(k, raising=False)
-        for k, v in env.items():
-            monkeypatch.setenv(k, v)
+        set_knobs(monkeypatch, env)
         m.refresh_weights()
         outs[name] = m.upscale(x)
     for name, y in outs.items():
@@ -389,47 +363,6 @@ def test_conv3r_and_tile_walk_knobs_leave_the_bits_unchanged(dtype, monkeypatch)
 # hold a handful of real pixels, one at level 4.  8 x 9 / 9 x 8 / 11 x 13 / 15 x 15 add floors and zero borders (15 -> 7 -> 3 -> 1: the
 # up-conv's 3 x 3 target is mostly border), 8 x 40 / 40 x 8 a 1 x 5 row and a 5 x 1 column at level 4.
 LOWER_SIZES = [(8, 8), (8, 9), (9, 8), (11, 13), (15, 15), (8, 40), (40, 8)]
-LOWER_B = 24  # different images: the three statistics of lowp_gate_vs_matched need samples (2X, 8 x 8: 18 432 output elements)
-
-
-def _config(r, ch, layers, hr):
-    cfg = {"upscale_ratio": r, "hidden_ratio": hr, "num_deg_features": 3}
-    for n, c, l in zip(("primary", "secondary", "tertiary", "quaternary"), ch, layers):
-        cfg[f"{n}_channels"] = c
-        cfg[f"{n}_layers"] = l
-    return cfg
-
-
-# a thin, wide 2X model (76 M parameters): conv3r, mix16b (C = 192) and mix16 (C = 384, 768) on the 4 x 4, 2 x 2 and 1 x 1 levels
-WIDE_CONFIG = _config(2, (96, 192, 384, 768), (2, 2, 2, 2), 2)
-LOWER_MODELS = {
-    "g1": "g1_2x_c16", "g3": "g3_4x_c16", "g4": "g4_8x_c16", "g8": "g8_c24_f5",  # 2X, 4X, 8X; pad channels
-    "g7": "g7_cfg1_2x_c48",                                                       # 48 channels: conv3t, conv3r_ragged
-    "c96": next(_config(r, ch, l, hr) for r, ch, l, hr, _ in FUZZ_CONFIGS if ch == (96, 96, 96, 96)),
-    "wide": WIDE_CONFIG,
-}
-
-
-@functools.lru_cache(maxsize=None)
-def lower_model(name):
-    """(config, state dict) of a model of LOWER_MODELS: a fixture's own weights, or hash-initialised ones."""
-    spec = LOWER_MODELS[name]
-    if isinstance(spec, str):
-        case = GoldenCase(spec)
-        return case.config, case.weights()
-    return spec, synth_state_dict(oracle.parameter_shapes(spec), seed=sum(ord(c) for c in name))
-
-
-@functools.lru_cache(maxsize=None)
-def lower_built(name, dtype):
-    cfg, sd = lower_model(name)
-    return build(cfg, sd, dtype)
-
-
-def lower_image(H, W, B=LOWER_B):
-    return synth_image(B, H, W, seed=1000 * H + W)
-
-
 @functools.lru_cache(maxsize=None)
 def lower_oracle(name, H, W, storage=None):
     """(sr, qa) of the oracle on the LOWER_B images, computed once per model, size and mode and never changed."""

@@ -2,30 +2,15 @@
 on its own, against the CPU oracle (torch CPU float32) on the same inputs.  Inputs and weights are
 rounded to the compute dtype first, so what is measured is the kernel's arithmetic."""
 
-import ctypes
-
 import pytest
 import torch
 import torch.nn.functional as F
 
-from gpu_util import DTYPES, assert_op_close, alloc_act, from_act, op_conv, pad16, pad_part, q, stream_ptr, to_act
+from gpu_util import DTYPES, assert_op_close, alloc_act, from_act, pad16, pad_part, q, to_act
+from op_util import dev_w, op_conv, rnd, run_entry, set_knobs, wrnd
 from oracle import mewzoom_oracle as oracle
-from ultrazoom_amd import _ffi
-from ultrazoom_amd.synth import hash_uniform
 
 pytestmark = pytest.mark.gpu
-
-
-def rnd(shape, seed, scale=1.0):
-    n = 1
-    for s in shape:
-        n *= s
-    return torch.from_numpy(((2.0 * hash_uniform(n, seed) - 1.0) * scale).reshape(shape))
-
-
-def wrnd(shape, seed):
-    fan_in = shape[1] * shape[2] * shape[3]
-    return rnd(shape, seed, (3.0 / fan_in) ** 0.5 * 1.7)
 
 
 CONV_CASES = [
@@ -84,10 +69,7 @@ def test_conv3x3_persistent(dt, case, monkeypatch):
     w = q(wrnd((cout, cin, 3, 3), 12), dtype)
     outs = []
     for env in ({"MZ_PERSIST_WGS": "8"}, {"MZ_PERSIST_WGS": "16"}, {"MZ_NO_PERSIST": "1"}, {"MZ_PERSIST_WGS": "8", "MZ_NO_S16": "1"}):
-        for k in ("MZ_PERSIST_WGS", "MZ_NO_PERSIST", "MZ_NO_S16"):
-            monkeypatch.delenv(k, raising=False)
-        for k, v in env.items():
-            monkeypatch.setenv(k, v)
+        set_knobs(monkeypatch, env)
         out = alloc_act(B, cout, H, W, dtype)
         op_conv(dtype, 0, to_act(x, dtype), None, w, 0.0, out, B, H, W, cin, cout, silu=silu)
         outs.append(out)
@@ -109,7 +91,7 @@ def test_subpixel_conv_persistent(dt, monkeypatch):
     cq = cout // 4
     x = q(rnd((B, cin, H, W), 13), dtype)
     w = q(wrnd((cout, cin, 3, 3), 14), dtype)
-    monkeypatch.setenv("MZ_PERSIST_WGS", "8")
+    set_knobs(monkeypatch, wgs=8)
     out = alloc_act(B, cq, Hout, Wout, dtype)
     op_conv(dtype, 1, to_act(x, dtype), None, w, 0.0, out, B, H, W, cin, cout, Hout, Wout)
     want = oracle.fit_to(oracle.subpixel_conv(x, w), (Hout, Wout))
@@ -216,8 +198,6 @@ def test_mix_c192_both_kernels(dt, case, wgs, monkeypatch):
     that every wave walks several 32-pixel units (the loop that loads the next unit between the stores of the current one)."""
     dtype = DTYPES[dt]
     B, H, W = case
-    if wgs:
-        monkeypatch.setenv("MZ_PERSIST_WGS", wgs)
     c = 192
     x = q(rnd((B, c, H, W), 27), dtype)
     z = q(rnd((B, c, H, W), 28), dtype)
@@ -226,10 +206,7 @@ def test_mix_c192_both_kernels(dt, case, wgs, monkeypatch):
     want = oracle.residual_mix(x, z, w, torch.tensor(alpha))
     outs = {}
     for knob in ("0", "1"):
-        if knob == "1":
-            monkeypatch.setenv("MZ_NO_MIX16B", "1")
-        else:
-            monkeypatch.delenv("MZ_NO_MIX16B", raising=False)
+        set_knobs(monkeypatch, {"MZ_NO_MIX16B": "1"} if knob == "1" else {}, wgs)
         out = alloc_act(B, c, H, W, dtype)
         op_conv(dtype, 3, to_act(x, dtype), to_act(z, dtype), w, alpha, out, B, H, W, 2 * c, c)
         outs[knob] = from_act(out, c)
@@ -246,11 +223,7 @@ def test_stem(dt, case):
     w = rnd((c, 3, 1, 1), 11)
     b = rnd((c,), 12, 0.1)
     out = alloc_act(B, c, H, W, dtype)
-    xd, wd, bd = x.to("cuda", dtype).contiguous(), w.cuda(), b.cuda()
-    _ffi.check(_ffi.lib().mz_op_stem(
-        _ffi.dtype_code(dtype), ctypes.c_void_p(xd.data_ptr()), ctypes.c_void_p(wd.data_ptr()),
-        ctypes.c_void_p(bd.data_ptr()), ctypes.c_void_p(out.data_ptr()), B, H, W, c, ctypes.c_void_p(stream_ptr())))
-    torch.cuda.synchronize()
+    run_entry("stem", case, dt, {"x": x.to("cuda", dtype).contiguous(), "w": dev_w(w), "b": dev_w(b)}, out)
     want = F.conv2d(x, w, b)
     assert_op_close(from_act(out, c), want, dt)
     if pad16(c) > c:
@@ -278,12 +251,7 @@ def test_final_subpixel_bicubic_add_clamp(dt, case):
     img = q(rnd((B, 3, Hi, Wi), 14).abs(), dtype)
     w = q(wrnd((12, cin, 3, 3), 15) * 0.5, dtype)
     out = torch.full((B, 3, 2 * H, 2 * W), 7.0, dtype=dtype, device="cuda")
-    fd, imd, wd = to_act(feat, dtype), img.to("cuda", dtype).contiguous(), w.cuda()
-    _ffi.check(_ffi.lib().mz_op_final(
-        _ffi.dtype_code(dtype), ctypes.c_void_p(fd.data_ptr()), ctypes.c_void_p(imd.data_ptr()),
-        ctypes.c_void_p(wd.data_ptr()), ctypes.c_void_p(out.data_ptr()), B, H, W, cin, R, clamp,
-        ctypes.c_void_p(stream_ptr())))
-    torch.cuda.synchronize()
+    run_entry("final", case, dt, {"feat": to_act(feat, dtype), "img": img.to("cuda", dtype).contiguous(), "w": dev_w(w)}, out)
     want = oracle.bicubic_upsample(img, R) + oracle.subpixel_conv(feat, w)
     if clamp:
         want = want.clamp(0, 1)

@@ -6,8 +6,8 @@ and stores staying inside their tensors: every run here is an ordinary, valid ca
 import pytest
 import torch
 
+from degrade_ref import DTYPES, ELEM, hip, image, shape_id
 from poison_util import Arena
-from test_degrade_gpu import DTYPES, ELEM, hip, image, shape_id
 from ultrazoom_amd import _ffi
 
 pytestmark = pytest.mark.gpu

@@ -8,8 +8,8 @@ import pytest
 import torch
 
 import ensemble_ref as ref
+from ensemble_ref import DTYPES, pass_results, random_bits, shape_id, stream
 from poison_util import Arena
-from test_dihedral_gpu import DTYPES, pass_results, random_bits, shape_id, stream
 from ultrazoom_amd import _ffi, dihedral
 
 pytestmark = pytest.mark.gpu

@@ -13,8 +13,8 @@ import pytest
 import torch
 
 from golden_util import GoldenCase
+from model_util import FUZZ_CONFIGS, lower_built, lower_image
 from poison_util import Arena, room
-from test_model_gpu import FUZZ_CONFIGS, lower_built, lower_image
 from ultrazoom_amd import MewZoom
 from ultrazoom_amd.synth import synth_image, synth_state_dict
 

@@ -7,7 +7,7 @@ import pytest
 import torch
 
 from poison_util import Arena
-from test_resize_gpu import DTYPES, ELEM, RAGGED, TAPS66, UP3, hip_resize, image, shape_id
+from resize_util import DTYPES, ELEM, RAGGED, TAPS66, UP3, hip_resize, image, shape_id
 from ultrazoom_amd import _ffi
 
 pytestmark = pytest.mark.gpu

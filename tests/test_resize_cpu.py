@@ -58,9 +58,9 @@ def test_tap_tables_are_torchs_weight_matrix(axis, filt):
 @pytest.mark.parametrize("shape", [((5, 1), (2, 1)), ((9, 7), (4, 1)), ((1, 7), (2, 3)), ((16, 16), (1, 1)), ((2, 2), (7, 9)), ((9, 7), (4, 3))],
                          ids=lambda s: f"{s[0][0]}x{s[0][1]}to{s[1][0]}x{s[1][1]}")
 def test_the_gpu_tests_checker_is_torchs_weight_matrices(shape, filt):
-    """tests/test_resize_gpu.want64_of at the smallest shapes, outputs of one column included (which it runs transposed, around a fault
+    """tests/resize_util.want64_of at the smallest shapes, outputs of one column included (which it runs transposed, around a fault
     of torch's kernel), against out = My^T x Mx with torch's own weight matrices (interpolate of an identity, as above)."""
-    from test_resize_gpu import want64_of
+    from resize_util import want64_of
 
     (hin, win), (hout, wout) = shape
 

@@ -4,19 +4,15 @@ describe the call, a Conv3Call, exactly as they do for mz_forward and the mz_op_
 runs.  The expected names are those mz_debug_last_kernel() reported for these layers when the selection was spread over the
 launch code; a row that changes is a change of the kernel that runs, and belongs in a pull request that says so."""
 
-import ctypes
-
 import pytest
 
+from op_util import select_op, set_knobs
 from ultrazoom_amd import _ffi
 
 F32, BF16, F16 = _ffi.MZ_F32, _ffi.MZ_BF16, _ffi.MZ_F16
 # mz_debug_select's ops (include/mewzoom_hip.h)
 CONV1, CONV, UP, HEAD, QA, FILM, CONV2, MIX = range(8)
 CUS = 256  # MI355X
-# every knob read_knobs() reads; each row sees only its own
-KNOBS = ("MZ_NO_WIDE", "MZ_NO_FUSE", "MZ_NO_S16", "MZ_NO_FUSE16", "MZ_NO_MIX16B", "MZ_NO_R", "MZ_NO_T", "MZ_NO_R2", "MZ_NO_BLK4",
-         "MZ_KPAD_PCT", "MZ_NO_PERSIST", "MZ_PERSIST_WGS")
 
 # (dtype, op, cin, cout, B, H, W, knobs, kernel).  Every distinct 3x3 / mix layer of bench.py's workloads (UP: cout = 4 x the shuffled
 # channels; CONV2: cin = the hidden channels, the fused family where mz_forward fuses conv2 and the mix; MIX: the unfused mix, cin = 2 cout).
@@ -322,23 +318,9 @@ TABLE = [
 ]
 
 
-def _lib():
-    lib = ctypes.CDLL(str(_ffi.LIB_PATH))
-    lib.mz_debug_select.restype = ctypes.c_char_p
-    lib.mz_debug_select.argtypes = [ctypes.c_int] * 8
-    lib.mz_last_error.restype = ctypes.c_char_p
-    return lib
-
-
 def _select(monkeypatch, dtype, op, cin, cout, B, H, W, env=""):
-    for k in KNOBS:
-        monkeypatch.delenv(k, raising=False)
-    for kv in env.split():
-        k, v = kv.split("=")
-        monkeypatch.setenv(k, v)
-    lib = _lib()
-    got = lib.mz_debug_select(dtype, op, cin, cout, B, H, W, CUS)
-    return (got.decode() if got is not None else None), lib.mz_last_error().decode()
+    set_knobs(monkeypatch, dict(kv.split("=") for kv in env.split()))  # each row sees only its own knobs
+    return select_op(dtype, op, cin, cout, B, H, W, CUS), _ffi.lib().mz_last_error().decode()
 
 
 @pytest.mark.parametrize("row", TABLE, ids=lambda r: "-".join(str(v) for v in r[:7]) + ("-" + r[7].replace(" ", "+") if r[7] else ""))

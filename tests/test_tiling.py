@@ -4,6 +4,7 @@ import pytest
 import torch
 
 from golden_util import GoldenCase
+from op_util import set_knobs
 from ultrazoom_amd import MewZoom
 from ultrazoom_amd.synth import synth_image
 from ultrazoom_amd.tiling import receptive_field, upscale_tiled
@@ -143,10 +144,7 @@ def test_tiled_equals_untiled_96_channels_hidden_ratio_2(dt, no_r, monkeypatch):
     (Slices of 200 / 296 / 224 columns against a 328-column image: where the 8 x 48 tiles of conv3r pad fewer pixels than conv3s's
     8 x 64 tiles differs from slice to slice -- 240 against 256, 336 against 320.)"""
     dtype = {"bf16": torch.bfloat16, "f16": torch.float16}[dt]
-    if no_r:
-        monkeypatch.setenv("MZ_NO_R", "1")
-    else:
-        monkeypatch.delenv("MZ_NO_R", raising=False)
+    set_knobs(monkeypatch, {"MZ_NO_R": "1"} if no_r else {})
     cfg = dict(upscale_ratio=2, primary_channels=96, primary_layers=2, secondary_channels=96, secondary_layers=2,
                tertiary_channels=96, tertiary_layers=2, quaternary_channels=96, quaternary_layers=2, hidden_ratio=2, num_deg_features=3)
     from ultrazoom_amd.synth import synth_state_dict

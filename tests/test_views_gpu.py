@@ -10,6 +10,7 @@ import pytest
 import torch
 
 from golden_util import GoldenCase
+from op_util import selected, set_knobs
 from ultrazoom_amd import MewZoom, _ffi
 from ultrazoom_amd.synth import synth_image, synth_state_dict
 from ultrazoom_amd.tiling import receptive_field, upscale_tiled
@@ -279,8 +280,6 @@ def test_tiled_equals_untiled_48_channels_hidden_ratio_2(kind):
     Both sum in another order than the kernels they replace, so a tile must choose them exactly as the whole image does: the choice
     is asserted for the image and for the centre tile's slice (mz_debug_select runs the function the launches run), the result
     bit for bit."""
-    import ctypes
-
     cfg = dict(upscale_ratio=2, primary_channels=48, primary_layers=2, secondary_channels=96, secondary_layers=2,
                tertiary_channels=96, tertiary_layers=2, quaternary_channels=96, quaternary_layers=2, hidden_ratio=2, num_deg_features=3)
     m = MewZoom(**cfg)
@@ -289,19 +288,17 @@ def test_tiled_equals_untiled_48_channels_hidden_ratio_2(kind):
     halo = receptive_field(cfg)
     H, W, tile = 2 * 104 + halo + 16, 2 * 104 + halo + 24, (104, 104)
     assert all(t > halo and n > 2 * t + halo for t, n in zip(tile, (H, W))), "the centre tile must be cut on all four sides"
-    lib = _ffi.lib()
-    lib.mz_debug_select.restype = ctypes.c_char_p
     cus = torch.cuda.get_device_properties(0).multi_processor_count // 8 * 8
     for h, w in ((H, W), (tile[0] + 2 * halo, tile[1] + 2 * halo)):
-        assert lib.mz_debug_select(_ffi.dtype_code(MODEL_DTYPE[kind]), 0, 48, 96, 1, h, w, cus) == b"conv3r_ragged"
-        assert lib.mz_debug_select(_ffi.dtype_code(MODEL_DTYPE[kind]), 6, 96, 48, 1, h, w, cus) == b"conv3t_fused"
+        assert selected("conv", (1, h, w, 48, 96, 1), kind, cus=cus) == "conv3r_ragged"
+        assert selected("conv_mix", (1, h, w, 96, 48), kind, cus=cus) == "conv3t_fused"
     x = image(kind, 1, H, W, 32)
     assert torch.equal(upscale_tiled(m, x, tile=tile), m.upscale(x))
 
 
 def test_f32_views_on_the_256_pixel_kernel(monkeypatch):
     """MZ_NO_WIDE=1 keeps the f32 image head on conv_kernel: its view instantiation against its dense one."""
-    monkeypatch.setenv("MZ_NO_WIDE", "1")
+    set_knobs(monkeypatch, {"MZ_NO_WIDE": "1"})
     case = GoldenCase("g1_2x_c16")
     m = MewZoom(**case.config)
     m.load_state_dict(case.weights())
