@@ -375,6 +375,25 @@ int mz_debug_tile_list(int B, int tiles_y, int tiles_x, int ntiles, int gm, int 
  * No reference counterpart. */
 const char* mz_debug_select(int dtype, int op, int cin, int cout, int B, int H, int W, int cus);
 
+/* One step of a forward pass (mz_debug_schedule).  kind: 0 stem, 1 conv3x3, 2 AdaptiveResidualMix, 3 PixelCrush, 4 zero border of an
+ * up-sampled tensor, 5 quality-head reduction.  op: mz_debug_select()'s op of a kind 1 / 2 step, else -1.  H x W: the input's pixels;
+ * Hout x Wout: the output's where they differ (ops 2 and 3, kinds 3 and 4), else 0.  fused: a block's conv2 with the mix in its epilogue.
+ * Operand j = 0 first input, 1 second input (the block input of a fused conv2, z of a mix, the low-resolution image of the image head),
+ * 2 output: off[j] = its byte offset in the workspace, or -1 none, -2 the input image, -3 the output image, -4 the quality output;
+ * bytes[j] = its extent (the images: as dense tensors of the handle's dtype).  kernel: the family a kind 1 / 2 step runs on, as
+ * mz_debug_select() names it; NULL for the other kinds. */
+typedef struct mz_debug_step {
+    int32_t kind, op, cin, cout, B, H, W, Hout, Wout, fused;
+    int64_t off[3];
+    uint64_t bytes[3];
+    const char* kernel;
+} mz_debug_step;
+
+/* Host-only (no GPU, no weights): the steps mz_forward launches for ONE micro-batch of B images of H x W pixels, in launch order, under
+ * the knobs the handle read when it was created, on a device of `cus` compute units; want_qa = 0: as upscale() runs it (out_qa NULL).
+ * At most `cap` steps are written to out.  Returns the number of steps, negative on bad arguments.  No reference counterpart. */
+int mz_debug_schedule(const mz_handle* h, int B, int H, int W, int want_qa, int cus, mz_debug_step* out, int cap);
+
 /* Host-only (no GPU): one packing of one layer's weights as the library plans and packs it.  dtype, op, cin, cout as for
  * mz_debug_select(), and op 8 = the gate weights of a block's mix, packed for the fused conv2 + mix (cin, cout: those of conv2).
  * layout: 0 the 32x32-MFMA packing every layer has, 1 3x3 for conv3s / conv3r, 2 mix16, 3 conv3s's fused gate, 4 mix16b,

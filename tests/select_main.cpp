@@ -1,13 +1,15 @@
-// Host-only driver of ultrazoom_amd/csrc/mz_plan.h and mz_select.h: layer plans, kernel choices, tile walks, tile lists and workspace
-// plans over the layers of tests/test_select_cpu.py's table, channel counts around every tile and chunk boundary, shapes from 1 x 1 to
-// 4320 x 7680 and 1 to 64 images.  tests/test_select_cpu.py compiles it with g++ -fsanitize=address,undefined
+// Host-only driver of ultrazoom_amd/csrc/mz_plan.h, mz_select.h and mz_schedule.h: planned models and their schedules (liveness and
+// extents of every operand) for the fixture configurations and bench.py's models, then layer plans, kernel choices, tile walks and tile
+// lists over the layers of those schedules, channel counts around every tile and chunk boundary, shapes from 1 x 1 to 4320 x 7680 and
+// 1 to 64 images.  tests/test_select_cpu.py compiles it with g++ -fsanitize=address,undefined
 // -fno-sanitize-recover=undefined and runs it: exit status 0 and no sanitizer report (a signed overflow in a tile count, an offset guard
-// or a workspace size would abort it).  Nothing of the library is linked: the two headers call nothing in HIP.
+// or a workspace size would abort it).  Nothing of the library is linked: the three headers call nothing in HIP.
 #include <stdio.h>
 
+#include <array>
 #include <set>
 
-#include "../ultrazoom_amd/csrc/mz_select.h"
+#include "../ultrazoom_amd/csrc/mz_schedule.h"
 
 using namespace mz;
 
@@ -19,31 +21,20 @@ static int g_failed = 0;
         }                                                           \
     } while (0)
 
-// every distinct (dtype, op, cin, cout) of tests/test_select_cpu.py's TABLE (ops: mz_debug_select's, include/mewzoom_hip.h)
-static const int kTableLayers[][4] = {
-    {0, 0, 48, 96}, {0, 0, 96, 192}, {0, 0, 192, 384}, {0, 0, 384, 768}, {0, 0, 768, 1536}, {0, 2, 96, 192}, {0, 2, 96, 384},
-    {0, 2, 192, 384}, {0, 2, 384, 768}, {0, 2, 768, 1536}, {0, 3, 48, 12}, {0, 3, 96, 12}, {0, 4, 384, 3}, {0, 4, 768, 3},
-    {0, 5, 96, 96}, {0, 6, 96, 48}, {0, 6, 192, 96}, {0, 6, 384, 192}, {0, 6, 768, 384}, {0, 6, 1536, 768}, {0, 7, 96, 48},
-    {0, 7, 192, 96}, {0, 7, 384, 192}, {0, 7, 768, 384}, {0, 7, 1536, 768}, {1, 0, 16, 32}, {1, 0, 16, 64}, {1, 0, 24, 48},
-    {1, 0, 32, 64}, {1, 0, 40, 80}, {1, 0, 48, 96}, {1, 0, 64, 128}, {1, 0, 72, 144}, {1, 0, 96, 48}, {1, 0, 96, 192},
-    {1, 0, 128, 256}, {1, 0, 136, 272}, {1, 0, 192, 384}, {1, 0, 256, 512}, {1, 0, 384, 768}, {1, 0, 768, 1536}, {1, 1, 16, 16},
-    {1, 1, 96, 96}, {1, 2, 16, 64}, {1, 2, 24, 96}, {1, 2, 32, 64}, {1, 2, 32, 128}, {1, 2, 40, 96}, {1, 2, 64, 128},
-    {1, 2, 72, 160}, {1, 2, 96, 192}, {1, 2, 96, 384}, {1, 2, 128, 256}, {1, 2, 136, 288}, {1, 2, 192, 384}, {1, 2, 256, 512},
-    {1, 2, 384, 768}, {1, 2, 768, 1536}, {1, 3, 16, 12}, {1, 3, 24, 12}, {1, 3, 32, 12}, {1, 3, 48, 12}, {1, 3, 96, 12},
-    {1, 4, 128, 3}, {1, 4, 136, 3}, {1, 4, 256, 3}, {1, 4, 384, 3}, {1, 4, 768, 3}, {1, 5, 48, 96}, {1, 5, 96, 96}, {1, 6, 16, 16},
-    {1, 6, 32, 16}, {1, 6, 48, 24}, {1, 6, 64, 16}, {1, 6, 64, 32}, {1, 6, 80, 40}, {1, 6, 96, 48}, {1, 6, 128, 64}, {1, 6, 144, 72},
-    {1, 6, 192, 96}, {1, 6, 256, 128}, {1, 6, 272, 136}, {1, 6, 384, 192}, {1, 6, 512, 256}, {1, 6, 768, 384}, {1, 6, 1536, 768},
-    {1, 7, 32, 16}, {1, 7, 48, 24}, {1, 7, 64, 32}, {1, 7, 80, 40}, {1, 7, 96, 48}, {1, 7, 128, 64}, {1, 7, 144, 72},
-    {1, 7, 192, 96}, {1, 7, 256, 128}, {1, 7, 272, 136}, {1, 7, 384, 192}, {1, 7, 512, 256}, {1, 7, 768, 384}, {1, 7, 1536, 768},
-    {2, 0, 16, 32}, {2, 0, 24, 48}, {2, 0, 32, 64}, {2, 0, 40, 80}, {2, 0, 64, 128}, {2, 0, 72, 144}, {2, 0, 96, 192},
-    {2, 0, 128, 256}, {2, 0, 136, 272}, {2, 0, 192, 384}, {2, 0, 256, 512}, {2, 0, 384, 768}, {2, 0, 768, 1536}, {2, 2, 32, 64},
-    {2, 2, 40, 96}, {2, 2, 64, 128}, {2, 2, 72, 160}, {2, 2, 96, 384}, {2, 2, 128, 256}, {2, 2, 136, 288}, {2, 2, 192, 384},
-    {2, 2, 256, 512}, {2, 2, 384, 768}, {2, 2, 768, 1536}, {2, 3, 16, 12}, {2, 3, 24, 12}, {2, 3, 32, 12}, {2, 3, 96, 12},
-    {2, 4, 128, 3}, {2, 4, 136, 3}, {2, 4, 256, 3}, {2, 4, 768, 3}, {2, 5, 32, 64}, {2, 6, 32, 16}, {2, 6, 48, 24}, {2, 6, 64, 32},
-    {2, 6, 80, 40}, {2, 6, 128, 64}, {2, 6, 144, 72}, {2, 6, 192, 96}, {2, 6, 256, 128}, {2, 6, 272, 136}, {2, 6, 384, 192},
-    {2, 6, 512, 256}, {2, 6, 768, 384}, {2, 6, 1536, 768}, {2, 7, 32, 16}, {2, 7, 48, 24}, {2, 7, 64, 32}, {2, 7, 80, 40},
-    {2, 7, 128, 64}, {2, 7, 144, 72}, {2, 7, 192, 96}, {2, 7, 256, 128}, {2, 7, 272, 136}, {2, 7, 384, 192}, {2, 7, 512, 256},
-    {2, 7, 768, 384}, {2, 7, 1536, 768},
+// the models whose schedules are built: the fixtures' configurations (2X / 4X / 8X; C = 16, 24, 32; hidden ratio 1, 2, 4) and bench.py's two
+struct Config { int ratio, ch[4], layers[4], hidden_ratio, features; };
+static const Config kFixtures[] = {
+    {2, {16, 32, 64, 128}, {2, 2, 2, 2}, 2, 3}, {4, {16, 32, 64, 128}, {2, 2, 2, 2}, 2, 3}, {8, {16, 32, 64, 128}, {2, 2, 2, 2}, 2, 3},
+    {2, {16, 32, 64, 128}, {2, 2, 2, 2}, 1, 3}, {2, {16, 32, 64, 128}, {2, 2, 2, 2}, 4, 3}, {2, {16, 32, 64, 128}, {3, 2, 5, 4}, 2, 3},
+    {2, {24, 40, 72, 136}, {2, 2, 2, 2}, 2, 5}, {4, {24, 40, 72, 136}, {2, 2, 2, 2}, 2, 3}, {4, {32, 64, 128, 256}, {2, 2, 2, 4}, 2, 3},
+};
+static const Config kBench[] = {
+    {4, {96, 192, 384, 768}, {8, 8, 8, 16}, 2, 3},  // cfg3
+    {2, {48, 96, 192, 384}, {4, 4, 4, 8}, 2, 3},    // cfg2
+};
+// (dtype, op, cin, cout) of tests/test_select_cpu.py's knob, tile-shape and FiLM rows that no schedule above has (ops: mz_debug_select's)
+static const int kExtraLayers[][4] = {
+    {0, 5, 96, 96}, {1, 0, 96, 48}, {1, 1, 16, 16}, {1, 1, 96, 96}, {1, 5, 48, 96}, {1, 5, 96, 96}, {2, 5, 32, 64},
 };
 static const int kChannels[] = {1, 15, 16, 17, 31, 32, 33, 48, 96, 191, 192, 193, 384, 768, 1536, 2047, 2048};
 static const int kShapes[][2] = {{1, 1}, {1, 2}, {2, 1}, {2, 3}, {8, 8}, {9, 11}, {37, 45}, {67, 120}, {135, 240}, {540, 960}, {1080, 1920}, {2160, 3840}, {4320, 7680}};
@@ -123,44 +114,127 @@ static void run_layer(const Knobs& k, int dtype, int op, int cin, int cout, int 
     if (ch.tile_list) check_tile_list(w, B, ch.th, ch.tw);
 }
 
-// offsets of a workspace plan: 256-aligned, ascending, each buffer ending before the next begins
-static void check_plan(const ModelDims& m, int B, int H, int W) {
-    Plan p;
-    const int nb = default_micro_batch(m, B, H, W, 0);
-    EXPECT(nb >= 1 && nb <= B);
-    make_plan(m, nb, H, W, p);
-    const size_t sz = dtype_size(m.dtype);
-    std::vector<std::pair<size_t, size_t>> bufs;  // offset, bytes, in the order make_plan takes them
+// the buffers of a workspace plan as {offset, bytes}, in the order make_plan takes them: 256-aligned, ascending, each ending before the next
+static std::vector<std::pair<size_t, size_t>> check_plan(const ModelDims& m, const Plan& p) {
+    const size_t sz = dtype_size(m.dtype), nb = p.nb;
+    std::vector<std::pair<size_t, size_t>> bufs;
     for (int l = 0; l < 4; ++l) {
-        const size_t px = (size_t)nb * p.hs[l] * p.ws[l], c = px * pad16(m.ch[l]) * sz;
+        const size_t px = nb * p.hs[l] * p.ws[l], c = px * pad16(m.ch[l]) * sz;
         for (int i = 0; i < 3; ++i) bufs.push_back({p.R[l][i], c});
         bufs.push_back({p.HID[l], px * pad16(m.hidden_ratio * m.ch[l]) * sz});
         bufs.push_back({p.Z[l], c});
         if (l < 3) bufs.push_back({p.U[l], c});
     }
     for (int j = 1; j < m.nhead; ++j) {
-        const size_t px = (size_t)nb * ((size_t)H << j) * ((size_t)W << j), c = px * pad16(m.ch[0]) * sz;
+        const size_t px = nb * ((size_t)p.hs[0] << j) * ((size_t)p.ws[0] << j), c = px * pad16(m.ch[0]) * sz;
         bufs.push_back({p.HR[j][0], c});
         bufs.push_back({p.HR[j][1], c});
         bufs.push_back({p.HHID[j], px * pad16(m.hidden_ratio * m.ch[0]) * sz});
         bufs.push_back({p.HZ[j], c});
     }
-    bufs.push_back({p.QA, (size_t)nb * p.hs[3] * p.ws[3] * pad16(m.num_deg_features) * sz});
+    bufs.push_back({p.QA, nb * p.hs[3] * p.ws[3] * pad16(m.num_deg_features) * sz});
     for (size_t i = 0; i < bufs.size(); ++i) {
         EXPECT(bufs[i].first % 256 == 0 && bufs[i].second > 0);
         EXPECT(bufs[i].first + bufs[i].second <= (i + 1 < bufs.size() ? bufs[i + 1].first : p.total));
     }
     EXPECT(bufs[0].first == 0 && p.total % 256 == 0);
+    return bufs;
+}
+
+static std::set<std::array<int, 4>> g_layers;  // (dtype, op, cin, cout) of every 3x3 / mix step scheduled
+static long long g_steps = 0;
+
+// One micro-batch of the model: every operand has the extent of its shape and sits in a buffer of the plan that holds it; what a step
+// reads, an earlier step wrote and none since has touched; no step but the zero border writes over its own input; the image comes in
+// at the first step and leaves at the last.  (tests/test_schedule_cpu.py asserts the same of mz_debug_schedule.)
+static void check_schedule(const Config& cfg, int dtype, const Knobs& k, int B, int H, int W, bool want_qa) {
+    const int nhead = cfg.ratio == 2 ? 1 : cfg.ratio == 4 ? 2 : 3;
+    const ModelDims dims = {dtype, {cfg.ch[0], cfg.ch[1], cfg.ch[2], cfg.ch[3]}, cfg.hidden_ratio, nhead, cfg.features};
+    Model<LayerPlan> m;
+    plan_model(m, dims, cfg.layers);
+    Plan p;
+    const int nb = default_micro_batch(dims, B, H, W, 0);
+    EXPECT(nb >= 1 && nb <= B);
+    make_plan(dims, nb, H, W, p);
+    const auto bufs = check_plan(dims, p);
+    const auto steps = make_schedule(m, dims, p, k, want_qa, cfg.ratio, 1);
+    const size_t sz = dtype_size(dtype);
+    auto bytes = [&](long long hh, long long ww, int c) { return (size_t)nb * hh * ww * pad16(c) * sz; };
+    std::vector<std::pair<size_t, size_t>> live;  // {begin, end} of the tensors in the workspace
+    auto overlaps = [](const BufRef& a, const BufRef& b) {
+        return a.where == BUF_WS && b.where == BUF_WS && a.off < b.off + b.bytes && b.off < a.off + a.bytes;
+    };
+    for (size_t i = 0; i < steps.size(); ++i) {
+        const Step<LayerPlan>& s = steps[i];
+        const bool conv3 = s.kind == ST_CONV3, d2s = s.role == ROLE_D2S || s.kind == ST_ZERO_BORDER, head = s.role == ROLE_HEAD;
+        ++g_steps;
+        // extents
+        const size_t image = (size_t)nb * 3 * H * W * sz;
+        EXPECT(s.B == nb && s.cin > 0 && s.cout > 0);
+        if (s.kind == ST_STEM) EXPECT(i == 0 && s.in.where == BUF_IMAGE_IN && s.in.bytes == image && s.cin == 3);
+        else if (s.kind == ST_ZERO_BORDER) EXPECT(s.in.where == BUF_WS && s.in.off == s.out.off && s.in.bytes == s.out.bytes);
+        else EXPECT(s.in.where == BUF_WS && s.in.bytes == bytes(s.H, s.W, s.kind == ST_MIX || s.kind == ST_QA_REDUCE ? s.cout : s.cin));
+        if (s.kind == ST_MIX || s.fused) EXPECT(s.in1.where == BUF_WS && s.in1.bytes == bytes(s.H, s.W, s.cout));
+        else if (head) EXPECT(s.in1.where == BUF_IMAGE_IN && s.in1.bytes == image && s.Hout == cfg.ratio * H && s.Wout == cfg.ratio * W);
+        else EXPECT(s.in1.where == BUF_NONE);
+        if (head) EXPECT(i + 1 == steps.size() && s.out.where == BUF_IMAGE_OUT && s.out.bytes == (size_t)nb * 3 * s.Hout * s.Wout * sz);
+        else if (s.kind == ST_QA_REDUCE) EXPECT(s.out.where == BUF_QA_OUT && s.out.bytes == (size_t)nb * s.cout * 4);
+        else if (d2s) EXPECT(s.out.where == BUF_WS && s.out.bytes == (size_t)nb * s.Hout * s.Wout * s.layer->cq_p * sz && s.Hout >= 2 * s.H && s.Wout >= 2 * s.W);
+        else if (s.kind == ST_CRUSH) EXPECT(s.out.where == BUF_WS && s.out.bytes == bytes(s.Hout, s.Wout, s.cout) && s.Hout == s.H / 2 && s.Wout == s.W / 2);
+        else EXPECT(s.out.where == BUF_WS && s.out.bytes == bytes(s.H, s.W, s.cout));
+        // each workspace operand inside one buffer of the plan
+        for (const BufRef* b : {&s.in, &s.in1, &s.out}) {
+            if (b->where != BUF_WS) continue;
+            bool found = false;
+            for (const auto& buf : bufs) found = found || (buf.first == b->off && b->bytes <= buf.second);
+            EXPECT(found && b->off + b->bytes <= p.total);
+        }
+        // liveness
+        for (const BufRef* b : {&s.in, &s.in1}) {
+            if (b->where != BUF_WS) continue;
+            bool found = false;
+            for (const auto& t : live) found = found || (t.first == b->off && t.second == b->off + b->bytes);
+            EXPECT(found);
+        }
+        if (s.kind != ST_ZERO_BORDER) EXPECT(!overlaps(s.out, s.in) && !overlaps(s.out, s.in1));
+        if (s.out.where == BUF_WS) {
+            const size_t b0 = s.out.off, b1 = s.out.off + s.out.bytes;
+            for (size_t t = live.size(); t-- > 0;)
+                if (live[t].first < b1 && b0 < live[t].second) live.erase(live.begin() + t);
+            live.push_back({b0, b1});
+        }
+        // the layer, for the sweep below
+        static const int role_op[] = {-1, 0, 6, 4, 2, 3};
+        if (conv3) g_layers.insert({dtype, role_op[s.role], s.cin, s.cout});
+        if (s.kind == ST_MIX) g_layers.insert({dtype, 7, s.cin, s.cout});
+        // with MZ_NO_FUSE=1 no block fuses; otherwise those of at most 96 channels do
+        if (s.role == ROLE_CONV2) EXPECT(s.fused == (k.fuse && s.cout <= 96));
+    }
+    EXPECT(!steps.empty() && steps.back().role == ROLE_HEAD);
 }
 
 int main() {
     Knobs other;  // row-major tile walk, eight persistent workgroups
     other.blk4 = 0; other.persist = 8;
+    Knobs nofuse;  // MZ_NO_FUSE=1
+    nofuse.fuse = false;
     const Knobs knobs[] = {Knobs(), other};
+    // the schedules: the fixture configurations at the sizes of tests/test_schedule_cpu.py, bench.py's models up to 4320 x 7680
+    for (int dtype = 0; dtype < 3; ++dtype)
+        for (const Knobs& k : {Knobs(), nofuse})
+            for (bool want_qa : {false, true}) {
+                for (const Config& cfg : kFixtures)
+                    for (const auto& s : {std::array<int, 2>{8, 8}, {37, 45}, {64, 120}}) check_schedule(cfg, dtype, k, 2, s[0], s[1], want_qa);
+                for (const Config& cfg : kBench)
+                    for (const auto& s : kShapes)
+                        for (int B : kBatches)
+                            if (s[0] >= 8 && s[1] >= 8) check_schedule(cfg, dtype, k, B, s[0], s[1], want_qa);
+            }
+    for (const auto& l : kExtraLayers) EXPECT(g_layers.insert({l[0], l[1], l[2], l[3]}).second);  // (a layer the schedules have is no extra)
     for (const Knobs& k : knobs)
         for (int cus : kCus) {
-            // the table's layers at every shape and batch
-            for (const auto& l : kTableLayers)
+            // the schedules' layers at every shape and batch
+            for (const auto& l : g_layers)
                 for (const auto& s : kShapes)
                     for (int B : kBatches) run_layer(k, l[0], l[1], l[2], l[3], B, s[0], s[1], cus);
             // every role at channel counts around the 16 / 32 / 48 / 96 / 192 boundaries, at the ends and the middle of the shapes
@@ -177,14 +251,7 @@ int main() {
     EXPECT(!plan_debug_layer(b, DT_BF16, 9, 96, 96, &why) && why.code == MZ_ERR_INVALID_ARGUMENT && why.msg[0]);
     EXPECT(!plan_debug_layer(b, DT_BF16, 7, 96, 96, &why) && why.msg[0]);
     EXPECT(!plan_debug_layer(b, DT_BF16, 8, 768, 384, &why) && why.msg[0]);
-    // the workspace of bench.py's three workloads, every dtype
-    for (int dtype = 0; dtype < 3; ++dtype) {
-        check_plan({dtype, {96, 192, 384, 768}, 2, 2, 3}, 16, 1080, 1920);  // cfg3_1080p
-        check_plan({dtype, {96, 192, 384, 768}, 2, 2, 3}, 16, 540, 960);    // cfg3_540p
-        check_plan({dtype, {48, 96, 192, 384}, 2, 1, 3}, 32, 540, 960);     // cfg2
-        check_plan({dtype, {16, 32, 64, 128}, 4, 3, 3}, 64, 8, 8);          // the smallest image, 8X
-    }
-    printf("%lld layer calls, %lld tile lists\n", g_choices, g_lists);
+    printf("%lld scheduled steps, %d layers, %lld layer calls, %lld tile lists\n", g_steps, (int)g_layers.size(), g_choices, g_lists);
     if (g_failed) return 1;
     printf("selection OK\n");
     return 0;

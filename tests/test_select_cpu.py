@@ -343,9 +343,10 @@ def test_refusals_say_why(monkeypatch):
 
 
 def test_planning_and_selection_survive_the_sanitizers(tmp_path):
-    """tests/select_main.cpp -- the layers of TABLE and channel counts around every tile and chunk boundary, 8 x 8 to 4320 x 7680 pixels,
-    1 to 64 images, 0 / 8 / 256 CUs: plans, choices, walks, tile lists (every tile exactly once) and workspace plans -- built from
-    mz_plan.h and mz_select.h alone with the address and undefined-behaviour sanitizers: a signed overflow in a tile count or an offset
+    """tests/select_main.cpp -- planned models and their schedules (liveness and extents of every operand), then the layers of those
+    schedules and channel counts around every tile and chunk boundary, 8 x 8 to 4320 x 7680 pixels, 1 to 64 images, 0 / 8 / 256 CUs:
+    plans, choices, walks, tile lists (every tile exactly once) and workspace plans -- built from mz_plan.h, mz_select.h and
+    mz_schedule.h alone with the address and undefined-behaviour sanitizers: a signed overflow in a tile count or an offset
     guard ends it.  A stand-alone host program: nothing of it is loaded here, nothing of HIP is linked."""
     import os
     import shutil

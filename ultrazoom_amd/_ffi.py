@@ -48,6 +48,13 @@ class MzImageView(Structure):
     _fields_ = [("data", c_void_p), ("stride", c_int64 * 4)]
 
 
+class MzDebugStep(Structure):
+    """mz_debug_step: one step of a forward pass (include/mewzoom_hip.h documents the fields)."""
+
+    _fields_ = [(name, c_int32) for name in "kind op cin cout B H W Hout Wout fused".split()] + [
+        ("off", c_int64 * 3), ("bytes", c_uint64 * 3), ("kernel", c_char_p)]
+
+
 class MewZoomHipError(RuntimeError):
     def __init__(self, code: int, message: str):
         super().__init__(f"libmewzoom_hip error {code}: {message}")
@@ -121,6 +128,8 @@ def _declare(lib) -> None:
     lib.mz_version.restype = c_char_p
     lib.mz_flops_per_image.argtypes = [H, c_int, c_int]
     lib.mz_flops_per_image.restype = c_double
+    lib.mz_debug_schedule.argtypes = [H, c_int, c_int, c_int, c_int, c_int, POINTER(MzDebugStep), c_int]
+    lib.mz_debug_schedule.restype = c_int
     lib.mz_profile_enable.argtypes = [H, c_int]
     lib.mz_profile_read.argtypes = [H] + [POINTER(c_double)] * 5
     lib.mz_profile_dump.argtypes = [H, c_char_p]
@@ -415,6 +424,18 @@ class Handle:
 
     def flops_per_image(self, H: int, W: int) -> float:
         return float(lib().mz_flops_per_image(self._h, H, W))
+
+    def schedule(self, B: int, H: int, W: int, want_qa: bool, cus: int = 256):
+        """mz_debug_schedule (host only): the steps of one micro-batch of B images, in launch order, as a list of dicts with
+        mz_debug_step's fields (off, bytes: tuples of in, second in, out; kernel: a str or None)."""
+        n = lib().mz_debug_schedule(self._h, B, H, W, int(bool(want_qa)), cus, None, 0)  # how many
+        if n < 0:
+            check(n)
+        steps = (MzDebugStep * n)()
+        lib().mz_debug_schedule(self._h, B, H, W, int(bool(want_qa)), cus, steps, n)
+        ints = [name for name, _ in MzDebugStep._fields_[:10]]
+        return [dict({k: int(getattr(s, k)) for k in ints}, off=tuple(s.off), bytes=tuple(s.bytes),
+                     kernel=s.kernel.decode() if s.kernel else None) for s in steps]
 
     def profile_enable(self, on: bool) -> None:
         check(lib().mz_profile_enable(self._h, int(on)))

@@ -103,23 +103,40 @@ extern "C" const char* mz_version(void) { return "mewzoom_hip 0.1 (gfx950)"; }
 
 extern "C" double mz_flops_per_image(const mz_handle* h, int H, int W) {
     if (!h) return 0.0;
-    const int hr = h->cfg.hidden_ratio;
-    int hs[4] = {H, 0, 0, 0}, ws[4] = {W, 0, 0, 0};
-    for (int i = 1; i < 4; ++i) { hs[i] = hs[i - 1] / 2; ws[i] = ws[i - 1] / 2; }
-    double macs = 3.0 * h->dims.ch[0] * H * W;
-    auto blk = [&](double c) { return (18.0 * hr + 2.0) * c * c; };
-    for (int l = 0; l < 4; ++l) macs += (h->enc[l] + h->dec[l]) * blk(h->dims.ch[l]) * hs[l] * ws[l];
-    for (int l = 0; l < 3; ++l) {
-        macs += 4.0 * h->dims.ch[l] * h->dims.ch[l + 1] * hs[l + 1] * ws[l + 1];
-        macs += 9.0 * h->dims.ch[l + 1] * 4.0 * h->dims.ch[l] * hs[l + 1] * ws[l + 1];
-        macs += 2.0 * h->dims.ch[l] * h->dims.ch[l] * hs[l] * ws[l];
+    Plan p;
+    make_plan(h->dims, 1, H, W, p);
+    long long macs = 0;
+    for (const auto& st : make_schedule(h->model, h->dims, p, h->ctx.knobs, /*want_qa*/ true, h->cfg.upscale_ratio, 0)) macs += step_macs(st);
+    return 2.0 * (double)macs;
+}
+
+// Host-only (no GPU, no weights): the steps of one micro-batch of B images of H x W pixels under the handle's own knobs, and the kernel a
+// device of `cus` compute units runs each 3x3 convolution and mix on.  Writes at most cap steps to out, returns their number.
+extern "C" int mz_debug_schedule(const mz_handle* h, int B, int H, int W, int want_qa, int cus, mz_debug_step* out, int cap) {
+    if (!h || cap < 0 || (cap > 0 && !out) || cus < 0) return fail(MZ_ERR_INVALID_ARGUMENT, "bad arguments");
+    if (B <= 0 || H < 8 || W < 8) return fail(MZ_ERR_INVALID_ARGUMENT, "need B >= 1 and H, W >= 8 (got %d, %d, %d)", B, H, W);
+    const Knobs& k = h->ctx.knobs;
+    const int dtype = h->dims.dtype;
+    Plan p;
+    make_plan(h->dims, B, H, W, p);
+    const auto steps = make_schedule(h->model, h->dims, p, k, want_qa != 0, h->cfg.upscale_ratio, 0);
+    static const int role_op[] = {-1, 0, 6, 4, 2, 3};  // StepRole -> mz_debug_select's op
+    for (size_t i = 0; i < steps.size() && i < (size_t)cap; ++i) {
+        const Step<ConvW>& st = steps[i];
+        mz_debug_step& d = out[i];
+        d.kind = st.kind;
+        d.op = st.kind == ST_MIX ? 7 : role_op[st.role];
+        d.cin = st.cin; d.cout = st.cout;
+        d.B = st.B; d.H = st.H; d.W = st.W; d.Hout = st.Hout; d.Wout = st.Wout;
+        d.fused = st.fused;
+        const BufRef* bufs[3] = {&st.in, &st.in1, &st.out};
+        for (int j = 0; j < 3; ++j) {
+            d.off[j] = bufs[j]->where == BUF_WS ? (long long)bufs[j]->off : bufs[j]->where;  // the external codes are negative
+            d.bytes[j] = bufs[j]->bytes;
+        }
+        d.kernel = nullptr;
+        if (st.kind == ST_MIX) d.kernel = kernel_name(choose_mix(k, dtype, *st.layer, st.B, st.H, st.W, cus));
+        if (st.kind == ST_CONV3) d.kernel = kernel_name(choose_conv3(k, dtype, step_call(k, st, nullptr, nullptr, nullptr), cus));
     }
-    macs += 9.0 * h->dims.ch[3] * h->cfg.num_deg_features * hs[3] * ws[3];
-    double hh = H, ww = W;
-    for (int i = 0; i < h->dims.nhead; ++i) {
-        const double cout = (i == h->dims.nhead - 1) ? 3 : h->dims.ch[0];
-        macs += blk(h->dims.ch[0]) * hh * ww + 9.0 * h->dims.ch[0] * 4.0 * cout * hh * ww;
-        hh *= 2; ww *= 2;
-    }
-    return 2.0 * macs;
+    return (int)steps.size();
 }

@@ -1,8 +1,7 @@
-// Model runtime of libmewzoom_hip.so: configuration checks, weight registry + packing, the layer schedule of the MewZoom forward pass,
-// the profiler, and their part of the C ABI (include/mewzoom_hip.h).  Planning and kernel selection: mz_plan.h, mz_select.h; launching a
-// layer: mz_runner.h; the mz_op_* entries: mz_ops.cpp; metrics, resize, degradations: mz_image.cpp; introspection: mz_debug.cpp.
-//
-// The schedule follows the reference's MewZoom.forward (src/ultrazoom/model.py:149-164) and its sub-modules; each step cites the lines it replaces.
+// Model runtime of libmewzoom_hip.so: configuration checks, weight registry + packing, running the schedule of the MewZoom forward pass,
+// the profiler, and their part of the C ABI (include/mewzoom_hip.h).  Planning, kernel selection and the schedule: mz_plan.h, mz_select.h,
+// mz_schedule.h; launching a layer: mz_runner.h; the mz_op_* entries: mz_ops.cpp; metrics, resize, degradations: mz_image.cpp;
+// introspection: mz_debug.cpp.
 #include <cstdio>
 
 #include "mz_host.h"
@@ -32,14 +31,11 @@ static void add_conv_slot(mz_handle* h, const std::string& name, ConvW& c, ConvW
 }
 static void add_alpha_slot(mz_handle* h, const std::string& name, float* alpha) { add_slot(h, name, SK_ALPHA, {}).alpha = alpha; }
 
-static void add_block(mz_handle* h, std::vector<std::unique_ptr<BlockW>>& blocks, const std::string& prefix, int c) {
-    blocks.emplace_back(new BlockW());
-    BlockW* b = blocks.back().get();
-    plan_block(*b, h->dims.dtype, c, h->cfg.hidden_ratio * c);
-    add_conv_slot(h, prefix + ".convnet.conv1.weight", b->conv1);
-    add_conv_slot(h, prefix + ".convnet.conv2.weight", b->conv2);
-    add_alpha_slot(h, prefix + ".skip.alpha", &b->alpha);  // a module's own parameters precede its children's
-    add_conv_slot(h, prefix + ".skip.conv.weight", b->mix, b->fused ? &b->mixf : nullptr);
+static void add_block_slots(mz_handle* h, BlockW& b, const std::string& prefix) {
+    add_conv_slot(h, prefix + ".convnet.conv1.weight", b.conv1);
+    add_conv_slot(h, prefix + ".convnet.conv2.weight", b.conv2);
+    add_alpha_slot(h, prefix + ".skip.alpha", &b.alpha);  // a module's own parameters precede its children's
+    add_conv_slot(h, prefix + ".skip.conv.weight", b.mix, b.fused ? &b.mixf : nullptr);
 }
 
 static int validate(const mz_config& c) {
@@ -71,49 +67,31 @@ extern "C" int mz_create(const mz_config* cfg, int dtype, mz_handle** out) {
     h->cfg = *cfg;
     const int ch[4] = {cfg->primary_channels, cfg->secondary_channels, cfg->tertiary_channels, cfg->quaternary_channels};
     const int ly[4] = {cfg->primary_layers, cfg->secondary_layers, cfg->tertiary_layers, cfg->quaternary_layers};
-    for (int i = 0; i < 4; ++i) {
-        h->enc[i] = (ly[i] + 1) / 2;  // ceil, model.py:277-288
-        h->dec[i] = ly[i] / 2;        // floor, model.py:290-300
-    }
     const int nhead = cfg->upscale_ratio == 2 ? 1 : (cfg->upscale_ratio == 4 ? 2 : 3);  // model.py:945
     h->dims = {dtype, {ch[0], ch[1], ch[2], ch[3]}, cfg->hidden_ratio, nhead, cfg->num_deg_features};
+    Model<ConvW>& m = h->model;
+    plan_model(m, h->dims, ly);
 
-    // Registry in the reference's state_dict order.
+    // Registry: the planned layers by their names, in the reference's state_dict order.
+    const auto n = [](int i) { return std::to_string(i); };
     h->slots.reserve(1024);
     add_slot(h, "stem.conv.weight", SK_STEM_W, {ch[0], 3, 1, 1});
     add_slot(h, "stem.conv.bias", SK_STEM_B, {ch[0]});
-    for (int s = 0; s < 4; ++s) {
-        for (int i = 0; i < h->enc[s]; ++i) add_block(h, h->enc_blocks[s], "unet.encoder.stage" + std::to_string(s + 1) + "." + std::to_string(i), ch[s]);
-    }
-    for (int s = 0; s < 3; ++s) {  // model.py:388-390, 857-863
-        plan_conv(h->crush[s], dtype, MODE_GEMM1, ch[s + 1], ch[s], 2, 2, OUT_PLAIN, SRC_CRUSH, 0, 0);
-        add_conv_slot(h, "unet.encoder.downsample" + std::to_string(s + 1) + ".conv.weight", h->crush[s]);
-    }
-    plan_conv(h->qa_conv, dtype, MODE_CONV3, cfg->num_deg_features, ch[3], 3, 3, OUT_PLAIN, SRC_PLAIN, 0, 0);  // :1010
-    add_conv_slot(h, "unet.encoder.qa_head.conv.weight", h->qa_conv);
+    for (int s = 0; s < 4; ++s)
+        for (int i = 0; i < m.enc[s]; ++i) add_block_slots(h, m.enc_blocks[s][i], "unet.encoder.stage" + n(s + 1) + "." + n(i));
+    for (int s = 0; s < 3; ++s) add_conv_slot(h, "unet.encoder.downsample" + n(s + 1) + ".conv.weight", m.crush[s]);
+    add_conv_slot(h, "unet.encoder.qa_head.conv.weight", m.qa_conv);
     add_slot(h, "unet.encoder.qa_head.conv.bias", SK_QA_B, {cfg->num_deg_features});
-    for (int d = 0; d < 4; ++d) {  // decoder stage1 = coarsest level (model.py:290-300)
-        const int lvl = 3 - d;
-        for (int i = 0; i < h->dec[lvl]; ++i) add_block(h, h->dec_blocks[d], "unet.decoder.stage" + std::to_string(d + 1) + "." + std::to_string(i), ch[lvl]);
-    }
+    for (int d = 0; d < 4; ++d)  // decoder stage1 = coarsest level (model.py:290-300)
+        for (int i = 0; i < m.dec[3 - d]; ++i) add_block_slots(h, m.dec_blocks[d][i], "unet.decoder.stage" + n(d + 1) + "." + n(i));
+    for (int d = 0; d < 3; ++d) add_conv_slot(h, "unet.decoder.upsample" + n(d + 1) + ".conv.weight", m.up[d]);
     for (int d = 0; d < 3; ++d) {
-        const int cin = ch[3 - d], cout = ch[2 - d];
-        plan_conv(h->up[d], dtype, MODE_CONV3, 4 * cout, cin, 3, 3, OUT_D2S, SRC_PLAIN, 0, 0);  // model.py:569-571, 900-911
-        add_conv_slot(h, "unet.decoder.upsample" + std::to_string(d + 1) + ".conv.weight", h->up[d]);
-    }
-    for (int d = 0; d < 3; ++d) {
-        const int cout = ch[2 - d];
-        plan_conv(h->skipmix[d], dtype, MODE_GEMM1, cout, 2 * cout, 1, 1, OUT_PLAIN, SRC_CONCAT, cout, cout);  // model.py:573-575
-        add_alpha_slot(h, "unet.decoder.skip" + std::to_string(d + 1) + ".alpha", &h->skip_alpha[d]);
-        add_conv_slot(h, "unet.decoder.skip" + std::to_string(d + 1) + ".conv.weight", h->skipmix[d]);
+        add_alpha_slot(h, "unet.decoder.skip" + n(d + 1) + ".alpha", &m.skip_alpha[d]);
+        add_conv_slot(h, "unet.decoder.skip" + n(d + 1) + ".conv.weight", m.skipmix[d]);
     }
     for (int i = 0; i < nhead; ++i) {  // model.py:945-954, 981-983
-        add_block(h, h->head_blocks, "head.layers." + std::to_string(i) + ".refiner", ch[0]);
-        const bool last = i == nhead - 1;
-        const int cout = last ? 3 : ch[0];
-        h->head_up.emplace_back(new ConvW());
-        plan_conv(*h->head_up.back(), dtype, MODE_CONV3, 4 * cout, ch[0], 3, 3, last ? OUT_FINAL : OUT_D2S, SRC_PLAIN, 0, 0);
-        add_conv_slot(h, "head.layers." + std::to_string(i) + ".upscale.conv.weight", *h->head_up.back());
+        add_block_slots(h, m.head_blocks[i], "head.layers." + n(i) + ".refiner");
+        add_conv_slot(h, "head.layers." + n(i) + ".upscale.conv.weight", m.head_up[i]);
     }
     *out = h;
     return MZ_OK;
@@ -205,6 +183,7 @@ extern "C" int mz_workspace_bytes(const mz_handle* h, int B, int H, int W, int m
 // ------------------------------------------------------------------------------------------------
 // forward
 // ------------------------------------------------------------------------------------------------
+// One micro-batch: the steps of make_schedule (mz_schedule.h), their operands resolved against the workspace and the caller's tensors.
 // views: x and out_sr are the first elements of image views (out_sr: of the window) instead of dense NCHW tensors
 static int forward_micro(mz_handle* h, const char* x, char* out_sr, float* out_qa, int nb, int H, int W, int clamp,
                          char* ws, hipStream_t s, int io_u8, const ImageViews* views) {
@@ -212,102 +191,42 @@ static int forward_micro(mz_handle* h, const char* x, char* out_sr, float* out_q
     make_plan(h->dims, nb, H, W, p);
     Runner run{h->ctx, s, h->dims.dtype};
     run.io_u8 = io_u8;
-    const int r = h->cfg.upscale_ratio;
-
-    auto block = [&](const BlockW& b, const void* xin, void* hid, void* z, void* yout, int hh, int ww) {
-        // EncoderBlock / DecoderBlock (model.py:507-511): conv1 -> SiLU -> conv2 -> adaptive mix with the input
-        run.conv3(conv1_call(b.conv1, xin, hid, nb, hh, ww));
-        // conv2 + AdaptiveResidualMix in one launch (all output channels live in one workgroup), or in two
-        Conv3Call c2 = conv2_call(run.knobs, b, hid, xin, nb, hh, ww);
-        c2.out = c2.mixf ? yout : z;
-        run.conv3(c2);
-        if (!c2.mixf) run.mix(b.mix, b.alpha, xin, z, yout, nb, hh, ww);
+    const int dtype = h->dims.dtype;
+    auto at = [&](const BufRef& b) -> char* {
+        switch (b.where) {
+            case BUF_WS: return ws + b.off;
+            case BUF_IMAGE_IN: return const_cast<char*>(x);
+            case BUF_IMAGE_OUT: return out_sr;
+            case BUF_QA_OUT: return (char*)out_qa;
+        }
+        return nullptr;
     };
-
-    // stem (model.py:158): NCHW image -> NHWC features
-    char* cur = ws + p.R[0][0];
-    if (int rc = hip_rc(launch_stem(h->dims.dtype, x, (const float*)h->stem_w4.p, cur, nb, H, W, pad16(h->dims.ch[0]), s, io_u8, views ? views->in : nullptr), "stem launch"))
-        return rc;
-
-    // encoder (model.py:461-484)
-    char* feat[4];
-    int feat_slot[4];
-    for (int l = 0; l < 4; ++l) {
-        int slot = 0;
-        if (l > 0) {
-            cur = ws + p.R[l][0];
-            run.crush(h->crush[l - 1], feat[l - 1], cur, nb, p.hs[l - 1], p.ws[l - 1]);
-        }
-        for (auto& b : h->enc_blocks[l]) {
-            char* nxt = ws + p.R[l][slot ^ 1];
-            block(*b, cur, ws + p.HID[l], ws + p.Z[l], nxt, p.hs[l], p.ws[l]);
-            cur = nxt;
-            slot ^= 1;
-        }
-        feat[l] = cur;
-        feat_slot[l] = slot;
-    }
-
-    // quality head (model.py:482, 1026-1032); upscale() discards it (model.py:175)
-    if (out_qa) {
-        const int F = h->cfg.num_deg_features;
-        run.conv3(plain_call(h->qa_conv, feat[3], ws + p.QA, nb, p.hs[3], p.ws[3]));
-        if (run.rc) return run.rc;
-        if (int rc = hip_rc(launch_qa_reduce(h->dims.dtype, ws + p.QA, (const float*)h->qa_bias.p, out_qa, nb, p.hs[3] * p.ws[3], pad16(F), F, s), "qa reduce launch"))
-            return rc;
-    }
-
-    // decoder (model.py:691-724)
-    cur = feat[3];
-    int slot = feat_slot[3];
-    for (int d = 0; d < 4; ++d) {
-        const int l = 3 - d;
-        if (d > 0) {
-            // SubpixelConv2d (model.py:926-930) + crop_feature_maps zero pad (model.py:650-689) + skip mix (:701)
-            const ConvW& up = h->up[d - 1];
-            char* u = ws + p.U[l];
-            run.conv3(d2s_call(up, cur, u, nb, p.hs[l + 1], p.ws[l + 1], p.hs[l], p.ws[l]));
-            if (run.rc) return run.rc;
-            if (int rc = hip_rc(launch_zero_border(h->dims.dtype, u, nb, p.hs[l], p.ws[l], up.cq_p, 2 * p.hs[l + 1], 2 * p.ws[l + 1], s), "zero border launch"))
-                return rc;
-            // pick a level-l buffer that is not the saved encoder feature
-            slot = (feat_slot[l] + 1) % 3;
-            char* dst = ws + p.R[l][slot];
-            run.mix(h->skipmix[d - 1], h->skip_alpha[d - 1], feat[l], u, dst, nb, p.hs[l], p.ws[l]);
-            cur = dst;
-        }
-        for (auto& b : h->dec_blocks[d]) {
-            int nslot = (slot + 1) % 3;
-            if (d > 0 && nslot == feat_slot[l]) nslot = (nslot + 1) % 3;  // (the encoder feature is dead after the skip mix, but keep it simple)
-            char* nxt = ws + p.R[l][nslot];
-            block(*b, cur, ws + p.HID[l], ws + p.Z[l], nxt, p.hs[l], p.ws[l]);
-            cur = nxt;
-            slot = nslot;
-        }
-    }
-
-    // head (model.py:968-972, 997-1001) + bicubic skip + residual add + clamp (model.py:156,162,177)
-    int hh = H, ww = W;
-    for (int i = 0; i < h->dims.nhead; ++i) {
-        char *hid, *z, *y;
-        if (i == 0) {
-            hid = ws + p.HID[0]; z = ws + p.Z[0];
-            int nslot = (slot + 1) % 3;
-            y = ws + p.R[0][nslot];
-        } else {
-            hid = ws + p.HHID[i]; z = ws + p.HZ[i]; y = ws + p.HR[i][1];
-        }
-        block(*h->head_blocks[i], cur, hid, z, y, hh, ww);
-        const bool last = i == h->dims.nhead - 1;
-        if (last) {
-            Conv3Call head = head_call(*h->head_up[i], y, out_sr, nb, hh, ww);
-            head.img = x; head.R = r; head.clamp = clamp; head.views = views;
-            run.conv3(head);
-        } else {
-            char* nxt = ws + p.HR[i + 1][0];
-            run.conv3(d2s_call(*h->head_up[i], y, nxt, nb, hh, ww, 2 * hh, 2 * ww));
-            cur = nxt;
-            hh *= 2; ww *= 2;
+    for (const Step<ConvW>& st : make_schedule(h->model, h->dims, p, run.knobs, out_qa != nullptr, h->cfg.upscale_ratio, clamp)) {
+        const char *in = at(st.in), *in1 = at(st.in1);
+        char* out = at(st.out);
+        switch (st.kind) {
+            case ST_CONV3: {
+                Conv3Call c = step_call(run.knobs, st, in, in1, out);
+                if (st.role == ROLE_HEAD) c.views = views;
+                run.conv3(c);
+                break;
+            }
+            case ST_MIX: run.mix(*st.layer, st.alpha, in, in1, out, st.B, st.H, st.W); break;
+            case ST_CRUSH: run.crush(*st.layer, in, out, st.B, st.H, st.W); break;
+            case ST_STEM:
+                if (int rc = hip_rc(launch_stem(dtype, in, (const float*)h->stem_w4.p, out, st.B, st.H, st.W, pad16(st.cout), s, io_u8, views ? views->in : nullptr), "stem launch"))
+                    return rc;
+                break;
+            case ST_ZERO_BORDER:
+                if (run.rc) return run.rc;
+                if (int rc = hip_rc(launch_zero_border(dtype, out, st.B, st.Hout, st.Wout, st.layer->cq_p, 2 * st.H, 2 * st.W, s), "zero border launch"))
+                    return rc;
+                break;
+            case ST_QA_REDUCE:
+                if (run.rc) return run.rc;
+                if (int rc = hip_rc(launch_qa_reduce(dtype, in, (const float*)h->qa_bias.p, (float*)out, st.B, st.H * st.W, pad16(st.cout), st.cout, s), "qa reduce launch"))
+                    return rc;
+                break;
         }
     }
     return run.rc;

@@ -1,12 +1,12 @@
-// The model handle of libmewzoom_hip.so (mz_host.cpp; mz_debug.cpp reads its dimensions): the layers with their weights, the
-// registry of parameters, and what its launches share.
+// The model handle of libmewzoom_hip.so (mz_host.cpp; mz_debug.cpp reads its dimensions and its schedule): the layers with their
+// weights, the registry of parameters, and what its launches share.
 #pragma once
-#include <memory>
 #include <string>
 #include <unordered_map>
 #include <vector>
 
 #include "mz_runner.h"
+#include "mz_schedule.h"
 
 enum SlotKind { SK_CONV, SK_ALPHA, SK_STEM_W, SK_STEM_B, SK_QA_B };
 // One parameter of the reference's state_dict: its name and shape (mz_weight_info), where its value goes, whether it has been set
@@ -24,13 +24,7 @@ struct Slot {
 struct mz_handle {
     mz_config cfg;
     mz::ModelDims dims;  // dtype, channels per level, hidden ratio, head levels, quality features
-    int enc[4], dec[4];  // blocks per level
-    // weights
-    std::vector<std::unique_ptr<mz::BlockW>> enc_blocks[4], dec_blocks[4], head_blocks;
-    mz::ConvW crush[3], up[3], skipmix[3];
-    float skip_alpha[3] = {0, 0, 0};
-    std::vector<std::unique_ptr<mz::ConvW>> head_up;
-    mz::ConvW qa_conv;
+    mz::Model<mz::ConvW> model;  // every layer, planned, with its weights
     mz::DevBuf stem_w4;  // float [cp0][4]
     mz::DevBuf qa_bias;  // float [F]
     std::vector<Slot> slots;

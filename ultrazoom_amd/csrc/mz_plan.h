@@ -5,6 +5,7 @@
 #include <stdlib.h>
 
 #include <algorithm>
+#include <vector>
 
 #include "mz_geo.h"
 
@@ -168,9 +169,52 @@ template <class Layer> void plan_block(Block<Layer>& b, int dtype, int c, int hi
     if (b.fused) plan_mixf(b.mixf, dtype, b.conv2);
 }
 
-// ---- workspace plan -----------------------------------------------------------------------------
-// what of a model sizes its workspace
+// ---- the model ----------------------------------------------------------------------------------
+// what of a model sizes its layers and its workspace
 struct ModelDims { int dtype, ch[4], hidden_ratio, nhead, num_deg_features; };
+
+// Every layer of a MewZoom: Layer as for Block.  Level l = 0..3 has ch[l] channels at 1 / 2^l of the image; decoder stage d runs
+// level 3 - d (the reference's decoder stage1 is the coarsest level, model.py:290-300).
+template <class Layer> struct Model {
+    int enc[4], dec[4];  // blocks per level
+    std::vector<Block<Layer>> enc_blocks[4], dec_blocks[4], head_blocks;  // dec_blocks[d]; one head block per head level
+    Layer crush[3], up[3], skipmix[3];  // crush[l]: level l -> l + 1; up[d - 1], skipmix[d - 1]: into decoder stage d
+    float skip_alpha[3] = {0, 0, 0};
+    std::vector<Layer> head_up;
+    Layer qa_conv;
+};
+
+// Plans every layer of the model; layers[l] blocks on level l, the encoder's half rounded up (model.py:277-300).  The vectors get
+// their final size here: a block or a layer stays where it is (mz_create's registry points at them).
+template <class Layer> void plan_model(Model<Layer>& m, const ModelDims& d, const int layers[4]) {
+    const int* ch = d.ch;
+    auto plan_blocks = [&](std::vector<Block<Layer>>& blocks, int n, int c) {
+        blocks = std::vector<Block<Layer>>(n);
+        for (auto& b : blocks) plan_block(b, d.dtype, c, d.hidden_ratio * c);
+    };
+    for (int l = 0; l < 4; ++l) {
+        m.enc[l] = (layers[l] + 1) / 2;  // ceil, model.py:277-288
+        m.dec[l] = layers[l] / 2;        // floor, model.py:290-300
+        plan_blocks(m.enc_blocks[l], m.enc[l], ch[l]);
+        plan_blocks(m.dec_blocks[3 - l], m.dec[l], ch[l]);
+    }
+    for (int l = 0; l < 3; ++l)  // model.py:388-390, 857-863
+        plan_conv(m.crush[l], d.dtype, MODE_GEMM1, ch[l + 1], ch[l], 2, 2, OUT_PLAIN, SRC_CRUSH, 0, 0);
+    plan_conv(m.qa_conv, d.dtype, MODE_CONV3, d.num_deg_features, ch[3], 3, 3, OUT_PLAIN, SRC_PLAIN, 0, 0);  // model.py:1010
+    for (int i = 0; i < 3; ++i) {
+        const int cin = ch[3 - i], cout = ch[2 - i];
+        plan_conv(m.up[i], d.dtype, MODE_CONV3, 4 * cout, cin, 3, 3, OUT_D2S, SRC_PLAIN, 0, 0);              // model.py:569-571, 900-911
+        plan_conv(m.skipmix[i], d.dtype, MODE_GEMM1, cout, 2 * cout, 1, 1, OUT_PLAIN, SRC_CONCAT, cout, cout);  // model.py:573-575
+    }
+    plan_blocks(m.head_blocks, d.nhead, ch[0]);  // model.py:945-954, 981-983
+    m.head_up = std::vector<Layer>(d.nhead);
+    for (int i = 0; i < d.nhead; ++i) {
+        const bool last = i == d.nhead - 1;
+        plan_conv(m.head_up[i], d.dtype, MODE_CONV3, 4 * (last ? 3 : ch[0]), ch[0], 3, 3, last ? OUT_FINAL : OUT_D2S, SRC_PLAIN, 0, 0);
+    }
+}
+
+// ---- workspace plan -----------------------------------------------------------------------------
 struct Plan {
     int nb;                // images per micro-batch
     int hs[4], ws[4];      // level sizes
