@@ -99,7 +99,17 @@ int mz_weights_complete(const mz_handle* h);
  * written during that call; it WRITES only its outputs (of a view: the elements of the window) and its workspace, never an input.
  * The workspace needs no initialisation and carries nothing from one call to the next: whatever it holds, NaN patterns included,
  * the results have the same bits.  mz_metrics writes the `out` slots of the metrics `which` selects and leaves the others alone.
- * tests/test_poison_ops_gpu.py, tests/test_poison_forward_gpu.py and tests/test_metrics_gpu.py hold every entry to this. */
+ * tests/test_poison_ops_gpu.py, tests/test_poison_forward_gpu.py and tests/test_metrics_gpu.py hold every entry to this.
+ *
+ * Number range (the convolution, mix, stem and head kernels, in every storage type): subnormals of the storage type are operands and
+ * results like any other value -- nothing is flushed on the way in, in the matrix unit's operands, or at the store.  Accumulation is
+ * f32, f32 subnormals included.  A result is rounded ONCE, to nearest even, into the subnormal range where it lies there and to
+ * +-inf from the overflow tie upward (fp16: 65520).  One thing holds instead of the plain formula inside SiLU and the mix's gate:
+ * their sigmoid is a hardware reciprocal (v_rcp_f32) whose result is ZERO where it would be an f32 subnormal, so for sigmoid(t) <
+ * 2^-126, t < -87.34, SiLU(t) is -0 (not t sigmoid(t), about -88 * 2^-126) and the gate's weight is 0 (the blend returns x; invisible
+ * beside x itself).  Not promised beyond that: other f32 intermediates below 2^-126 inside SiLU and the gate may flush, too; SiLU
+ * and the blend are accurate to half an ulp of the storage type plus 2^-16 relative, not exact.  Non-finite inputs are out of scope.
+ * tests/test_range_gpu.py holds every kernel family to this (data and bounds: tests/range_util.py, tests/test_range_cpu.py). */
 int mz_workspace_bytes(const mz_handle* h, int B, int H, int W, int max_images_in_flight, size_t* bytes);
 
 /* x        [B,3,H,W]      input, handle dtype
