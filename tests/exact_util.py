@@ -2,8 +2,9 @@
 
 Integer-valued activations and weights whose partial sums stay below 2^24 are added without error in fp32 in ANY order, so a kernel's
 output must equal the float64 result rounded ONCE to the storage type, bit for bit, whatever its tile walk or K order.  This module
-builds, for every row of the table below, the inputs, the float64 reference (torch.nn.functional on float64, the crop / zero border and
-the pixel shuffle from oracle.mewzoom_oracle), the expected storage-type tensor (round_once) and the figures the CPU test holds every
+draws, for every row of the table below, the inputs; finish() adds what follows from the entry's one statement in tests/op_ref.py: the
+float64 reference (torch.nn.functional on float64, the crop / zero border and the pixel shuffle from oracle.mewzoom_oracle), and with
+it the expected storage-type tensor (round_once) and the figures the CPU test holds every
 row to (absolute-product sums, maxima, the census of roundings and ties, the excluded share).
 
 Where an operator contains a transcendental (the sigmoid of the mix's gate; SiLU in the one family that exists only with SiLU), the
@@ -22,8 +23,8 @@ import torch
 import torch.nn.functional as F
 
 from gpu_util import DTYPES
+import op_ref
 from op_cases import CASES, TINY_CASES, fields
-from oracle import mewzoom_oracle as oracle
 
 SAT_HI, SAT_LO = 32.0, -100.0
 MAX_EXCLUDED = 0.02
@@ -194,10 +195,6 @@ class Exact:
         return self.y64 if self.keep is None else self.y64[self.keep]
 
 
-def _abs_sum(x, w, **kw):
-    return F.conv2d(x.abs(), w.abs(), **kw).max().item()
-
-
 def _saturate(ex: Exact, t64, one64, zero64, soft64):
     """t: the transcendental's argument.  one64 / zero64: the result where the sigmoid is exactly 1 / exactly 0."""
     hi, lo = t64 >= SAT_HI, t64 <= SAT_LO
@@ -207,80 +204,68 @@ def _saturate(ex: Exact, t64, one64, zero64, soft64):
     ex.branches = (hi.double().mean().item(), lo.double().mean().item())
 
 
-def _build(entry, args, dt, silu) -> Exact:
-    ex = Exact()
-    d = lambda t: t.double()
-    a = fields(entry, args)
-    B, H, W = a.B, a.H, a.W
-    big = dt == "f16" or bool(silu)
-    if entry in ("conv", "film", "d2s", "crush"):
-        cin, cout = a.cin, a.cout
-        k = 2 if entry == "crush" else 3
-        nterms = taps_inside(H, W, k) * cin * (4 if entry == "film" else 1)  # film: |gamma| <= 2 doubles the spread, as four times the terms would
-        full = k * k * cin * (4 if entry == "film" else 1)
-        x, w = ints((B, cin, H, W), conv_ax(nterms, dt, big, full), 101), ints((cout, cin, k, k), AW, 102)
-        ex.inputs = {"in0": x, "w": w}
-        kw = {"stride": 2} if entry == "crush" else {"padding": 1}
-        ex.sums["conv"] = _abs_sum(d(x), d(w), **kw)
-        if entry == "d2s":
-            ex.C, ex.y64 = cout // 4, oracle.fit_to(oracle.subpixel_conv(d(x), d(w)), (a.Hout, a.Wout))
-        elif entry == "film":
-            gamma, beta = choice((B, cout), [-1.0, 0.5, 1.0, 2.0], 103), ints((B, cout), 8, 104)
-            ex.inputs.update(gamma=gamma, beta=beta)
-            ex.C, ex.y64 = cout, oracle.film_conv(d(x), d(w), d(gamma), d(beta), False)
-            ex.sums["film"] = (F.conv2d(d(x).abs(), d(w).abs(), padding=1) * d(gamma).abs()[:, :, None, None] + d(beta).abs()[:, :, None, None]).max().item()
-        else:
-            ex.C, ex.y64 = cout, F.conv2d(d(x), d(w), **kw)
-            if silu:  # t >= SAT_HI: t * 1; t <= SAT_LO: t * 0
-                y = ex.y64
-                _saturate(ex, y, y, torch.zeros_like(y), F.silu(y))
-    elif entry == "stem":
-        c = a.C
-        x = ints((B, 3, H, W), INT_MAX[dt], 105).abs()
-        w, b = choice((c, 3, 1, 1), [-2.0, -1.0, -0.5, 0.5, 1.0, 2.0], 106), ints((c,), 8, 107)
-        ex.inputs = {"x": x, "w": w, "b": b}
-        ex.C, ex.y64 = c, F.conv2d(d(x), d(w), d(b))
-        ex.sums["stem"] = F.conv2d(d(x), d(w).abs(), d(b).abs()).max().item()
-    elif entry == "final":
-        cin, R = a.cin, a.R
-        feat, w = ints((B, cin, H, W), conv_ax(taps_inside(H, W) * cin, dt, big, 9 * cin), 108), ints((12, cin, 3, 3), AW, 109)
-        img = torch.zeros(B, 3, 2 * H // R, 2 * W // R)  # the bicubic term is exactly zero
-        ex.inputs = {"feat": feat, "img": img, "w": w}
-        ex.C, ex.y64 = None, oracle.bicubic_upsample(d(img), R) + oracle.subpixel_conv(d(feat), d(w))
-        ex.sums["conv"] = _abs_sum(d(feat), d(w), padding=1)
-    elif entry in ("mix", "conv_mix"):
-        ax = INT_MAX[dt]  # x: every integer the type holds
-        if entry == "mix":
-            c = a.C
-            # z: multiples of 4, so that (x + z) / 2 = x / 2 + 2 zi needs rounding (exact, tie or neither by x mod 4) in both 16-bit types
-            az = 255 if dt == "bf16" else 511
-            x, z = ints((B, c, H, W), ax, 110), ints((B, c, H, W), az, 111, 4.0)
-            ex.inputs = {"in0": x, "in1": z}
-            z64, wname, mean_z = d(z), "w", 2.0 * az
-        else:
-            cin, c = a.cin, a.cout
-            nterms = taps_inside(H, W) * cin
-            hid, x, w2 = ints((B, cin, H, W), conv_ax(nterms, dt, big, 9 * cin), 112), ints((B, c, H, W), ax, 113), ints((c, cin, 3, 3), AW, 114)
-            ex.inputs = {"hid": hid, "x": x, "w2": w2}
-            ex.sums["conv"] = _abs_sum(d(hid), d(w2), padding=1)
-            ex.z64_unrounded = F.conv2d(d(hid), d(w2), padding=1)
-            # z is rounded to the storage type BEFORE the gate GEMM and the blend, as the unfused path stores it
-            z64, wname = round_once(ex.z64_unrounded, dt).double(), "wmix"
-            mean_z = 0.8 * math.sqrt(nterms) * conv_ax(nterms, dt, big, 9 * cin) * AW / 3.0  # E|z| of a normal variable
-        wmix = ints((c, 2 * c, 1, 1), gate_aw(c, ax / 2.0, mean_z), 115, float(GATE_SCALE))
-        ex.inputs[wname] = wmix
-        ex.C = c
-        xz = torch.cat([d(x), z64], dim=1)
-        gate = F.conv2d(xz, d(wmix))
-        ex.sums["gate"] = _abs_sum(xz, d(wmix))
-        ex.sums["blend"] = (d(x).abs() + z64.abs()).max().item()
+def finish(ex: Exact, entry, args, dt, silu=0, gate=None) -> Exact:
+    """The shared end of every builder, on the drawn ex.inputs: C, the float64 reference, the sums of absolute products, the saturation
+    of a transcendental and the expected storage-type tensor, all from the entry's statement in tests/op_ref.py.  gate(ex, mix): the
+    gate that classifies the elements of a mix where that is not the mix's own; it then states the mix's sums itself."""
+    t = {k: v.double() for k, v in ex.inputs.items()}
+    op_ref.check_shapes(entry, args, t)
+    ex.C, shape = op_ref.output(entry, args)
+    ex.sums.update(op_ref.abs_sums(entry, t))
+    if entry in op_ref.MIXES:
+        m = op_ref.Mix(entry, t, lambda z: round_once(z, dt).double())
+        if entry == "conv_mix":
+            ex.z64_unrounded = m.z_raw
+        ex.z64 = m.z
+        if gate is None:
+            ex.sums.update(m.abs_sums())
         # alpha = 0: sigmoid(alpha) = 1/2 and the host's 1 + e^-alpha = 2 are exact
-        _saturate(ex, gate, (d(x) + z64) / 2, d(x), d(x) + 0.5 * torch.sigmoid(gate) * (z64 - d(x)))
-        ex.z64 = z64
+        _saturate(ex, m.gate if gate is None else gate(ex, m), (m.x + m.z) / 2, m.x, m.x + 0.5 * torch.sigmoid(m.gate) * (m.z - m.x))
     else:
-        raise ValueError(entry)
+        y = op_ref.reference(entry, args, t, silu=False)
+        if silu:  # t >= SAT_HI: t * 1; t <= SAT_LO: t * 0
+            _saturate(ex, y, y, torch.zeros_like(y), F.silu(y))
+        else:
+            ex.y64 = y
+    assert tuple(ex.y64.shape) == shape, (entry, args)
     ex.want = round_once(ex.y64, dt)
     return ex
+
+
+def _build(entry, args, dt, silu) -> Exact:
+    """The recipe of the exact rows: which numbers each of the entry's inputs (op_ref.shapes) holds."""
+    ex = Exact()
+    a, s = fields(entry, args), op_ref.shapes(entry, args)
+    big = dt == "f16" or bool(silu)
+    if entry in ("conv", "film", "d2s", "crush"):
+        k = s["w"][-1]
+        nterms = taps_inside(a.H, a.W, k) * a.cin * (4 if entry == "film" else 1)  # film: |gamma| <= 2 doubles the spread, as four times the terms would
+        full = k * k * a.cin * (4 if entry == "film" else 1)
+        ex.inputs = {"in0": ints(s["in0"], conv_ax(nterms, dt, big, full), 101), "w": ints(s["w"], AW, 102)}
+        if entry == "film":
+            ex.inputs.update(gamma=choice(s["gamma"], [-1.0, 0.5, 1.0, 2.0], 103), beta=ints(s["beta"], 8, 104))
+    elif entry == "stem":
+        ex.inputs = {"x": ints(s["x"], INT_MAX[dt], 105).abs(), "w": choice(s["w"], [-2.0, -1.0, -0.5, 0.5, 1.0, 2.0], 106), "b": ints(s["b"], 8, 107)}
+    elif entry == "final":
+        ex.inputs = {"feat": ints(s["feat"], conv_ax(taps_inside(a.H, a.W) * a.cin, dt, big, 9 * a.cin), 108),
+                     "img": torch.zeros(s["img"]),  # the bicubic term is exactly zero
+                     "w": ints(s["w"], AW, 109)}
+    elif entry == "mix":
+        ax = INT_MAX[dt]  # x: every integer the type holds
+        # z: multiples of 4, so that (x + z) / 2 = x / 2 + 2 zi needs rounding (exact, tie or neither by x mod 4) in both 16-bit types
+        az = 255 if dt == "bf16" else 511
+        ex.inputs = {"in0": ints(s["in0"], ax, 110), "in1": ints(s["in1"], az, 111, 4.0),
+                     "w": ints(s["w"], gate_aw(a.C, ax / 2.0, 2.0 * az), 115, float(GATE_SCALE))}
+    elif entry == "conv_mix":
+        ax = INT_MAX[dt]
+        nterms = taps_inside(a.H, a.W) * a.cin
+        ah = conv_ax(nterms, dt, big, 9 * a.cin)
+        mean_z = 0.8 * math.sqrt(nterms) * ah * AW / 3.0  # E|z| of a normal variable
+        ex.inputs = {"hid": ints(s["hid"], ah, 112), "x": ints(s["x"], ax, 113), "w2": ints(s["w2"], AW, 114),
+                     "wmix": ints(s["wmix"], gate_aw(a.cout, ax / 2.0, mean_z), 115, float(GATE_SCALE))}
+    else:
+        raise ValueError(entry)
+    return finish(ex, entry, args, dt, silu)
 
 
 @functools.lru_cache(maxsize=None)

@@ -1,6 +1,7 @@
 """The family table of the operator tests: every operator entry, how its call is written, and the rows that pin every kernel family.
 Pure data, no GPU.  A new kernel family is registered HERE: its rows in CASES (and TINY_CASES), with the knobs that pin it and the name
-mz_debug_last_kernel() reports; tests/op_util.py runs the rows, tests/exact_util.py and tests/large_util.py build their tables on them."""
+mz_debug_last_kernel() reports; tests/op_util.py runs the rows, tests/exact_util.py and tests/large_util.py build their tables on them.
+A new ENTRY gets its argument names in ARGS; what it is (inputs and their roles, output, reference) is stated once in tests/op_ref.py."""
 
 from types import SimpleNamespace
 

@@ -1,15 +1,19 @@
-"""The runner of the operator tests: knobs, seeded data, the ONE call of each mz_op_* entry (run_entry), the tensors and oracle of a row
-of tests/op_cases.py (Op), and the host's choice read without a GPU (selected).  A new entry gets its names in op_cases.ARGS, its call in
-run_entry and its tensors in Op."""
+"""The runner of the operator tests: knobs, seeded data, the ONE call of each mz_op_* entry (run_entry), the ONE way an entry's tensors
+reach the GPU and its output comes back (upload, alloc_out, real, launch: by the roles of tests/op_ref.py), the ONE check of a row of the
+exact tables (check_rounded_once), the seeded data and oracle of a row of tests/op_cases.py (Op), and the host's choice read without a
+GPU (selected).  A new entry gets its names in op_cases.ARGS, its call in run_entry, its inputs, output and reference in
+op_ref.ENTRIES and its seeds in SEEDS."""
 
 import ctypes
+import functools
 import re
 from pathlib import Path
 
 import torch
-import torch.nn.functional as F
 
-from gpu_util import DTYPES, alloc_act, from_act, q, stream_ptr, to_act, ulp_of
+import op_ref
+from exact_util import MAX_EXCLUDED, bits_of
+from gpu_util import DTYPES, assert_op_close, last_kernel, pad16, pad_part, planes_per, q, stream_ptr, to_act, ulp_of
 from op_cases import KNOBS, fields, select_args
 from oracle import mewzoom_oracle as oracle
 from ultrazoom_amd import _ffi
@@ -82,78 +86,125 @@ def op_conv_mix(dtype, hid, x, w2, wmix, alpha, out, B, H, W, cin, cout):
     run_entry("conv_mix", (B, H, W, cin, cout), dtype, {"hid": hid, "x": x, "w2": dev_w(w2), "wmix": dev_w(wmix)}, out, alpha)
 
 
+def upload(entry, args, dt, inputs):
+    """The entry's inputs, logical float CPU tensors by name, as the device tensors of its call: by the roles of tests/op_ref.py."""
+    dtype = DTYPES.get(dt, dt)
+    op_ref.check_shapes(entry, args, inputs)
+    how = {op_ref.ACT: lambda v: to_act(v, dtype), op_ref.IMG: lambda v: v.to("cuda", dtype).contiguous(), op_ref.PAR: dev_w}
+    return {name: how[role](inputs[name]) for name, (_, role) in op_ref.inputs(entry, args).items()}
+
+
+def out_shape(entry, args, dt):
+    """Shape of the output's device tensor: plane-major, or the head's dense image."""
+    C, logical = op_ref.output(entry, args)
+    ppu = planes_per(DTYPES.get(dt, dt))
+    return logical if C is None else (logical[0], pad16(C) // ppu, logical[2], logical[3], ppu)
+
+
+def alloc_out(entry, args, dt, fill=7.0):
+    """The output's device tensor, pre-filled with garbage."""
+    return torch.full(out_shape(entry, args, dt), fill, dtype=DTYPES.get(dt, dt), device="cuda")
+
+
+def real(entry, args, out):
+    """The real channels of an output, [B, C, Hout, Wout] in its storage type, on the CPU."""
+    C = op_ref.output(entry, args)[0]
+    if C is None:
+        return out.cpu()
+    B, P, H, W, ppu = out.shape
+    return out.permute(0, 1, 4, 2, 3).reshape(B, P * ppu, H, W)[:, :C].cpu()
+
+
+def launch(entry, args, dt, inputs, alpha=0.0):
+    """The operator on the given data (upload): (output on the GPU, its real channels [B, C, H, W] on the CPU, storage type)."""
+    out = alloc_out(entry, args, dt)
+    run_entry(entry, args, dt, upload(entry, args, dt, inputs), out, alpha)
+    return out, real(entry, args, out)
+
+
+def check_rounded_once(row, what, ex, out, got):
+    """A row of the exact tables (exact_util.Exact) after launch(): equality with the float64 result rounded once (zeros of either sign
+    are equal); the elements whose transcendental is not saturated are compared with the one-operator tolerance instead."""
+    if row.kernel is not None:
+        assert last_kernel() == row.kernel, (last_kernel(), row.kernel)
+    want = ex.want
+    assert got.shape == want.shape and got.dtype == want.dtype
+    assert not bool(torch.isnan(got.float()).any())
+    g, w = (got, want) if ex.keep is None else (got[ex.keep], want[ex.keep])
+    if not torch.equal(g, w):
+        bad = (got != want) if ex.keep is None else (got != want) & ex.keep
+        idx = tuple(int(v) for v in bad.nonzero()[0])
+        mask = 0xFFFFFFFF if row.dt == "f32" else 0xFFFF
+        flushed = int((bad & (got == 0)).sum())
+        raise AssertionError(f"{what}: {int(bad.sum())} of {g.numel()} elements differ from the float64 result rounded once ({flushed} of them are "
+                             f"zero); first at {idx}: got {got[idx].item()!r} (bits {bits_of(got[idx].reshape(1)).item() & mask:#x}), want "
+                             f"{want[idx].item()!r} (bits {bits_of(want[idx].reshape(1)).item() & mask:#x}), float64 {ex.y64[idx].item()!r}")
+    if ex.keep is not None:
+        print(f"{what}: excluded share {ex.excluded:.5f} ({int((~ex.keep).sum())} elements)")
+        assert ex.excluded <= MAX_EXCLUDED
+        assert bool(torch.isfinite(got.float()).all())
+        soft = ~ex.keep
+        if bool(soft.any()):
+            assert_op_close(got.float()[soft], ex.soft64[soft].float(), row.dt, what + " (excluded elements)")
+    if ex.C is not None:
+        assert bool((pad_part(out, ex.C) == 0).all()), "pad channels must be written as zeros"
+
+
+# Op's data: seeds in the order of the entry's inputs, the alpha of the mixes, and the parameters that are not q(wrnd(shape, seed))
+SEEDS = {"conv": (1, 2), "film": (1, 2, 43, 44), "d2s": (3, 4), "crush": (5, 6), "mix": (7, 8, 9), "conv_mix": (41, 42, 43, 44),
+         "stem": (10, 11, 12), "final": (13, 14, 15)}
+ALPHA = {"mix": 0.37, "conv_mix": 0.3}
+
+
+def _parameter(shape, seed, dtype):
+    return q(wrnd(shape, seed), dtype)
+
+
+PARAMETERS = {("film", "gamma"): lambda shape, seed, dtype: 1.0 + 0.5 * rnd(shape, seed),
+              ("film", "beta"): lambda shape, seed, dtype: 0.3 * rnd(shape, seed),
+              ("stem", "w"): lambda shape, seed, dtype: rnd(shape, seed),
+              ("stem", "b"): lambda shape, seed, dtype: rnd(shape, seed, 0.1),
+              ("final", "w"): lambda shape, seed, dtype: q(wrnd(shape, seed) * 0.5, dtype)}
+
+
 class Op:
-    """One operator call: its device tensors by argument name, which of them hold one entry per image, its output and its oracle."""
+    """One operator call on seeded O(1) data.  Host side, needs no GPU: `inputs` (float32 CPU tensors by argument name, rounded to the
+    storage type where they travel in it), `batched` (the names that hold one entry per image), `C` and `out_shape` of the output,
+    `alpha`, the float32 oracle `want` and `tol`.  `t` uploads the inputs when it is first read."""
 
     def __init__(self, entry, args, dt):
         self.entry, self.args, self.dt = entry, args, dt
         dtype = self.dtype = DTYPES[dt]
-        a = fields(entry, args)
-        B, H, W = a.B, a.H, a.W
-        self.alpha = 0.0
+        stated = op_ref.inputs(entry, args)
+        self.inputs = {}
+        for (name, (shape, role)), seed in zip(stated.items(), SEEDS[entry], strict=True):
+            if role == op_ref.PAR:
+                self.inputs[name] = PARAMETERS.get((entry, name), _parameter)(shape, seed, dtype)
+            else:  # an image is not negative
+                self.inputs[name] = q(rnd(shape, seed).abs() if role == op_ref.IMG else rnd(shape, seed), dtype)
+        self.batched = [name for name, (_, role) in stated.items() if role != op_ref.PAR]
+        self.C, self.out_shape = op_ref.output(entry, args)[0], out_shape(entry, args, dt)
+        self.alpha = ALPHA.get(entry, 0.0)
         self.tol = None  # element-wise tolerance where it is not gpu_util's one-operator tolerance
-        if entry in ("conv", "film"):
-            x, w = q(rnd((B, a.cin, H, W), 1), dtype), q(wrnd((a.cout, a.cin, 3, 3), 2), dtype)
-            self.t, self.batched = {"in0": to_act(x, dtype), "w": dev_w(w)}, ["in0"]
-            self.C, self.out_shape = a.cout, alloc_act(B, a.cout, H, W, dtype).shape
-            if entry == "film":
-                gamma, beta = 1.0 + 0.5 * rnd((B, a.cout), 43), 0.3 * rnd((B, a.cout), 44)
-                self.t.update(gamma=dev_w(gamma), beta=dev_w(beta))
-                self.want = oracle.film_conv(x, w, gamma.float(), beta.float(), bool(a.silu))
-            else:
-                self.want = F.conv2d(x, w, padding=1)
-                if a.silu:
-                    self.want = F.silu(self.want)
-        elif entry == "d2s":
-            x, w = q(rnd((B, a.cin, H, W), 3), dtype), q(wrnd((a.cout, a.cin, 3, 3), 4), dtype)
-            self.t, self.batched = {"in0": to_act(x, dtype), "w": dev_w(w)}, ["in0"]
-            self.C, self.out_shape = a.cout // 4, alloc_act(B, a.cout // 4, a.Hout, a.Wout, dtype).shape
-            self.want = oracle.fit_to(oracle.subpixel_conv(x, w), (a.Hout, a.Wout))
-        elif entry == "crush":
-            x, w = q(rnd((B, a.cin, H, W), 5), dtype), q(wrnd((a.cout, a.cin, 2, 2), 6), dtype)
-            self.t, self.batched = {"in0": to_act(x, dtype), "w": dev_w(w)}, ["in0"]
-            self.C, self.out_shape = a.cout, alloc_act(B, a.cout, H // 2, W // 2, dtype).shape
-            self.want = F.conv2d(x, w, stride=2)
-        elif entry == "mix":
-            c = a.C
-            x, z, w = q(rnd((B, c, H, W), 7), dtype), q(rnd((B, c, H, W), 8), dtype), q(wrnd((c, 2 * c, 1, 1), 9), dtype)
-            self.alpha = 0.37
-            self.t, self.batched = {"in0": to_act(x, dtype), "in1": to_act(z, dtype), "w": dev_w(w)}, ["in0", "in1"]
-            self.C, self.out_shape = c, alloc_act(B, c, H, W, dtype).shape
-            self.want = oracle.residual_mix(x, z, w, torch.tensor(self.alpha))
-        elif entry == "conv_mix":
-            cin, cout = a.cin, a.cout
-            hid, x = q(rnd((B, cin, H, W), 41), dtype), q(rnd((B, cout, H, W), 42), dtype)
-            w2, wmix = q(wrnd((cout, cin, 3, 3), 43), dtype), q(rnd((cout, 2 * cout, 1, 1), 44, (3.0 / (2 * cout)) ** 0.5 * 1.7), dtype)
-            self.alpha = 0.3
-            self.t, self.batched = {"hid": to_act(hid, dtype), "x": to_act(x, dtype), "w2": dev_w(w2), "wmix": dev_w(wmix)}, ["hid", "x"]
-            self.C, self.out_shape = cout, alloc_act(B, cout, H, W, dtype).shape
-            # the kernel rounds z to the storage type before the gate GEMM and the blend, as the unfused path stores it: one rounding
-            # of the output plus one rounding step of z where its fp32 sum sits on a boundary (tests/test_conv3r_gpu.py)
-            z = q(F.conv2d(hid, w2, padding=1), dtype)
-            self.want = oracle.residual_mix(x, z, wmix, torch.tensor(self.alpha))
-            self.tol = ulp_of(self.want, dt) + ulp_of(z, dt) + 1e-5
-        elif entry == "stem":
-            c = a.C
-            x, w, b = q(rnd((B, 3, H, W), 10).abs(), dtype), rnd((c, 3, 1, 1), 11), rnd((c,), 12, 0.1)
-            self.t, self.batched = {"x": x.to("cuda", dtype).contiguous(), "w": dev_w(w), "b": dev_w(b)}, ["x"]
-            self.C, self.out_shape = c, alloc_act(B, c, H, W, dtype).shape
-            self.want = F.conv2d(x, w, b)
-        elif entry == "final":
-            Hi, Wi = 2 * H // a.R, 2 * W // a.R
-            assert Hi * a.R == 2 * H and Wi * a.R == 2 * W
-            feat, img = q(rnd((B, a.cin, H, W), 13), dtype), q(rnd((B, 3, Hi, Wi), 14).abs(), dtype)
-            w = q(wrnd((12, a.cin, 3, 3), 15) * 0.5, dtype)
-            self.t = {"feat": to_act(feat, dtype), "img": img.to("cuda", dtype).contiguous(), "w": dev_w(w)}
-            self.batched = ["feat", "img"]
-            self.C, self.out_shape = None, (B, 3, 2 * H, 2 * W)  # a dense NCHW image
-            self.want = oracle.bicubic_upsample(img, a.R) + oracle.subpixel_conv(feat, w)
+        if entry in op_ref.MIXES:
+            # the fused kernel rounds z to the storage type before the gate GEMM and the blend, as the unfused path stores it: one
+            # rounding of the output plus one rounding step of z where its fp32 sum sits on a boundary (tests/test_conv3r_gpu.py)
+            m = op_ref.Mix(entry, self.inputs, lambda z: q(z, dtype))
+            self.want = oracle.residual_mix(m.x, m.z, m.w, torch.tensor(self.alpha))
+            if entry == "conv_mix":
+                self.tol = ulp_of(self.want, dt) + ulp_of(m.z, dt) + 1e-5
         else:
-            raise ValueError(entry)
+            self.want = op_ref.reference(entry, args, self.inputs)
+        assert tuple(self.want.shape) == op_ref.output(entry, args)[1], (entry, args)
+
+    @functools.cached_property
+    def t(self):
+        """The device tensors by argument name."""
+        return upload(self.entry, self.args, self.dt, self.inputs)
 
     def real(self, out):
         """The output's real channels as float32 [B, C, H, W] on the CPU."""
-        return out.float().cpu() if self.C is None else from_act(out, self.C)
+        return real(self.entry, self.args, out).float()
 
     def run(self, t, out):
         run_entry(self.entry, self.args, self.dt, t, out, self.alpha)

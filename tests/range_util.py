@@ -43,11 +43,11 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
-from exact_util import (AW, GATE_SCALE, INT_MAX, ROWS, SAT_HI, SAT_LO, Exact, Row, _abs_sum, _round_parts, _saturate, choice, ints, lower_edge,
-                        round_once, row_id, taps_inside)
+import op_ref
+from exact_util import AW, GATE_SCALE, INT_MAX, ROWS, SAT_HI, SAT_LO, Exact, Row, _round_parts, choice, finish, ints, lower_edge, row_id, taps_inside
 from gpu_util import DTYPES
 from op_cases import ALL, CASES, LOW, TINY_CASES, fields
-from oracle import mewzoom_oracle as oracle
+from op_ref import MIXES, abs_sum
 
 MIN_NORMAL = {"f32": 2.0 ** -126, "bf16": 2.0 ** -126, "f16": 2.0 ** -14}
 MANTISSA = {"f32": 23, "bf16": 7, "f16": 10}
@@ -96,31 +96,32 @@ def drivers(c: int):
 
 
 # ---- SMALL ---------------------------------------------------------------------------------------------------------------------------
-def _gate(ex: Exact, dt, x, z64, c, seed):
-    """The driver construction (module docstring): wmix, the driver-only gate that classifies, the bound of what the rest moves."""
-    d = lambda t: t.double()
+def _gate_weights(c, seed):
+    """The driver construction (module docstring): x16 integers in the drivers' columns, m 2^-10 in every other."""
     drv = drivers(c)
     wmix = ints((c, 2 * c, 1, 1), AW, seed, GATE_REST)
     wmix[:, drv] = ints((c, len(drv), 1, 1), AW, seed + 1, float(GATE_SCALE))
-    xz = torch.cat([d(x), z64], dim=1)
-    only = torch.zeros_like(xz)
-    only[:, drv] = xz[:, drv]
-    gate = F.conv2d(only, d(wmix))
-    ex.sums["gate"] = _abs_sum(only, d(wmix))
-    ex.gate_shift = _abs_sum(xz - only, d(wmix))
-    rest = torch.ones(c, dtype=torch.bool)
-    rest[drv] = False
-    ex.rest = rest
-    _saturate(ex, gate, (d(x) + z64) / 2, d(x), d(x) + 0.5 * torch.sigmoid(F.conv2d(xz, d(wmix))) * (z64 - d(x)))
-    ex.z64 = z64
     return wmix
+
+
+def _drivers_gate(ex: Exact, m, sx):
+    """The driver-only gate, which classifies, and the bound of what the rest moves; the blend's sum over the channels that are no
+    drivers', in units of the activations' scale `sx` (x and the rounded z are multiples of it)."""
+    c = m.x.shape[1]
+    drv = drivers(c)
+    only = torch.zeros_like(m.xz)
+    only[:, drv] = m.xz[:, drv]
+    ex.sums["gate"] = abs_sum(only, m.w)
+    ex.gate_shift = abs_sum(m.xz - only, m.w)
+    ex.rest = torch.ones(c, dtype=torch.bool)
+    ex.rest[drv] = False
+    ex.sums["blend"] = (m.x.abs() + m.z.abs())[:, ex.rest].max().item() / sx
+    return F.conv2d(only, m.w)
 
 
 def _build_small(entry, args, dt, silu, variant) -> Exact:
     ex = Exact()
-    d = lambda t: t.double()
-    a = fields(entry, args)
-    B, H, W = a.B, a.H, a.W
+    s = op_ref.shapes(entry, args)
     xs, ax, ws = SCALE[(dt, variant)]
     if dt == "f32" and entry in HALVING:
         xs *= 2.0
@@ -135,82 +136,55 @@ def _build_small(entry, args, dt, silu, variant) -> Exact:
             ex.subnormal[name] = (is_sub(t, dt).double().mean().item(), floor)
 
     if entry in ("conv", "film", "d2s", "crush"):
-        cin, cout = a.cin, a.cout
-        k = 2 if entry == "crush" else 3
-        x, w = ints((B, cin, H, W), ax, 201, xs), ints((cout, cin, k, k), AW, 202, ws)
+        x, w = ints(s["in0"], ax, 201, xs), ints(s["w"], AW, 202, ws)
         if silu:  # saturated without drivers (module docstring)
             assert entry == "conv" and variant != "wsub"
-            sign = torch.where(torch.arange(cout) % 2 == 0, 1.0, -1.0)[:, None, None, None]
-            x, w = x.abs(), ints((cout, cin, k, k), AW, 202, SILU_WS[dt]).abs() * sign
+            sign = torch.where(torch.arange(s["w"][0]) % 2 == 0, 1.0, -1.0)[:, None, None, None]
+            x, w = x.abs(), ints(s["w"], AW, 202, SILU_WS[dt]).abs() * sign
             ex.grid = xs * SILU_WS[dt]
         ex.inputs = {"in0": x, "w": w}
         note("in0", x, xfloor)
         note("w", w, wfloor)
-        kw = {"stride": 2} if entry == "crush" else {"padding": 1}
-        ex.sums["conv"] = _abs_sum(d(x), d(w), **kw) / ex.grid
-        if entry == "d2s":
-            ex.C, ex.y64 = cout // 4, oracle.fit_to(oracle.subpixel_conv(d(x), d(w)), (a.Hout, a.Wout))
-        elif entry == "film":  # gamma as exact_util's, beta on the product grid
-            gamma, beta = choice((B, cout), [-1.0, 0.5, 1.0, 2.0], 203), ints((B, cout), 8, 204, ex.grid)
-            ex.inputs.update(gamma=gamma, beta=beta)
-            ex.C, ex.y64 = cout, oracle.film_conv(d(x), d(w), d(gamma), d(beta), False)
-            ex.sums["film"] = (F.conv2d(d(x).abs(), d(w).abs(), padding=1) * d(gamma).abs()[:, :, None, None]
-                               + d(beta).abs()[:, :, None, None]).max().item() / (ex.grid / 2)
-        else:
-            ex.C, ex.y64 = cout, F.conv2d(d(x), d(w), **kw)
-            if silu:
-                y = ex.y64
-                _saturate(ex, y, y, torch.zeros_like(y), F.silu(y))
+        if entry == "film":  # gamma as exact_util's, beta on the product grid
+            ex.inputs.update(gamma=choice(s["gamma"], [-1.0, 0.5, 1.0, 2.0], 203), beta=ints(s["beta"], 8, 204, ex.grid))
     elif entry == "stem":
-        c = a.C
-        x = ints((B, 3, H, W), ax, 205, xs).abs()
-        w, b = choice((c, 3, 1, 1), [-2.0, -1.0, -0.5, 0.5, 1.0, 2.0], 206), ints((c,), 8, 207, xs)
         ex.grid = xs / 2
-        ex.inputs = {"x": x, "w": w, "b": b}
-        note("x", x, xfloor)
-        ex.C, ex.y64 = c, F.conv2d(d(x), d(w), d(b))
-        ex.sums["stem"] = F.conv2d(d(x), d(w).abs(), d(b).abs()).max().item() / ex.grid
+        ex.inputs = {"x": ints(s["x"], ax, 205, xs).abs(), "w": choice(s["w"], [-2.0, -1.0, -0.5, 0.5, 1.0, 2.0], 206), "b": ints(s["b"], 8, 207, xs)}
+        note("x", ex.inputs["x"], xfloor)
     elif entry == "final":
-        cin, R = a.cin, a.R
-        feat, w = ints((B, cin, H, W), ax, 208, xs), ints((12, cin, 3, 3), AW, 209, ws)
-        img = torch.zeros(B, 3, 2 * H // R, 2 * W // R)  # the bicubic term is exactly zero
-        ex.inputs = {"feat": feat, "img": img, "w": w}
-        note("feat", feat, xfloor)
-        note("w", w, wfloor)
-        ex.C, ex.y64 = None, oracle.bicubic_upsample(d(img), R) + oracle.subpixel_conv(d(feat), d(w))
-        ex.sums["conv"] = _abs_sum(d(feat), d(w), padding=1) / ex.grid
-    elif entry in ("mix", "conv_mix"):
-        c = a.C if entry == "mix" else a.cout
+        ex.inputs = {"feat": ints(s["feat"], ax, 208, xs),
+                     "img": torch.zeros(s["img"]),  # the bicubic term is exactly zero
+                     "w": ints(s["w"], AW, 209, ws)}
+        note("feat", ex.inputs["feat"], xfloor)
+        note("w", ex.inputs["w"], wfloor)
+    elif entry in MIXES:
+        xname = "in0" if entry == "mix" else "x"
+        B, c, H, W = s[xname]
         drv = drivers(c)
         rest = [i for i in range(c) if i not in drv]
         # x at the bottom of the type (the "wsub" variant's, too: its activations of 2^-8 belong to hid), integers in the driver channels
         sx, amp = (2.0 ** -24, 1023) if variant == "wsub" else (xs, ax)
-        x = ints((B, c, H, W), amp, 210, sx)
+        x = ints(s[xname], amp, 210, sx)
         x[:, drv] = ints((B, len(drv), H, W), INT_MAX[dt], 211)
         if entry == "mix":
-            z = ints((B, c, H, W), ax, 212, xs)
+            z = ints(s["in1"], ax, 212, xs)
             z[:, drv] = 0.0
-            ex.inputs = {"in0": x, "in1": z}
+            ex.inputs = {"in0": x, "in1": z, "w": _gate_weights(c, 215)}
             note("in0", x, FLOOR_X, rest)
             note("in1", z, FLOOR_X, rest)
-            z64, wname = d(z), "w"
         else:
-            cin = a.cin
-            hid, w2 = ints((B, cin, H, W), ax, 213, xs), ints((c, cin, 3, 3), AW, 214, ws)
+            hid, w2 = ints(s["hid"], ax, 213, xs), ints(s["w2"], AW, 214, ws)
             w2[drv] = 0.0
-            ex.inputs = {"hid": hid, "x": x, "w2": w2}
+            ex.inputs = {"hid": hid, "x": x, "w2": w2, "wmix": _gate_weights(c, 215)}
             note("x", x, FLOOR_X, rest)
             note("hid", hid, xfloor)
             note("w2", w2[rest], wfloor)
-            ex.sums["conv"] = _abs_sum(d(hid), d(w2), padding=1) / ex.grid
-            ex.z64_unrounded = F.conv2d(d(hid), d(w2), padding=1)
-            z64, wname = round_once(ex.z64_unrounded, dt).double(), "wmix"  # z is rounded BEFORE the gate GEMM and the blend
-        ex.inputs[wname] = _gate(ex, dt, x, z64, c, 215)
-        ex.C = c
-        ex.sums["blend"] = (d(x).abs() + z64.abs())[:, rest].max().item() / sx  # x and the rounded z are multiples of sx
     else:
         raise ValueError(entry)
-    ex.want = round_once(ex.y64, dt)
+    finish(ex, entry, args, dt, silu, gate=functools.partial(_drivers_gate, sx=sx) if entry in MIXES else None)
+    for name, unit in (("conv", ex.grid), ("film", ex.grid / 2), ("stem", ex.grid)):  # in units of the quantity's grid
+        if name in ex.sums:
+            ex.sums[name] /= unit
     return ex
 
 
@@ -271,51 +245,32 @@ def _plant(x, w, tap, step):
 
 def _build_large(entry, args) -> Exact:
     ex = Exact()
-    d = lambda t: t.double()
-    a = fields(entry, args)
-    B, H, W = a.B, a.H, a.W
+    a, s = fields(entry, args), op_ref.shapes(entry, args)
     if entry in ("conv", "film", "d2s", "crush"):
-        cin, cout = a.cin, a.cout
-        k = 2 if entry == "crush" else 3
-        nterms = taps_inside(H, W, k) * cin * (1.5 if entry == "film" else 1)  # film: gamma of {-1, 1/2, 1, 2} has a mean square of 1.56
-        x, w = ints((B, cin, H, W), large_ax(nterms), 301), ints((cout, cin, k, k), AW, 302)
+        k = s["w"][-1]
+        nterms = taps_inside(a.H, a.W, k) * a.cin * (1.5 if entry == "film" else 1)  # film: gamma of {-1, 1/2, 1, 2} has a mean square of 1.56
+        x, w = ints(s["in0"], large_ax(nterms), 301), ints(s["w"], AW, 302)
         _plant(x, w, (0, 0) if k == 2 else (1, 1), 2 if k == 2 else 1)
         ex.inputs = {"in0": x, "w": w}
-        kw = {"stride": 2} if entry == "crush" else {"padding": 1}
-        ex.sums["conv"] = _abs_sum(d(x), d(w), **kw)
-        if entry == "d2s":
-            ex.C, ex.y64 = cout // 4, oracle.fit_to(oracle.subpixel_conv(d(x), d(w)), (a.Hout, a.Wout))
-        elif entry == "film":
-            gamma, beta = choice((B, cout), [-1.0, 0.5, 1.0, 2.0], 303), ints((B, cout), 8, 304)
+        if entry == "film":
+            gamma, beta = choice(s["gamma"], [-1.0, 0.5, 1.0, 2.0], 303), ints(s["beta"], 8, 304)
             gamma[0, 0], beta[0, 0] = 1.0, 0.0
             ex.inputs.update(gamma=gamma, beta=beta)
-            ex.C, ex.y64 = cout, oracle.film_conv(d(x), d(w), d(gamma), d(beta), False)
-            ex.sums["film"] = (F.conv2d(d(x).abs(), d(w).abs(), padding=1) * d(gamma).abs()[:, :, None, None] + d(beta).abs()[:, :, None, None]).max().item()
-        else:
-            ex.C, ex.y64 = cout, F.conv2d(d(x), d(w), **kw)
     elif entry == "stem":  # the weights travel as f32: exact_util's times 16, or three pixels of 2047 could not reach 65504
-        c = a.C
-        x = ints((B, 3, H, W), INT_MAX["f16"], 305).abs()
-        w, b = choice((c, 3, 1, 1), [-2.0, -1.0, -0.5, 0.5, 1.0, 2.0], 306) * 16.0, ints((c,), 8, 307)
+        x = ints(s["x"], INT_MAX["f16"], 305).abs()
+        w, b = choice(s["w"], [-2.0, -1.0, -0.5, 0.5, 1.0, 2.0], 306) * 16.0, ints(s["b"], 8, 307)
         w[0, :, 0, 0], w[1, :, 0, 0] = torch.tensor([32.0, 1.0, 0.0]), torch.tensor([-32.0, -1.0, 0.0])
         b[0] = b[1] = 0.0
         for i, (p, q) in enumerate(PLANT[:2]):
             x[0, 0, 0, i], x[0, 1, 0, i] = p, q
         ex.inputs = {"x": x, "w": w, "b": b}
-        ex.C, ex.y64 = c, F.conv2d(d(x), d(w), d(b))
-        ex.sums["stem"] = F.conv2d(d(x), d(w).abs(), d(b).abs()).max().item()
     elif entry == "final":
-        cin, R = a.cin, a.R
-        feat, w = ints((B, cin, H, W), large_ax(taps_inside(H, W) * cin), 308), ints((12, cin, 3, 3), AW, 309)
+        feat, w = ints(s["feat"], large_ax(taps_inside(a.H, a.W) * a.cin), 308), ints(s["w"], AW, 309)
         _plant(feat, w, (1, 1), 1)
-        img = torch.zeros(B, 3, 2 * H // R, 2 * W // R)
-        ex.inputs = {"feat": feat, "img": img, "w": w}
-        ex.C, ex.y64 = None, oracle.bicubic_upsample(d(img), R) + oracle.subpixel_conv(d(feat), d(w))
-        ex.sums["conv"] = _abs_sum(d(feat), d(w), padding=1)
+        ex.inputs = {"feat": feat, "img": torch.zeros(s["img"]), "w": w}
     else:
         raise ValueError(entry)
-    ex.want = round_once(ex.y64, "f16")
-    return ex
+    return finish(ex, entry, args, "f16")
 
 
 @functools.lru_cache(maxsize=None)
@@ -454,8 +409,7 @@ def _gate_rows():
         if entry not in ("mix", "conv_mix"):
             continue
         f = fields(entry, args)
-        c = f.C if entry == "mix" else f.cout
-        B = window_B(dt, c * f.H * f.W, f.B)
+        B = window_B(dt, op_ref.output(entry, args)[0] * f.H * f.W, f.B)
         out.append(Win(entry, (B,) + tuple(args[1:]), env, dt, kernel))
     return out
 
@@ -480,8 +434,9 @@ def _cached_window(entry, args, dt):
     d = lambda t: t.double()
     a = fields(entry, args)
     B, H, W = a.B, a.H, a.W
+    wd.C = c = op_ref.output(entry, args)[0]
     if entry in ("conv", "film"):
-        cin, cout = a.cin, a.cout
+        cin, cout = a.cin, c
         nread = min(cin, cout)
         x = torch.empty(B, cin, H, W)
         x[:, :nread] = _fill(B * nread * H * W, dt, 401).reshape(B, nread, H, W)
@@ -492,14 +447,12 @@ def _cached_window(entry, args, dt):
         wd.inputs = {"in0": x, "w": w}
         if entry == "film":
             wd.inputs.update(gamma=torch.ones(B, cout), beta=torch.zeros(B, cout))
-        wd.C = cout
         wd.x64 = d(x)[:, src]
         wd.want64 = wd.x64 * torch.sigmoid(wd.x64)
         wd.scale64 = wd.want64.abs()
         wd.may_flush, wd.flushed64 = torch.sigmoid(wd.x64) < RCP_MIN * (1 + REL), 0.0 * wd.x64
         wd.read = x[:, :nread]
     else:
-        c = a.C if entry == "mix" else a.cout
         n = B * c * H * W
         x = _fill(n, dt, 411).reshape(B, c, H, W)
         g = torch.Generator().manual_seed(412)
@@ -516,12 +469,12 @@ def _cached_window(entry, args, dt):
             w2 = torch.zeros(c, cin, 3, 3)
             w2[torch.arange(c), torch.arange(c), 1, 1] = 1.0  # z[c] = hid[c]
             wd.inputs = {"hid": hid, "x": x, "w2": w2, "wmix": wmix}
-        wd.C = c
         wd.x64, wd.z64 = d(x), d(zc)
         wd.want64 = wd.x64 + 0.5 * torch.sigmoid(wd.x64) * (wd.z64 - wd.x64)
         wd.scale64 = wd.x64.abs() + (wd.z64 - wd.x64).abs()
         wd.may_flush, wd.flushed64 = 0.5 * torch.sigmoid(wd.x64) < RCP_MIN * (1 + REL), wd.x64
         wd.read = x
+    op_ref.check_shapes(entry, args, wd.inputs)
     return wd
 
 

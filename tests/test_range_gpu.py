@@ -11,62 +11,12 @@ tests/test_range_cpu.py holds the data to the conditions that keep these from be
 import pytest
 import torch
 
-from exact_util import MAX_EXCLUDED, bits_of, row_id
-from gpu_util import DTYPES, alloc_act, assert_op_close, last_kernel, pad_part, to_act
-from op_util import run_entry, set_knobs
+from exact_util import bits_of, row_id
+from gpu_util import last_kernel, pad_part
+from op_util import check_rounded_once, launch, set_knobs
 from range_util import GATE_WINDOW, LARGE, SILU_TWINS, SILU_WINDOW, SMALL, large, small, small_id, win_id, window, window_ratio
 
 pytestmark = pytest.mark.gpu
-
-ACTIVATIONS = {"in0", "in1", "hid", "x", "feat"}  # plane-major activation tensors; the stem's x and the head's img are dense images
-
-
-def launch(entry, args, dt, inputs, C, shape, alpha=0.0):
-    """The operator on the given data: (output on the GPU, its real channels [B, C, H, W] on the CPU, storage type)."""
-    dtype = DTYPES[dt]
-    t = {}
-    for name, v in inputs.items():
-        if name in ACTIVATIONS and not (entry == "stem" and name == "x"):
-            t[name] = to_act(v, dtype)
-        elif name in ("x", "img"):
-            t[name] = v.to("cuda", dtype).contiguous()
-        else:
-            t[name] = v.to("cuda", torch.float32).contiguous()
-    if C is None:
-        out = torch.full(tuple(shape), 7.0, dtype=dtype, device="cuda")
-    else:
-        out = alloc_act(shape[0], C, shape[2], shape[3], dtype)
-    run_entry(entry, args, dt, t, out, alpha)
-    if C is None:
-        return out, out.cpu()
-    Bo, P, H, W, ppu = out.shape
-    return out, out.permute(0, 1, 4, 2, 3).reshape(Bo, P * ppu, H, W)[:, :C].cpu()
-
-
-def check(row, what, ex, out, got):
-    """Equality with the float64 result rounded once (zeros of either sign are equal); exact_util's rule for the excluded elements."""
-    if row.kernel is not None:
-        assert last_kernel() == row.kernel, (last_kernel(), row.kernel)
-    want = ex.want
-    assert got.shape == want.shape and got.dtype == want.dtype
-    assert not bool(torch.isnan(got.float()).any())
-    g, w = (got, want) if ex.keep is None else (got[ex.keep], want[ex.keep])
-    if not torch.equal(g, w):
-        bad = (got != want) if ex.keep is None else (got != want) & ex.keep
-        idx = tuple(int(v) for v in bad.nonzero()[0])
-        mask = 0xFFFFFFFF if row.dt == "f32" else 0xFFFF
-        flushed = int((bad & (got == 0)).sum())
-        raise AssertionError(f"{what}: {int(bad.sum())} of {g.numel()} elements differ from the float64 result rounded once ({flushed} of them are "
-                             f"zero); first at {idx}: got {got[idx].item()!r} (bits {bits_of(got[idx].reshape(1)).item() & mask:#x}), want "
-                             f"{want[idx].item()!r} (bits {bits_of(want[idx].reshape(1)).item() & mask:#x}), float64 {ex.y64[idx].item()!r}")
-    if ex.keep is not None:
-        assert ex.excluded <= MAX_EXCLUDED
-        assert bool(torch.isfinite(got.float()).all())
-        soft = ~ex.keep
-        if bool(soft.any()):
-            assert_op_close(got.float()[soft], ex.soft64[soft].float(), row.dt, what + " (excluded elements)")
-    if ex.C is not None:
-        assert bool((pad_part(out, ex.C) == 0).all()), "pad channels must be written as zeros"
 
 
 @pytest.mark.parametrize("s", SMALL, ids=small_id)
@@ -74,23 +24,23 @@ def test_small_bit_for_bit(s, monkeypatch):
     row = s.row
     set_knobs(monkeypatch, row.env)
     ex = small(s)
-    out, got = launch(row.entry, row.args, row.dt, ex.inputs, ex.C, ex.want.shape, ex.alpha)
-    check(row, small_id(s), ex, out, got)
+    out, got = launch(row.entry, row.args, row.dt, ex.inputs, ex.alpha)
+    check_rounded_once(row, small_id(s), ex, out, got)
 
 
 @pytest.mark.parametrize("row", LARGE, ids=row_id)
 def test_large_bit_for_bit(row, monkeypatch):
     set_knobs(monkeypatch, row.env)
     ex = large(row)
-    out, got = launch(row.entry, row.args, row.dt, ex.inputs, ex.C, ex.want.shape)
-    check(row, row_id(row) + "-large", ex, out, got)
+    out, got = launch(row.entry, row.args, row.dt, ex.inputs)
+    check_rounded_once(row, row_id(row) + "-large", ex, out, got)
     assert bool(torch.isinf(got).any())
 
 
 def sweep(w, monkeypatch):
     set_knobs(monkeypatch, w.env)
     wd = window(w)
-    out, got = launch(w.entry, w.args, w.dt, wd.inputs, wd.C, wd.want64.shape)
+    out, got = launch(w.entry, w.args, w.dt, wd.inputs)
     assert last_kernel() == w.kernel, (last_kernel(), w.kernel)
     assert bool((pad_part(out, wd.C) == 0).all()), "pad channels must be written as zeros"
     return wd, got
