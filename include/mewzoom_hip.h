@@ -94,7 +94,7 @@ int mz_weights_complete(const mz_handle* h);
  * micro-batches of at most `max_images_in_flight` images (0 = library default), so memory does
  * not grow beyond that.
  *
- * What a call touches (mz_forward, mz_forward_u8, mz_forward_view, mz_metrics, mz_resize, mz_blur, mz_noise, mz_jpeg and the mz_op_* entries alike): it READS only its
+ * What a call touches (mz_forward, mz_forward_u8, mz_forward_view, mz_metrics, mz_resize, mz_interpolate, mz_blur, mz_noise, mz_jpeg and the mz_op_* entries alike): it READS only its
  * input tensors -- the elements its shape and strides name, never a byte next to them -- and the workspace bytes it has itself
  * written during that call; it WRITES only its outputs (of a view: the elements of the window) and its workspace, never an input.
  * The workspace needs no initialisation and carries nothing from one call to the next: whatever it holds, NaN patterns included,
@@ -137,7 +137,7 @@ int mz_forward_u8(mz_handle* h, const uint8_t* x, uint8_t* out_sr, float* out_qa
  * and out, or between elements of out, is the caller's responsibility and is not checked (beyond refusing an output stride of 0;
  * mz_blur, mz_noise and mz_jpeg also compare the two byte ranges).
  *
- * THE VIEW REFUSALS.  Every entry that takes views (mz_forward_view, mz_metrics, mz_resize, mz_blur, mz_noise, mz_jpeg, mz_dihedral,
+ * THE VIEW REFUSALS.  Every entry that takes views (mz_forward_view, mz_metrics, mz_resize, mz_interpolate, mz_blur, mz_noise, mz_jpeg, mz_dihedral,
  * mz_ensemble_add, mz_ensemble_finish) returns
  * MZ_ERR_INVALID_ARGUMENT, before anything touches the GPU, for: a null view or null data; an `elem` outside the entry's codes; a view
  * that is WRITTEN whose channel, row or column stride is 0, or whose image stride is 0 when B > 1 (strides of a view that is only read
@@ -265,6 +265,43 @@ int mz_resize(const mz_image_view* x, const mz_image_view* out, int elem, int B,
 /* Host only (no GPU): the table of output index i of one axis, from the source the device compiles too: returns count (<= cap), *first,
  * w[0..count) in double; negative on bad arguments (count > cap among them).  No reference counterpart. */
 int mz_debug_resize_taps(int n_in, int n_out, int filter, int i, int* first, double* w, int cap);
+
+/* ---- plain interpolation to any size: the model's own skip connection, `Upsample(scale_factor=r, mode="bicubic")` (model.py:71, 156),
+ *      and the bicubic baseline the reference puts next to every result (validate.py:84-118, test_compare.py:61-77) ----------------------
+ * NOT mz_resize: no antialiasing, a fixed tap count (1, 2 or 4 an axis) whatever the ratio, and bicubic with A = -0.75.  Stateless like
+ * mz_resize: the call enqueues on the given stream, never synchronises, allocates nothing, uses no atomics and needs NO WORKSPACE.  x is a
+ * VIEW of [B,3,Hin,Win], out a view of the window {y0, x0, h, w} of the [B,3,Hout,Wout] result, or of all of it when window is NULL (as
+ * for mz_resize: the window changes where results are stored, never what is computed).  Any sizes, up or down; no ratio limit.  Both
+ * views have one element type.  The touch contract of the workspace paragraph above holds: the call reads only the source elements that
+ * the window's outputs name and writes only the window.
+ *
+ * The arithmetic is torch.nn.functional.interpolate(x, size=(Hout, Wout), mode=..., align_corners=False) without antialiasing
+ * (Upsample(scale_factor=r) with an integer r is the same function).  Per axis, n_in samples to n_out, s = n_in / n_out in double:
+ *   nearest   (torch's legacy "nearest")  idx = i when n_in == n_out, else min((int)floorf((float)i * sf), n_in - 1) with
+ *             sf = (float)n_in / (float)n_out, in float32 as torch does it.  Elements are moved and never changed: bit patterns survive,
+ *             NaN payloads and -0 included.
+ *   bilinear  src = max(s (i + 0.5) - 0.5, 0);  i0 = (int)src;  i1 = i0 + (i0 < n_in - 1);  w = {1 - (src - i0), src - i0}
+ *   bicubic   src = s (i + 0.5) - 0.5;  f = floor(src);  t = src - f;  idx_k = clamp(f - 1 + k, 0, n_in - 1), k = 0..3;
+ *             w = {c2(t + 1), c1(t), c1(1 - t), c2(2 - t)};  c1(u) = ((A + 2) u - (A + 3)) u u + 1;  c2(u) = ((A u - 5 A) u + 8 A) u - 4 A;
+ *             A = -0.75
+ * Bilinear and bicubic: weights in double; each source row an output needs is filtered horizontally, the row results are combined
+ * vertically, both in FLOAT64 as acc = fma(w_k, v_k, acc) from 0 in ascending k; ONE rounding to the stored type.  A uint8 value v is
+ * read as v / 255 and stored as clamp -> * 255 + 0.5 -> truncate (float64); clamp != 0 clamps the other types to [0, 1] before the store
+ * (on 0 / 1 data bicubic reaches -0.32 and 1.32).  An axis with n_out == n_in has the weights {1, 0} / {0, 1, 0, 0} exactly: finite values
+ * pass through.  Dense and strided views give the same bits, two calls give the same bits, and an image does not depend on the batch it
+ * is interpolated in.  (ultrazoom_amd/csrc/mz_interp.h is the one statement of taps and order, compiled by the kernels and the host.)
+ *
+ * Refuses the view refusals above (elem outside 0..3), and: a mode outside 0..2; B < 1 or > 65535; a size < 1 or > 2^28; x and out whose
+ * byte ranges overlap or do not fit in signed 64-bit addresses; clamp != 0 with nearest. */
+#define MZ_INTERP_NEAREST  0
+#define MZ_INTERP_BILINEAR 1
+#define MZ_INTERP_BICUBIC  2
+/* elem 0..2 = mz_dtype, 3 = uint8; window {y0, x0, h, w} of the Hout x Wout result or NULL; no workspace */
+int mz_interpolate(const mz_image_view* x, const mz_image_view* out, int elem, int B, int Hin, int Win,
+                   int Hout, int Wout, int mode, int clamp, const int32_t window[4], void* hip_stream);
+/* host only, no GPU: the taps of output index i of one axis, from the source the kernels compile too:
+   returns count (1, 2 or 4), idx[0..count) already clamped to [0, n_in), w[0..count) in double; negative on bad arguments */
+int mz_debug_interp_taps(int n_in, int n_out, int mode, int i, int idx[4], double w[4]);
 
 /* ---- the degradation chain: no reference counterpart in `model.py`; stands in for torchvision's `gaussian_blur`, `gaussian_noise`
  *      and `jpeg` as the reference's `transforms.py` calls them (data.py:134-164: blur -> noise -> resize -> JPEG makes the LR input of

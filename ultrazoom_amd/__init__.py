@@ -9,7 +9,8 @@ All arithmetic runs in hand-written gfx950 kernels behind the C ABI in include/m
 
 from .degrade import Degradation, gaussian_blur, gaussian_noise, jpeg  # noqa: F401
 from .ensemble import dihedral, dihedral_inverse, upscale_ensemble  # noqa: F401
+from .interpolate import interpolate  # noqa: F401
 from .model import MewZoom, bake_state_dict  # noqa: F401
 
 __all__ = ["MewZoom", "bake_state_dict", "Degradation", "gaussian_blur", "gaussian_noise", "jpeg", "dihedral", "dihedral_inverse",
-           "upscale_ensemble"]
+           "upscale_ensemble", "interpolate"]

@@ -24,6 +24,7 @@ MZ_METRIC_SLOTS = 16  # doubles per image of mz_metrics' output (include/mewzoom
 MZ_METRIC_PSNR, MZ_METRIC_SSIM, MZ_METRIC_VIF = 1, 2, 4
 MZ_RESIZE_BICUBIC, MZ_RESIZE_BILINEAR = 0, 1
 MZ_RESIZE_MAX_TAPS = 66  # taps of one output at the largest accepted ratio (n_in / n_out = 16, bicubic)
+MZ_INTERP_NEAREST, MZ_INTERP_BILINEAR, MZ_INTERP_BICUBIC = 0, 1, 2
 
 
 class MzConfig(Structure):
@@ -91,6 +92,11 @@ def _declare(lib) -> None:
     lib.mz_resize.restype = c_int
     lib.mz_debug_resize_taps.argtypes = [c_int, c_int, c_int, c_int, POINTER(c_int), POINTER(c_double), c_int]
     lib.mz_debug_resize_taps.restype = c_int
+    lib.mz_interpolate.argtypes = [POINTER(MzImageView), POINTER(MzImageView), c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                                   POINTER(c_int32), c_void_p]
+    lib.mz_interpolate.restype = c_int
+    lib.mz_debug_interp_taps.argtypes = [c_int, c_int, c_int, c_int, POINTER(c_int), POINTER(c_double)]
+    lib.mz_debug_interp_taps.restype = c_int
     lib.mz_blur.argtypes = [POINTER(MzImageView), POINTER(MzImageView), c_int, c_int, c_int, c_int, c_double, c_void_p]
     lib.mz_blur.restype = c_int
     lib.mz_noise.argtypes = [POINTER(MzImageView), POINTER(MzImageView), c_int, c_int, c_int, c_int, c_double, c_uint64, c_uint64, c_void_p]
@@ -259,6 +265,22 @@ def resize_taps(n_in: int, n_out: int, filter_: int, i: int):
     if count < 0:
         check(count)
     return int(first.value), [float(w[j]) for j in range(count)]
+
+
+def interpolate(x_ptr, x_strides, out_ptr, out_strides, elem, B, Hin, Win, Hout, Wout, mode, clamp, window, stream) -> None:
+    """mz_interpolate: the two views and the window as for `resize`; `mode` 0 nearest, 1 bilinear, 2 bicubic (A = -0.75); no workspace."""
+    xv, ov = view(x_ptr, x_strides), view(out_ptr, out_strides)
+    win = (c_int32 * 4)(*[int(v) for v in window]) if window is not None else None
+    check(lib().mz_interpolate(byref(xv), byref(ov), int(elem), B, Hin, Win, Hout, Wout, int(mode), int(bool(clamp)), win, c_void_p(stream)))
+
+
+def interp_taps(n_in: int, n_out: int, mode: int, i: int):
+    """mz_debug_interp_taps (host only): ([idx_0 ..], [w_0 ..]) of output index i of one axis, 1, 2 or 4 taps."""
+    idx, w = (c_int * 4)(), (c_double * 4)()
+    count = lib().mz_debug_interp_taps(n_in, n_out, int(mode), i, idx, w)
+    if count < 0:
+        check(count)
+    return [int(idx[j]) for j in range(count)], [float(w[j]) for j in range(count)]
 
 
 def blur(x_ptr, x_strides, out_ptr, out_strides, elem, B, H, W, sigma, stream) -> None:

@@ -1,11 +1,12 @@
-// Stateless image entry points of libmewzoom_hip.so: image-quality metrics, antialiased resizing, the degradation chain, the dihedral
-// transforms with the self-ensemble accumulator, and the
+// Stateless image entry points of libmewzoom_hip.so: image-quality metrics, antialiased resizing, plain interpolation, the degradation
+// chain, the dihedral transforms with the self-ensemble accumulator, and the
 // host-only mz_debug_* views of what their kernels are handed.  Every check comes before anything touches the GPU.
 #include <cstring>
 
 #include "mz_degrade.h"
 #include "mz_dihedral.h"
 #include "mz_err.h"
+#include "mz_interp.h"
 #include "mz_metrics.h"
 #include "mz_resize.h"
 
@@ -15,6 +16,16 @@ using namespace mz;
 template <class Launch> static int launched(const char* what, Launch launch) {
     if (int rc = device_cus(); rc < 0) return rc;
     return hip_rc(launch(), what);
+}
+
+// the two byte ranges of a call, each from its own shape (mz_interpolate, mz_dihedral, the ensemble entries)
+static int check_ranges_apart(const mz_image_view* a, int elem_a, int Ha, int Wa, const mz_image_view* b, int elem_b, int Hb, int Wb, int B,
+                              const char* what) {
+    long long al, ah, bl, bh;
+    if (!view_extent(a, elem_a, B, Ha, Wa, &al, &ah) || !view_extent(b, elem_b, B, Hb, Wb, &bl, &bh))
+        return fail(MZ_ERR_INVALID_ARGUMENT, "a view's byte range does not fit in 63 bits");
+    if (al < bh && bl < ah) return fail(MZ_ERR_INVALID_ARGUMENT, "%s overlap: this entry does not work in place", what);
+    return MZ_OK;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -112,6 +123,46 @@ extern "C" int mz_debug_resize_taps(int n_in, int n_out, int filter, int i, int*
 }
 
 // ------------------------------------------------------------------------------------------------
+// plain interpolation to any size (mz_interp.h): the model's own skip (model.py:71, 156) and the bicubic baseline of the reference's
+// validate.py:84-118.  Stateless like mz_resize, no workspace.  Every check comes before anything touches the GPU.
+// ------------------------------------------------------------------------------------------------
+static int check_interp_shape(int n_in_h, int n_in_w, int n_out_h, int n_out_w, int mode) {
+    if (mode != IM_NEAREST && mode != IM_BILINEAR && mode != IM_BICUBIC)
+        return fail(MZ_ERR_INVALID_ARGUMENT, "mode must be 0 (nearest), 1 (bilinear) or 2 (bicubic), got %d", mode);
+    if (n_in_h < 1 || n_in_w < 1 || n_out_h < 1 || n_out_w < 1)
+        return fail(MZ_ERR_INVALID_ARGUMENT, "need sizes >= 1 (got %d x %d -> %d x %d)", n_in_h, n_in_w, n_out_h, n_out_w);
+    if (n_in_h > (1 << 28) || n_in_w > (1 << 28) || n_out_h > (1 << 28) || n_out_w > (1 << 28))
+        return fail(MZ_ERR_INVALID_ARGUMENT, "at most 2^28 pixels a side (got %d x %d -> %d x %d)", n_in_h, n_in_w, n_out_h, n_out_w);
+    return MZ_OK;
+}
+
+extern "C" int mz_interpolate(const mz_image_view* x, const mz_image_view* out, int elem, int B, int Hin, int Win, int Hout, int Wout, int mode,
+                              int clamp, const int32_t window[4], void* hip_stream) {
+    static const ViewRules rules = {3, MZ_ELEM_NAMES_0_3, /*second_is_output*/ true, /*batch_bound*/ true, /*side_bound*/ false};
+    InterpArgs a = {};
+    if (const Refusal r = check_views(x, out, rules, elem, B, Hout, Wout, &a.x, &a.out)) return fail(r);
+    if (int rc = check_interp_shape(Hin, Win, Hout, Wout, mode)) return rc;
+    if (const Refusal r = check_window(window, Hout, Wout, &a.y0, &a.x0, &a.h, &a.w)) return fail(r);
+    if (int rc = check_ranges_apart(x, elem, Hin, Win, out, elem, a.h, a.w, B, "x and out")) return rc;
+    if (mode == IM_NEAREST && clamp != 0)  // (the last check: nearest moves bit patterns, a clamp would change them)
+        return fail(MZ_ERR_INVALID_ARGUMENT, "clamp with mode 0 (nearest): nearest moves elements and never changes them");
+    a.elem = elem;
+    a.B = B;
+    a.Hin = Hin; a.Win = Win; a.Hout = Hout; a.Wout = Wout;
+    a.mode = mode;
+    a.clamp = clamp != 0;
+    return launched("interpolate launch", [&] { return (hipError_t)launch_interp(a, hip_stream); });
+}
+
+// Host only: interp_taps() (mz_interp.h) of one output index, the source the kernels compile too
+extern "C" int mz_debug_interp_taps(int n_in, int n_out, int mode, int i, int idx[4], double w[4]) {
+    if (!idx || !w) return fail(MZ_ERR_INVALID_ARGUMENT, "null argument");
+    if (int rc = check_interp_shape(n_in, 1, n_out, 1, mode)) return rc;
+    if (i < 0 || i >= n_out) return fail(MZ_ERR_INVALID_ARGUMENT, "output index %d is not in [0, %d)", i, n_out);
+    return interp_taps(n_in, n_out, mode, i, idx, w);
+}
+
+// ------------------------------------------------------------------------------------------------
 // the degradation chain (mz_degrade.h): no reference counterpart in model.py; stands in for torchvision's gaussian_blur, gaussian_noise
 // and jpeg as the reference's transforms.py uses them.  Stateless like mz_resize.  Every check comes before anything touches the GPU.
 // ------------------------------------------------------------------------------------------------
@@ -193,16 +244,6 @@ static const ViewRules kDihedralIn = {3, MZ_ELEM_NAMES_0_3, /*second_is_output*/
 
 static int check_orientation(int k) {
     return dihedral_valid(k) ? MZ_OK : fail(MZ_ERR_INVALID_ARGUMENT, "orientation k must be 0..7, got %d", k);
-}
-
-// the two byte ranges of a call, each from its own shape
-static int check_ranges_apart(const mz_image_view* a, int elem_a, int Ha, int Wa, const mz_image_view* b, int elem_b, int Hb, int Wb, int B,
-                              const char* what) {
-    long long al, ah, bl, bh;
-    if (!view_extent(a, elem_a, B, Ha, Wa, &al, &ah) || !view_extent(b, elem_b, B, Hb, Wb, &bl, &bh))
-        return fail(MZ_ERR_INVALID_ARGUMENT, "a view's byte range does not fit in 63 bits");
-    if (al < bh && bl < ah) return fail(MZ_ERR_INVALID_ARGUMENT, "%s overlap: this entry does not work in place", what);
-    return MZ_OK;
 }
 
 // the accumulator of a B x H x W result as a dense float32 view, after the workspace check

@@ -1,0 +1,203 @@
+// gfx950 (MI355X / CDNA4): plain interpolation of image views (mz_interp.h) -- the tile kernel and the launcher of one mz_interpolate() call.
+#include <hip/hip_runtime.h>
+#include <stdlib.h>
+
+#include "mz_interp.h"
+
+namespace mz {
+
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+
+template <int E> constexpr int kElemBytes = E == EL_F32 ? 4 : E == EL_U8 ? 1 : 2;
+template <int E> constexpr int kVec = 16 / kElemBytes<E>;  // elements of one 16-byte store
+
+// an element as it lies in memory, zero-extended to a dword, and back (nearest moves bit patterns)
+template <int E> __device__ __forceinline__ uint32_t ld_raw(const void* base, long long i) {
+    if constexpr (E == EL_F32) return ((const uint32_t*)base)[i];
+    else if constexpr (E == EL_U8) return ((const uint8_t*)base)[i];
+    else return ((const uint16_t*)base)[i];
+}
+template <int E> __device__ __forceinline__ void st_raw(void* base, long long i, uint32_t v) {
+    if constexpr (E == EL_F32) ((uint32_t*)base)[i] = v;
+    else if constexpr (E == EL_U8) ((uint8_t*)base)[i] = (uint8_t)v;
+    else ((uint16_t*)base)[i] = (uint16_t)v;
+}
+template <int E> __device__ __forceinline__ void vec_put(u32x4& v, int e, uint32_t raw) {
+    if constexpr (E == EL_F32) v[e] = raw;
+    else if constexpr (E == EL_U8) v[e >> 2] |= raw << (8 * (e & 3));
+    else v[e >> 1] |= raw << (16 * (e & 1));
+}
+
+// A 16-byte global store with the wait states gfx950 needs behind it PINNED (as store16() of mz_dihedral.hip):
+// the store and `s_nop 1` in one statement, which the scheduler cannot part.  Every 16-byte store of this unit goes through here.
+__device__ __forceinline__ void store16(void* p, const u32x4& v) {
+    asm volatile("global_store_dwordx4 %0, %1, off\n\ts_nop 1" ::"v"(p), "v"(v) : "memory");
+}
+
+// float64 -> float32 rounded to ODD (truncate, then set the last bit when inexact): a following round-to-nearest to a 16-bit type is then
+// the one rounding of the float64 value
+__device__ __forceinline__ float f32_round_odd(double d) {
+    const float f = (float)d;
+    if ((double)f == d || f != f) return f;
+    uint32_t u = __builtin_bit_cast(uint32_t, f);
+    if (fabs((double)f) > fabs(d)) u -= 1;  // towards zero (|f| > |d| >= 0: f is not a zero)
+    return __builtin_bit_cast(float, u | 1u);
+}
+
+// the one rounding of a result to the stored element, as its raw bits
+template <int E> __device__ __forceinline__ uint32_t finish_raw(double v, int clamp) {
+#pragma clang fp contract(off)
+    if constexpr (E == EL_U8) {
+        v = fmin(fmax(v, 0.0), 1.0);
+        return (uint32_t)(uint8_t)(v * 255.0 + 0.5);
+    } else {
+        if (clamp) v = fmin(fmax(v, 0.0), 1.0);
+        if constexpr (E == EL_F32) return __builtin_bit_cast(uint32_t, (float)v);
+        else if constexpr (E == EL_BF16) return __builtin_bit_cast(uint16_t, (__bf16)f32_round_odd(v));
+        else return __builtin_bit_cast(uint16_t, (_Float16)f32_round_odd(v));
+    }
+}
+
+// grid: tiles * 3 * B workgroups, tile fastest (tiles of the WINDOW, row by row).  vec: the output view is dense with 16-byte aligned
+// rows (the launcher's finding); stage: the separable path is allowed (enlarging on both axes, no debug knob)
+template <int E, int MODE>
+__global__ __launch_bounds__(kInterpThreads) void interp_kernel(const StridedView x, const StridedView out, int Hin, int Win, int Hout, int Wout,
+                                                                 int y0, int x0, int h, int w, long long tiles, int tiles_x, int clamp, int vec,
+                                                                 int stage) {
+    constexpr int TH = kInterpTileH, TW = kInterpTileW, NT = kInterpThreads, SR = kInterpStageRows;
+    constexpr int K = interp_count(MODE), V = kVec<E>, CPR = TW / V;  // taps an axis; elements and chunks of 16 bytes a tile row
+    constexpr bool kFilter = MODE != IM_NEAREST;
+    static_assert((TW & (TW - 1)) == 0 && TW % 16 == 0, "a tile row is whole 16-byte chunks of every element type");
+    __shared__ int ci[K * TW], ri[K * TH];                                // the tile's taps, tap-major
+    __shared__ double cw[kFilter ? K * TW : 1], rw[kFilter ? K * TH : 1];
+    // the horizontal sums, [source row - rmin][element of a chunk][chunk] with one double of padding behind every element's chunks: the
+    // lanes of the output phase, one chunk each, read neighbouring doubles (no bank conflict), and the lanes of the horizontal phase, along
+    // the columns, write at a pitch that is odd
+    constexpr int HP = CPR + 1, ROWP = V * HP;
+    __shared__ double hrow[kFilter ? SR * ROWP : 1];
+    auto hslot = [](int r, int cc) { return r * ROWP + (cc % V) * HP + cc / V; };
+    const int tid = threadIdx.x;
+    const long long wg = blockIdx.x;
+    const long long plane = wg / tiles;  // b * 3 + c
+    const int tile = (int)(wg - plane * tiles);
+    const long long b = plane / 3, c = plane - b * 3;
+    const int tile_y = tile / tiles_x, tile_x = tile - tile_y * tiles_x;
+    const int i0 = tile_y * TH, j0 = tile_x * TW;  // inside the window
+    const int th = min(TH, h - i0), tw = min(TW, w - j0);
+
+    // ---- the taps of the tile's columns and rows ----
+    for (int t = tid; t < TW + TH; t += NT) {
+        const bool col = t < TW;
+        const int l = col ? t : t - TW;
+        if (l >= (col ? tw : th)) continue;
+        int idx[4];
+        double wt[4];
+        interp_taps(col ? Win : Hin, col ? Wout : Hout, MODE, (col ? x0 + j0 : y0 + i0) + l, idx, wt);
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+            if (col) ci[k * TW + l] = idx[k];
+            else ri[k * TH + l] = idx[k];
+            if constexpr (kFilter) {
+                if (col) cw[k * TW + l] = wt[k];
+                else rw[k * TH + l] = wt[k];
+            }
+        }
+    }
+    __syncthreads();
+
+    const long long sbase = b * x.s[0] + c * x.s[1];
+    // h[row] of tile column cc: the horizontal sum of one source row
+    auto hsum = [&](int row, int cc) -> double {
+        double wk[K], vk[K];
+        const long long at = sbase + (long long)row * x.s[2];
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+            wk[k] = cw[k * TW + cc];
+            vk[k] = ld_f64<E>(x.data, at + (long long)ci[k * TW + cc] * x.s[3]);
+        }
+        return interp_dot<K>(wk, vk);
+    };
+
+    // ---- the separable path: the horizontal sums of the source rows [rmin, rmin + nr) under the tile, into LDS ----
+    bool staged = false;
+    int rmin = 0;
+    if constexpr (kFilter) {
+        rmin = ri[0];                                   // taps grow with the output index: the first row's first, the last row's last
+        const int nr = ri[(K - 1) * TH + th - 1] - rmin + 1;
+        staged = stage != 0 && nr <= SR;                // the same for every thread of the workgroup
+        if (staged) {
+#pragma unroll 2
+            for (int it = tid; it < nr * TW; it += NT) {
+                const int r = it / TW, cc = it & (TW - 1);
+                if (cc < tw) hrow[hslot(r, cc)] = hsum(rmin + r, cc);
+            }
+        }
+        __syncthreads();
+    }
+
+    // ---- the outputs: a lane takes 16 bytes of consecutive elements of one row ----
+    const long long obase = b * out.s[0] + c * out.s[1];
+    for (int ch = tid; ch < TH * CPR; ch += NT) {
+        const int di = ch / CPR, dj = (ch - di * CPR) * V;
+        if (di >= th || dj >= tw) continue;
+        int rows[K];   // the row's taps, once for the chunk
+        [[maybe_unused]] double wk[K];
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+            rows[k] = ri[k * TH + di];
+            if constexpr (kFilter) wk[k] = rw[k * TH + di];
+        }
+        auto value = [&](int cc) -> uint32_t {  // the stored bits of the tile's output (di, cc)
+            if constexpr (!kFilter) {
+                return ld_raw<E>(x.data, sbase + (long long)rows[0] * x.s[2] + (long long)ci[cc] * x.s[3]);
+            } else {
+                double hk[K];
+#pragma unroll
+                for (int k = 0; k < K; ++k) hk[k] = staged ? hrow[hslot(rows[k] - rmin, cc)] : hsum(rows[k], cc);
+                return finish_raw<E>(interp_dot<K>(wk, hk), clamp);
+            }
+        };
+        const long long at = obase + (long long)(i0 + di) * out.s[2] + (long long)(j0 + dj) * out.s[3];  // (out.data: the window's corner)
+        if (vec && dj + V <= tw) {  // (out.s[3] == 1; j0 and dj are multiples of the chunk: aligned once base and strides are)
+            u32x4 v = {0u, 0u, 0u, 0u};
+#pragma unroll
+            for (int e = 0; e < V; ++e) vec_put<E>(v, e, value(dj + e));
+            store16((char*)out.data + at * kElemBytes<E>, v);
+        } else {
+            for (int e = 0; e < V && dj + e < tw; ++e) st_raw<E>((void*)out.data, at + (long long)e * out.s[3], value(dj + e));
+        }
+    }
+}
+
+// every address of a [B,3,H,*] view's rows is a multiple of 16 bytes: the base and the strides of the dimensions that have a second step
+static bool rows_aligned16(const StridedView& v, int B, int H, int elem_bytes) {
+    if ((uintptr_t)v.data % 16) return false;
+    const long long per = 16 / elem_bytes;
+    return (B == 1 || v.s[0] % per == 0) && v.s[1] % per == 0 && (H == 1 || v.s[2] % per == 0);
+}
+
+template <int E, int MODE> static hipError_t launch_interp_em(const InterpArgs& a, hipStream_t s) {
+    const int tiles_x = (a.w + kInterpTileW - 1) / kInterpTileW, tiles_y = (a.h + kInterpTileH - 1) / kInterpTileH;
+    const long long tiles = (long long)tiles_x * tiles_y;
+    if (tiles <= 0 || tiles > 0x7fffffffLL / (3LL * a.B)) return hipErrorInvalidValue;
+    const int vec = a.out.s[3] == 1 && rows_aligned16(a.out, a.B, a.h, kElemBytes<E>) ? 1 : 0;
+    const int stage = a.Hin <= a.Hout && a.Win <= a.Wout && getenv("MZ_INTERP_GATHER") == nullptr ? 1 : 0;
+    hipLaunchKernelGGL((interp_kernel<E, MODE>), dim3((unsigned)(tiles * 3 * a.B)), dim3(kInterpThreads), 0, s, a.x, a.out, a.Hin, a.Win, a.Hout,
+                       a.Wout, a.y0, a.x0, a.h, a.w, tiles, tiles_x, a.clamp, vec, stage);
+    return hipGetLastError();
+}
+
+int launch_interp(const InterpArgs& a, void* hip_stream) {
+    return (int)for_elem(a.elem, [&](auto e) {
+        constexpr int E = decltype(e)::value;
+        const hipStream_t s = (hipStream_t)hip_stream;
+        switch (a.mode) {
+            case IM_NEAREST: return launch_interp_em<E, IM_NEAREST>(a, s);
+            case IM_BILINEAR: return launch_interp_em<E, IM_BILINEAR>(a, s);
+            case IM_BICUBIC: return launch_interp_em<E, IM_BICUBIC>(a, s);
+            default: return hipErrorInvalidValue;
+        }
+    });
+}
+
+}  // namespace mz

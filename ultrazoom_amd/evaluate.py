@@ -162,14 +162,36 @@ class VIF:
         return self.total / self.n if self.n else float("nan")
 
 
+def _bicubic_keys(res: dict) -> dict:
+    return {"bicubic_" + k: res[k] for k in ("psnr", "ssim", "vif")}
+
+
+def bicubic_baseline(x: Tensor, size, backend: str = "torch") -> Tensor:
+    """The baseline the reference's validate.py:84-118 measures next to every result: `x` enlarged to `size` = (H, W) with plain bicubic
+    interpolation (A = -0.75, no antialiasing: the model's own skip connection), clamped to [0, 1].  `backend="torch"`: `F.interpolate`
+    wherever the tensor lives, in float64 like every computation of this file, rounded once to x's dtype (uint8: v / 255 in, clamp ->
+    * 255 + 0.5 -> truncate out) -- the checker of the kernel; `backend="hip"`: the library's kernel (`ultrazoom_amd.interpolate`, CUDA
+    tensors only), which accumulates in float64 and rounds once, too."""
+    size = tuple(int(v) for v in size)
+    if backend == "hip":
+        from .interpolate import interpolate
+
+        return interpolate(x, size=size, mode="bicubic", clamp=True)
+    u8 = x.dtype == torch.uint8
+    y = F.interpolate(x.double() / 255 if u8 else x.double(), size=size, mode="bicubic", align_corners=False).clamp(0, 1)
+    return torch.floor(y * 255 + 0.5).to(torch.uint8) if u8 else y.to(x.dtype)
+
+
 @torch.inference_mode()
-def evaluate(model, pairs: Iterable[Tuple[Tensor, Tensor]], backend: str = "torch", ensemble: int = 1) -> dict:
+def evaluate(model, pairs: Iterable[Tuple[Tensor, Tensor]], backend: str = "torch", ensemble: int = 1, baseline: bool = False) -> dict:
     """`pairs` yields (low-resolution input, high-resolution target) batches already on the model's device/dtype;
     returns {"psnr": ..., "ssim": ..., "vif": ..., "images": n} as the reference's test loop accumulates them (pretrain.py:301-329;
     "vif" is None when the images are smaller than the 41 x 41 pixels the metric needs).  `backend="torch"`: the functions above,
     wherever the tensors live; `backend="hip"`: the same metrics from the library's kernels (`ultrazoom_amd.metrics`, CUDA tensors
     only), accumulated on the device and read once at the end.  `ensemble` = 2, 4 or 8: the predictions are the self-ensemble of that
-    many orientations (`ultrazoom_amd.ensemble.upscale_ensemble`, CUDA tensors only); 1 is the plain `model.upscale`."""
+    many orientations (`ultrazoom_amd.ensemble.upscale_ensemble`, CUDA tensors only); 1 is the plain `model.upscale`.  `baseline=True`:
+    the result also holds "bicubic_psnr", "bicubic_ssim" and "bicubic_vif", the same metrics of `bicubic_baseline(x, y's size, backend)`
+    against y, accumulated beside the others (on the device with `backend="hip"`: nothing is read inside the loop)."""
     if backend not in ("torch", "hip"):
         raise ValueError(f"backend is 'torch' or 'hip', got {backend!r}")
     predict = model.upscale
@@ -183,22 +205,28 @@ def evaluate(model, pairs: Iterable[Tuple[Tensor, Tensor]], backend: str = "torc
     if backend == "hip":
         from .metrics import MetricsAccumulator
 
-        acc = MetricsAccumulator(1.0)
+        acc, base = MetricsAccumulator(1.0), MetricsAccumulator(1.0)
         n = 0
         for x, y in pairs:
             acc.update(predict(x), y)
+            if baseline:
+                base.update(bicubic_baseline(x, y.shape[-2:], "hip"), y)
             n += x.shape[0]
-        return {**acc.compute(), "images": n}
-    psnr, ssim, vif = PSNR(1.0), SSIM(), VIF()
+        res = {**acc.compute(), "images": n}
+        return {**res, **_bicubic_keys(base.compute())} if baseline else res
+    meters = [(PSNR(1.0), SSIM(), VIF())] + ([(PSNR(1.0), SSIM(), VIF())] if baseline else [])
     n = 0
     for x, y in pairs:
-        sr = predict(x)
-        psnr.update(sr, y)
-        ssim.update(sr, y)
-        if min(y.shape[-2:]) >= 41:
-            vif.update(sr, y)
+        images = [predict(x)] + ([bicubic_baseline(x, y.shape[-2:])] if baseline else [])
+        for (psnr, ssim, vif), img in zip(meters, images):
+            psnr.update(img, y)
+            ssim.update(img, y)
+            if min(y.shape[-2:]) >= 41:
+                vif.update(img, y)
         n += x.shape[0]
-    return {"psnr": psnr.compute(), "ssim": ssim.compute(), "vif": vif.compute() if vif.n else None, "images": n}
+    out = [{"psnr": psnr.compute(), "ssim": ssim.compute(), "vif": vif.compute() if vif.n else None} for psnr, ssim, vif in meters]
+    res = {**out[0], "images": n}
+    return {**res, **_bicubic_keys(out[1])} if baseline else res
 
 
 _INTERP_MODES = ("bicubic", "bilinear")
@@ -229,7 +257,7 @@ def lr_from_hr(hr: Tensor, ratio: int, filter: str = "bicubic", backend: str = "
 
 
 def evaluate_hr(model, hr_batches: Iterable[Tensor], *, filter: str = "bicubic", backend: str = "torch", degrade=None,
-                ensemble: int = 1) -> dict:
+                ensemble: int = 1, baseline: bool = False) -> dict:
     """`evaluate` on high-resolution batches alone: each is turned into its (LR, HR) pair by `lr_from_hr` at the model's ratio.  With
     `backend="hip"` the chain HR -> LR -> upscale -> metrics stays on the device and is read once, at the end.
 
@@ -240,21 +268,24 @@ def evaluate_hr(model, hr_batches: Iterable[Tensor], *, filter: str = "bicubic",
     accumulated on the device and read with the image metrics.
 
     `ensemble` as for `evaluate`; with `degrade` the clamped SR is the self-ensemble and the quality head still runs once, on the
-    degraded input as it is."""
+    degraded input as it is.
+
+    `baseline` as for `evaluate`: the "bicubic_*" metrics of the low-resolution input (with `degrade`: the degraded one) enlarged to the
+    target's size with plain bicubic interpolation."""
     if degrade is None:
-        return evaluate(model, (lr_from_hr(hr, model.upscale_ratio, filter, backend) for hr in hr_batches), backend, ensemble)
+        return evaluate(model, (lr_from_hr(hr, model.upscale_ratio, filter, backend) for hr in hr_batches), backend, ensemble, baseline)
     if backend != "hip":
         raise ValueError("degrade runs on the device only: use backend='hip'. There is no CPU path.")
     if ensemble not in (1, 2, 4, 8):
         raise ValueError(f"ensemble is 1, 2, 4 or 8 orientations, got {ensemble}")
-    return _evaluate_degraded(model, hr_batches, degrade, int(ensemble))
+    return _evaluate_degraded(model, hr_batches, degrade, int(ensemble), bool(baseline))
 
 
 @torch.inference_mode()
-def _evaluate_degraded(model, hr_batches: Iterable[Tensor], degrade, ensemble: int = 1) -> dict:
+def _evaluate_degraded(model, hr_batches: Iterable[Tensor], degrade, ensemble: int = 1, baseline: bool = False) -> dict:
     from .metrics import MetricsAccumulator
 
-    acc = MetricsAccumulator(1.0)
+    acc, base = MetricsAccumulator(1.0), MetricsAccumulator(1.0)
     sq, count, n = None, 0, 0
     for hr in hr_batches:
         lr, target, want = degrade.apply(hr, model.upscale_ratio, index=n)
@@ -266,11 +297,14 @@ def _evaluate_degraded(model, hr_batches: Iterable[Tensor], degrade, ensemble: i
 
             qa = model.predict_degredation(lr)
             acc.update(upscale_ensemble(model, lr, n=ensemble), target)
+        if baseline:
+            base.update(bicubic_baseline(lr, target.shape[-2:], "hip"), target)
         d = qa.double() - want.double()
         sq = (d * d).sum() if sq is None else sq + (d * d).sum()
         count += d.numel()
         n += hr.shape[0]
+    extra = _bicubic_keys(base.compute()) if baseline else {}  # (a second read, still after the loop)
     if sq is None:
-        return {**acc.compute(), "deg_l2": float("nan"), "images": 0}
+        return {**acc.compute(), "deg_l2": float("nan"), "images": 0, **extra}
     res, (total,) = acc.compute(extra=sq.reshape(1))  # the one read of the run
-    return {**res, "deg_l2": total / count, "images": n}
+    return {**res, "deg_l2": total / count, "images": n, **extra}

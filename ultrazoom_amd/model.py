@@ -413,6 +413,17 @@ class MewZoom(nn.Module, PyTorchModelHubMixin):
 
         return upscale_ensemble(self, x, n=n, out=out, tile=tile)
 
+    @torch.inference_mode()
+    def upscale_and_bicubic(self, x: Tensor) -> Tuple[Tensor, Tensor]:
+        """``(sr, bicubic)``: ``upscale(x)`` (``upscale_uint8(x)`` for uint8 tensors) together with the plain bicubic enlargement of ``x``
+        by the model's ratio, clamped to [0, 1] -- ``ultrazoom_amd.interpolate(x, scale_factor=r, mode="bicubic", clamp=True)``, the
+        model's own skip connection (model.py:71, 156) as an image.  The pair the reference's validate.py:97 asks the model for and
+        measures side by side; v0.3.0's model.py no longer has the method.  Both results have the bits of their separate calls."""
+        from .interpolate import interpolate
+
+        sr = self.upscale_uint8(x) if x.dtype == torch.uint8 else self.upscale(x)
+        return sr, interpolate(x, scale_factor=self.upscale_ratio, mode="bicubic", clamp=True)
+
     # ---- checkpoint ingestion (test_compare.py:32-45 of the reference) -------------------------
     def load_training_checkpoint(self, state_dict: Dict[str, Tensor], lora_alpha: Optional[float] = None) -> None:
         """Loads a raw training checkpoint: strips ``_orig_mod.`` prefixes left by torch.compile, bakes weight-norm
