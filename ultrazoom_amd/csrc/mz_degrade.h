@@ -8,7 +8,11 @@
 //   the host (at most 31 weights: they travel as a kernel argument);  separable, reflect padding without edge repeat (index -i -> i,
 //   n - 1 + i -> n - 1 - i), per channel plane.  One workgroup of 256 threads = one 32 x 32 output tile of one plane: the haloed input
 //   tile is staged in LDS as float32 (exact for every element type), the horizontal pass runs LDS -> LDS (float32 intermediate, as
-//   resize_kernel's), the vertical pass LDS -> store.  Both passes accumulate in FLOAT64 with fma in ascending j.  k = 1 is a copy.
+//   resize_kernel's), the vertical pass LDS -> store.  Both passes accumulate in FLOAT64 as acc = fma(w_j, v_j, acc) from acc = +0 in
+//   ascending j.  THE LAST STEP (st_f64, mz_view.h): the second sum is stored as (float)acc for float32, as u8_of_unit((float)acc) for
+//   uint8, and rounded ONCE, from float64, to a 16-bit type (not through float32: resize_kernel's 16-bit results are rounded twice,
+//   this kernel's never were).  No clamp.  k = 1 runs the same two passes with the one weight 1.0: every value comes back, a -0 as +0
+//   (fma(1, -0, +0)).  tests/test_image_exact_gpu.py holds the kernel to this statement bit for bit.
 //
 // NOISE (noise_kernel): out = clamp(x + sigma n, 0, 1) in float64, one thread per element.  THE STREAM (stated here, once):
 //   Philox4x32-10 (Salmon et al., SC'11): multipliers 0xD2511F53, 0xCD9E8D57; key bumps (Weyl) 0x9E3779B9, 0xBB67AE85;
@@ -173,7 +177,7 @@ __global__ __launch_bounds__(kDegradeThreads) void blur_kernel(const StridedView
         for (int r = ty; r < th; r += kDegradeThreads / T) {
             double acc = 0.0;
             for (int j = 0; j < k; ++j) acc = fma(wl[j], (double)hrow[(r + j) * T + tx], acc);
-            st_f32<E>((void*)out.data, b * out.s[0] + c * out.s[1] + (long long)(y0 + r) * out.s[2] + (long long)(x0 + tx) * out.s[3], (float)acc, 0);
+            st_f64<E>((void*)out.data, b * out.s[0] + c * out.s[1] + (long long)(y0 + r) * out.s[2] + (long long)(x0 + tx) * out.s[3], acc);
         }
 }
 

@@ -34,17 +34,7 @@ __device__ __forceinline__ void store16(void* p, const u32x4& v) {
     asm volatile("global_store_dwordx4 %0, %1, off\n\ts_nop 1" ::"v"(p), "v"(v) : "memory");
 }
 
-// float64 -> float32 rounded to ODD (truncate, then set the last bit when inexact): a following round-to-nearest to a 16-bit type is then
-// the one rounding of the float64 value
-__device__ __forceinline__ float f32_round_odd(double d) {
-    const float f = (float)d;
-    if ((double)f == d || f != f) return f;
-    uint32_t u = __builtin_bit_cast(uint32_t, f);
-    if (fabs((double)f) > fabs(d)) u -= 1;  // towards zero (|f| > |d| >= 0: f is not a zero)
-    return __builtin_bit_cast(float, u | 1u);
-}
-
-// the one rounding of a result to the stored element, as its raw bits
+// the one rounding of a result to the stored element, as its raw bits (f32_round_odd: mz_view.h)
 template <int E> __device__ __forceinline__ uint32_t finish_raw(double v, int clamp) {
 #pragma clang fp contract(off)
     if constexpr (E == EL_U8) {

@@ -11,7 +11,10 @@
 //   triangle (interp 2).
 // The filter is separable: horizontal pass, then vertical pass.  Both passes accumulate in FLOAT64 with fma in ascending j, from the double
 // weights as they are (the inputs are exact in it); the intermediate between the passes is float32 and is never rounded to the storage
-// type.  Float32 accumulation (about 1e-7 absolute on [0, 1] images) would meet the float32 bound but not "one ulp of the storage type"
+// type.  THE LAST STEP: the second sum is rounded to float32, (float)acc, and that float32 goes through st_f32 (mz_view.h): the clamp, then
+// nothing more for float32, the cast to a 16-bit type -- a SECOND rounding: float64 -> float32 -> 16 bits, not the one rounding of
+// mz_interp.h -- or u8_of_unit.  A uint8 input is read as the float32 quotient v / 255.0f.  tests/test_image_exact_gpu.py holds the
+// kernel to this statement bit for bit.  Float32 accumulation (about 1e-7 absolute on [0, 1] images) would meet the float32 bound but not "one ulp of the storage type"
 // where a bicubic result of a 16-bit type comes close to zero, the ulp shrinking with the value (EXPERIMENTS.md, resize entry).
 //
 //   resize_table_kernel  one thread per output column / row: {first, count} and the weights of both axes, into the caller's workspace (no

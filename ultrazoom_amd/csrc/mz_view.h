@@ -20,7 +20,9 @@ enum Elem : int { EL_F32 = 0, EL_BF16 = 1, EL_F16 = 2, EL_U8 = 3, EL_F64 = 4 };
 #ifdef __HIPCC__
 #include <type_traits>
 
-// the uint8 contract in float32
+// the uint8 contract in float32.  v * 255.0f + 0.5f is compiled to one v_fma_f32; a product rounded before the sum (the host's and the
+// tests' restatements) gives the same byte for every float32 within 64 ulps of each threshold (k - 0.5) / 255 and for every value the
+// exact image tests store: tests/test_image_exact_cpu.py::test_uint8_store_rule_fused_and_unfused_give_the_same_bytes
 __device__ __forceinline__ float unit_of_u8(int v) { return (float)v / 255.0f; }
 __device__ __forceinline__ uint8_t u8_of_unit(float v) { return (uint8_t)fminf(fmaxf(v * 255.0f + 0.5f, 0.0f), 255.0f); }
 
@@ -46,6 +48,22 @@ template <int E> __device__ __forceinline__ void st_f32(void* base, long long i,
         else if constexpr (E == EL_BF16) ((__bf16*)base)[i] = (__bf16)v;
         else ((_Float16*)base)[i] = (_Float16)v;
     }
+}
+// float64 -> float32 rounded to ODD (truncate, then set the last bit when inexact): a following round-to-nearest to a 16-bit type is then
+// the one rounding of the float64 value
+__device__ __forceinline__ float f32_round_odd(double d) {
+    const float f = (float)d;
+    if ((double)f == d || f != f) return f;
+    uint32_t u = __builtin_bit_cast(uint32_t, f);
+    if (fabs((double)f) > fabs(d)) u -= 1;  // towards zero (|f| > |d| >= 0: f is not a zero)
+    return __builtin_bit_cast(float, u | 1u);
+}
+// A float64 sum to the stored element, no clamp: float32 is (float)v and uint8 is u8_of_unit((float)v); a 16-bit type is v rounded ONCE.
+// Written out because the two casts (T16)(float)v do not pin it: behind a clamp that is an argument the compiler rounds twice, as
+// written (resize_kernel), and without one it merges them into the one rounding (what blur_kernel, which calls this, always computed)
+template <int E> __device__ __forceinline__ void st_f64(void* base, long long i, double v) {
+    if constexpr (E == EL_BF16 || E == EL_F16) st_f32<E>(base, i, f32_round_odd(v), 0);
+    else st_f32<E>(base, i, (float)v, 0);
 }
 // v in [0, 1] already
 template <int E> __device__ __forceinline__ void st_f64_unit(void* base, long long i, double v) {
