@@ -294,7 +294,7 @@ def interp_expected(x: torch.Tensor, size, mode: str, dt: str, clamp: int, windo
 
 
 def finish64(v: np.ndarray, dt: str, clamp: int, rule: str) -> torch.Tensor:
-    """finish_raw of mz_interp.hip"""
+    """interp_round_raw of mz_interp.hip"""
     with np.errstate(all="ignore"):
         if dt == "u8":
             t = clamp01(v) * 255.0

@@ -40,6 +40,20 @@ def test_no_file_under_tests_imports_a_test_module():
         assert not found, f"{p} imports from a test module: {found}"
 
 
+def test_no_struct_name_is_defined_in_two_image_headers():
+    """The image headers (mz_view.h and those that include it) put their structs into namespace mz of one shared object: two definitions
+    of one name are one type to the linker (undefined behaviour where they differ), whichever translation units see them."""
+    seen = {}
+    for p in sorted((REPO / "ultrazoom_amd" / "csrc").glob("*.h")):
+        text = p.read_text()
+        if p.name != "mz_view.h" and '#include "mz_view.h"' not in text:
+            continue
+        for name in re.findall(r"^struct\s+(\w+)\s*\{", text, re.M):  # (column 0: namespace scope)
+            assert name not in seen, f"struct {name} is defined in {seen[name]} and in {p.name}"
+            seen[name] = p.name
+    assert {"StridedView", "MetricsFinishArgs", "EnsembleFinishArgs", "InterpArgs", "ResizeArgs", "DegradeArgs", "Refusal"} <= set(seen)
+
+
 def test_the_knob_list_is_what_read_knobs_reads():
     """op_util.set_knobs clears op_cases.KNOBS: a knob read_knobs() (mz_plan.h) reads and the list does not name would leak from the
     environment into every test that pins a kernel."""

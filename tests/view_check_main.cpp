@@ -122,6 +122,53 @@ int main() {
         EXPECT(check_workspace((void*)0x10000, SIZE_MAX, SIZE_MAX).code == MZ_OK);
     }
 
+    // the launchers' helpers of mz_view.h.  2^31 - 1 is prime and a plane-tile grid is a multiple of 3: its largest is 2^31 - 2
+    {
+        EXPECT(grid_ok(1) && grid_ok(INT32_MAX) && !grid_ok(0) && !grid_ok(-1) && !grid_ok((long long)INT32_MAX + 1) && !grid_ok(LLONG_MIN));
+        EXPECT(grid_ok(INT32_MAX, 1) && grid_ok(1, INT32_MAX) && grid_ok(715827882, 3) && !grid_ok(715827883, 3) && !grid_ok(65536, 32768));
+        EXPECT(!grid_ok(LLONG_MAX, LLONG_MAX) && !grid_ok(LLONG_MAX, 2) && !grid_ok(5, 0) && !grid_ok(5, -3));
+        TileGrid g;
+        const int h = 151 * 331, w = 2 * 3 * 7 * 11 * 31;  // h w = (2^31 - 2) / 3
+        EXPECT(plane_tile_grid(h, w, 1, 1, 1, &g) && g.tiles_x == w && g.tiles_y == h && g.tiles == 715827882LL && g.wgs == (long long)INT32_MAX - 1);
+        EXPECT(plane_tile_grid(16 * h - 15, 32 * w, 16, 32, 1, &g) && g.tiles_x == w && g.tiles_y == h && g.wgs == (long long)INT32_MAX - 1);
+        EXPECT(plane_tile_grid(151, w, 1, 1, 331, &g) && g.tiles == 151LL * w && g.wgs == (long long)INT32_MAX - 1);
+        EXPECT(!plane_tile_grid(h + 1, w, 1, 1, 1, &g));           // one more row of tiles
+        EXPECT(!plane_tile_grid(16 * h + 1, 32 * w, 16, 32, 1, &g));
+        EXPECT(!plane_tile_grid(151, w, 1, 1, 332, &g));           // one more image
+        EXPECT(!plane_tile_grid(side, side, 1, 1, 65535, &g));     // 2^56 tiles: refused before anything is multiplied by 3 B
+        EXPECT(!plane_tile_grid(side, side, 1, 1, 1, &g));
+        EXPECT(plane_tile_grid(side, side, 1 << 14, 1 << 14, 2, &g) && g.tiles == 1LL << 28 && g.wgs == 3LL << 29);
+        EXPECT(plane_tile_grid(1, 1, 64, 64, 65535, &g) && g.tiles_x == 1 && g.tiles_y == 1 && g.wgs == 3 * 65535);
+        EXPECT(plane_tile_grid(33, 129, 32, 128, 1, &g) && g.tiles_x == 2 && g.tiles_y == 2 && g.wgs == 12);  // ragged last tiles
+        for (int bad : {INT_MIN, -1, 0}) {
+            EXPECT(!plane_tile_grid(bad, 8, 8, 8, 1, &g) && !plane_tile_grid(8, bad, 8, 8, 1, &g) && !plane_tile_grid(8, 8, 8, 8, bad, &g));
+        }
+        EXPECT(plane_tile_grid(INT_MAX, 1, INT_MAX, INT_MAX, 1, &g) && g.wgs == 3);  // (the rounding up is done in 64 bits)
+
+        // rows_aligned: bf16 elements (2 bytes), 16-byte rows -> strides in multiples of 8 elements
+        const StridedView flipped = {(void*)0x10000, {-64, -16, -8, 1}};  // negative strides are multiples too
+        EXPECT(rows_aligned(flipped, 4, 4, 2, 16));
+        const StridedView odd_row = {(void*)0x10000, {-64, -16, -12, 1}}, odd_image = {(void*)0x10000, {3, 16, 8, 1}}, odd_chan = {(void*)0x10000, {64, 3, 8, 1}};
+        EXPECT(!rows_aligned(odd_row, 4, 4, 2, 16) && rows_aligned(odd_row, 4, 1, 2, 16));     // one row: its stride is never stepped
+        EXPECT(!rows_aligned(odd_image, 2, 4, 2, 16) && rows_aligned(odd_image, 1, 4, 2, 16));  // one image: likewise
+        EXPECT(!rows_aligned(odd_chan, 1, 1, 2, 16));                                            // there are always three channels
+        const StridedView off_base = {(void*)0x10008, {64, 16, 8, 1}};
+        EXPECT(!rows_aligned(off_base, 1, 1, 2, 16) && rows_aligned(off_base, 1, 1, 2, 8) && !rows_aligned(off_base, 4, 4, 4, 16));
+        const StridedView extreme = {(void*)(UINTPTR_MAX - 15), {INT64_MIN, INT64_MAX, INT64_MIN, 1}};
+        EXPECT(!rows_aligned(extreme, 2, 2, 1, 16));  // INT64_MAX is odd
+
+        // dense_view: the strides at the largest sides are exact, and the public checks refuse what 65535 such images would span
+        const StridedView d = dense_view((void*)0x10000, side, side);
+        EXPECT(d.data == (void*)0x10000 && d.s[0] == 3LL << 56 && d.s[1] == 1LL << 56 && d.s[2] == side && d.s[3] == 1);
+        EXPECT((__int128)d.s[0] == (__int128)3 * side * side && d.s[0] < INT64_MAX / 2);
+        const mz_image_view dv = view(0x10000, d.s[0], d.s[1], d.s[2], d.s[3]);
+        long long lo, hi;
+        EXPECT(!view_extent(&dv, 0, 65535, side, side, &lo, &hi));
+        EXPECT(view_extent(&dv, 3, 2, side, side, &lo, &hi) && hi - lo == 6LL << 56);
+        const StridedView small = dense_view(nullptr, 5, 7);
+        EXPECT(small.s[0] == 105 && small.s[1] == 35 && small.s[2] == 7 && small.s[3] == 1);
+    }
+
     if (g_failed) printf("%d expectation(s) failed\n", g_failed);
     else printf("view checks OK\n");
     return g_failed ? 1 : 0;

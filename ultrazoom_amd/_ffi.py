@@ -211,9 +211,35 @@ def check_image_batch(x, what: str, other=None, names=("x", "out")):
     return elem, B, H, W
 
 
+def output_shape(B: int, size, window, size_check=None):
+    """(Hout, Wout, window as a tuple or None, the shape `out` must have) of a call that resamples B images to `size` = (Hout, Wout) and
+    stores `window` = (y0, x0, h, w) of the result, or all of it; size_check(Hout, Wout), an entry's own bound on the size, runs between
+    the two."""
+    size = tuple(int(v) for v in size)
+    if len(size) != 2 or min(size) < 1:
+        raise ValueError(f"size is (Hout, Wout) with both at least 1, got {size}")
+    Hout, Wout = size
+    if size_check is not None:
+        size_check(Hout, Wout)
+    if window is None:
+        return Hout, Wout, None, (B, 3, Hout, Wout)
+    window = tuple(int(v) for v in window)
+    if len(window) != 4:
+        raise ValueError("window is (y0, x0, h, w) in output pixels")
+    y0, x0, h, w = window
+    if h < 1 or w < 1 or y0 < 0 or x0 < 0 or y0 + h > Hout or x0 + w > Wout:
+        raise ValueError(f"window {window} is empty or not inside the {Hout} x {Wout} result")
+    return Hout, Wout, window, (B, 3, h, w)
+
+
 def view(ptr, strides) -> MzImageView:
     """An mz_image_view: the address of element (0, 0, 0, 0) and the element strides (image, channel, row, column; signed)."""
     return MzImageView(c_void_p(ptr), (c_int64 * 4)(*[int(v) for v in strides]))
+
+
+def _window_arg(window):
+    """`window` = (y0, x0, h, w) or None as the `const int32_t window[4]` of an entry."""
+    return (c_int32 * 4)(*[int(v) for v in window]) if window is not None else None
 
 
 def make_config(cfg: dict) -> MzConfig:
@@ -248,7 +274,7 @@ def resize(x_ptr, x_strides, out_ptr, out_strides, elem, B, Hin, Win, Hout, Wout
     """mz_resize: the two views as for Handle.forward_view (out: of the window); `elem` 0..2 = MZ_F32 / MZ_BF16 / MZ_F16, 3 = uint8;
     `window` = (y0, x0, h, w) in pixels of the Hout x Wout result, or None."""
     xv, ov = view(x_ptr, x_strides), view(out_ptr, out_strides)
-    win = (c_int32 * 4)(*[int(v) for v in window]) if window is not None else None
+    win = _window_arg(window)
     check(
         lib().mz_resize(
             byref(xv), byref(ov), int(elem), B, Hin, Win, Hout, Wout, int(filter_), int(bool(clamp)), win, c_void_p(ws_ptr), ws_bytes,
@@ -270,7 +296,7 @@ def resize_taps(n_in: int, n_out: int, filter_: int, i: int):
 def interpolate(x_ptr, x_strides, out_ptr, out_strides, elem, B, Hin, Win, Hout, Wout, mode, clamp, window, stream) -> None:
     """mz_interpolate: the two views and the window as for `resize`; `mode` 0 nearest, 1 bilinear, 2 bicubic (A = -0.75); no workspace."""
     xv, ov = view(x_ptr, x_strides), view(out_ptr, out_strides)
-    win = (c_int32 * 4)(*[int(v) for v in window]) if window is not None else None
+    win = _window_arg(window)
     check(lib().mz_interpolate(byref(xv), byref(ov), int(elem), B, Hin, Win, Hout, Wout, int(mode), int(bool(clamp)), win, c_void_p(stream)))
 
 
@@ -358,7 +384,7 @@ def ensemble_add(y_ptr, y_strides, elem, B, H, W, k, first, ws_ptr, ws_bytes, st
 def ensemble_finish(out_ptr, out_strides, elem, B, H, W, n, clamp, window, ws_ptr, ws_bytes, stream) -> None:
     """mz_ensemble_finish: the mean of the n results added, into out (a view of the window, as for `resize`)."""
     ov = view(out_ptr, out_strides)
-    win = (c_int32 * 4)(*[int(v) for v in window]) if window is not None else None
+    win = _window_arg(window)
     check(lib().mz_ensemble_finish(byref(ov), int(elem), B, H, W, int(n), int(bool(clamp)), win, c_void_p(ws_ptr), ws_bytes, c_void_p(stream)))
 
 
@@ -436,7 +462,7 @@ class Handle:
         """mz_forward_view: `x_ptr` / `out_ptr` address element (0, 0, 0, 0) of each view (out: of the window), the strides count
         elements (image, channel, row, column; signed); `window` = (y0, x0, h, w) in output pixels or None; `elem` 1 = uint8."""
         xv, ov = view(x_ptr, x_strides), view(out_ptr, out_strides)
-        win = (c_int32 * 4)(*[int(v) for v in window]) if window is not None else None
+        win = _window_arg(window)
         check(
             lib().mz_forward_view(
                 self._h, byref(xv), byref(ov), c_void_p(qa_ptr) if qa_ptr else None, B, H, W, int(clamp), int(elem), win,

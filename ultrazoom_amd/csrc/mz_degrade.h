@@ -149,11 +149,9 @@ __global__ __launch_bounds__(kDegradeThreads) void blur_kernel(const StridedView
     __shared__ double wl[2 * kBlurMaxHalf + 1];
     const int tid = threadIdx.x, tx = tid & (T - 1), ty = tid / T;
     const int half = bw.half, k = 2 * half + 1;
-    const long long wg = blockIdx.x;
-    const long long plane = wg / tiles;
-    const int tile = (int)(wg - plane * tiles);
-    const long long b = plane / 3, c = plane - b * 3;
-    const int y0 = (tile / tiles_x) * T, x0 = (tile % tiles_x) * T;
+    const PlaneTile pt = plane_tile(blockIdx.x, tiles, tiles_x);
+    const long long b = pt.b, c = pt.c;
+    const int y0 = pt.ty * T, x0 = pt.tx * T;
     const int th = min(T, H - y0), tw = min(T, W - x0);  // outputs of this tile
     const int rows = th + 2 * half, cols = tw + 2 * half;  // staged input: every index reflects into the image (half < min(H, W))
     if (tid < k) wl[tid] = bw.w[tid];

@@ -5,19 +5,16 @@
 namespace mz {
 
 template <int E> static hipError_t launch_blur_e(const DegradeArgs& a, const BlurWeights& bw, hipStream_t s) {
-    const int tiles_x = (a.W + kBlurTile - 1) / kBlurTile, tiles_y = (a.H + kBlurTile - 1) / kBlurTile;
-    const long long tiles = (long long)tiles_x * tiles_y;
-    const long long wgs = tiles * 3 * a.B;
-    if (wgs <= 0 || wgs > 0x7fffffffLL) return hipErrorInvalidValue;
-    hipLaunchKernelGGL((blur_kernel<E>), dim3((unsigned)wgs), dim3(kDegradeThreads), 0, s, a.x, a.out, a.H, a.W, tiles, tiles_x, bw);
+    TileGrid g;
+    if (!plane_tile_grid(a.H, a.W, kBlurTile, kBlurTile, a.B, &g)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL((blur_kernel<E>), dim3((unsigned)g.wgs), dim3(kDegradeThreads), 0, s, a.x, a.out, a.H, a.W, g.tiles, g.tiles_x, bw);
     return hipGetLastError();
 }
 
 template <int E> static hipError_t launch_noise_e(const DegradeArgs& a, double sigma, unsigned long long seed, unsigned long long offset, hipStream_t s) {
     const long long chunks = (3LL * a.H * a.W + kDegradeThreads - 1) / kDegradeThreads;
-    const long long wgs = chunks * a.B;
-    if (wgs <= 0 || wgs > 0x7fffffffLL) return hipErrorInvalidValue;
-    hipLaunchKernelGGL((noise_kernel<E>), dim3((unsigned)wgs), dim3(kDegradeThreads), 0, s, a.x, a.out, a.H, a.W, chunks, sigma, seed, offset);
+    if (!grid_ok(chunks, a.B)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL((noise_kernel<E>), dim3((unsigned)(chunks * a.B)), dim3(kDegradeThreads), 0, s, a.x, a.out, a.H, a.W, chunks, sigma, seed, offset);
     return hipGetLastError();
 }
 
@@ -27,7 +24,7 @@ template <int E> static hipError_t launch_jpeg_e(const DegradeArgs& a, const Jpe
     const int tiles_x = (pl.Wp / 16 + kJpegMcus - 1) / kJpegMcus;
     const long long tiles = (long long)tiles_x * (pl.Hp / 16);
     const long long chunks = ((long long)a.H * a.W + kDegradeThreads - 1) / kDegradeThreads;
-    if (tiles * a.B <= 0 || tiles * a.B > 0x7fffffffLL || chunks * a.B > 0x7fffffffLL) return hipErrorInvalidValue;
+    if (!grid_ok(tiles, a.B) || !grid_ok(chunks, a.B)) return hipErrorInvalidValue;
     hipLaunchKernelGGL((jpeg_code_kernel<E>), dim3((unsigned)(tiles * a.B)), dim3(kDegradeThreads), 0, s, a.x, a.H, a.W, pl.Hp, pl.Wp, tiles, tiles_x, t,
                        ws_y, ws_c);
     hipError_t e = hipGetLastError();

@@ -74,7 +74,7 @@ struct DihedralArgs {
     int k;                 // dst = T(src, k)
     int first;             // DM_ACC: store (nonzero) or add
 };
-struct FinishArgs {
+struct EnsembleFinishArgs {
     const float* acc;      // dense [B][3][H][W]
     StridedView out;       // the window's view
     int elem, B, H, W;
@@ -83,7 +83,7 @@ struct FinishArgs {
 };
 // hipError_t values (kept as int: this header stays free of HIP types); hipErrorInvalidValue for a grid beyond 2^31 - 1 workgroups
 int launch_dihedral(const DihedralArgs& a, void* hip_stream);
-int launch_ensemble_finish(const FinishArgs& a, void* hip_stream);
+int launch_ensemble_finish(const EnsembleFinishArgs& a, void* hip_stream);
 
 // bytes of the accumulator of B results of H x W pixels; false where that is no size_t worth allocating (beyond 2^62)
 inline bool ensemble_workspace_bytes(int B, int H, int W, size_t* bytes) {

@@ -6,51 +6,18 @@
 
 namespace mz {
 
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-template <int E> constexpr int kElemBytes = E == EL_F32 ? 4 : E == EL_U8 ? 1 : 2;
-template <int E> constexpr int kVec = 16 / kElemBytes<E>;  // elements of one 16-byte access
 
 // how the lanes of a workgroup walk one side of a tile
 enum Walk : int { WALK_COLS = 0, WALK_ROWS = 1, WALK_VEC = 2 };  // one element a lane along columns / along rows; 16 bytes a lane along columns
 
-// an element as it lies in memory, zero-extended to a dword, and back
-template <int E> __device__ __forceinline__ uint32_t ld_raw(const void* base, long long i) {
-    if constexpr (E == EL_F32) return ((const uint32_t*)base)[i];
-    else if constexpr (E == EL_U8) return ((const uint8_t*)base)[i];
-    else return ((const uint16_t*)base)[i];
-}
-template <int E> __device__ __forceinline__ void st_raw(void* base, long long i, uint32_t v) {
-    if constexpr (E == EL_F32) ((uint32_t*)base)[i] = v;
-    else if constexpr (E == EL_U8) ((uint8_t*)base)[i] = (uint8_t)v;
-    else ((uint16_t*)base)[i] = (uint16_t)v;
-}
 // the `value` of the ensemble: the element as float32 (uint8: the raw sample 0..255, not v / 255 -- sums of eight stay exact integers)
 template <int E> __device__ __forceinline__ float value_of(uint32_t raw) {
     if constexpr (E == EL_F32) return __builtin_bit_cast(float, raw);
     else if constexpr (E == EL_BF16) return __builtin_bit_cast(float, raw << 16);
     else if constexpr (E == EL_F16) return (float)__builtin_bit_cast(_Float16, (uint16_t)raw);
     else return (float)raw;
-}
-// element e of a 16-byte vector of kVec<E> elements, and its place in one
-template <int E> __device__ __forceinline__ uint32_t vec_get(const u32x4& v, int e) {
-    if constexpr (E == EL_F32) return v[e];
-    else if constexpr (E == EL_U8) return (v[e >> 2] >> (8 * (e & 3))) & 0xffu;
-    else return (v[e >> 1] >> (16 * (e & 1))) & 0xffffu;
-}
-template <int E> __device__ __forceinline__ void vec_put(u32x4& v, int e, uint32_t raw) {
-    if constexpr (E == EL_F32) v[e] = raw;
-    else if constexpr (E == EL_U8) v[e >> 2] |= raw << (8 * (e & 3));
-    else v[e >> 1] |= raw << (16 * (e & 1));
-}
-
-// A 16-byte global store with the wait states gfx950 needs behind it PINNED (the store reads its data registers
-// late; hipcc pads one wait state, the probe of tests/test_store_hazard_gpu.py wants two): the store and `s_nop 1` in one statement,
-// which the scheduler cannot part.  Every 16-byte store of this unit goes through here; tools/asm_store_hazard.py re-checks the listing.
-__device__ __forceinline__ void store16(void* p, const u32x4& v) {
-    asm volatile("global_store_dwordx4 %0, %1, off\n\ts_nop 1" ::"v"(p), "v"(v) : "memory");
 }
 
 // grid: tiles * 3 * B workgroups, tile fastest (the tiles of the DESTINATION, row by row).  mz_dihedral.h describes the skeleton and
@@ -66,12 +33,9 @@ __global__ __launch_bounds__(kDihedralThreads) void dihedral_kernel(const Stride
     const int tid = threadIdx.x;
     int Hd, Wd;
     dihedral_shape(k, Hs, Ws, &Hd, &Wd);
-    const long long wg = blockIdx.x;
-    const long long plane = wg / tiles;  // b * 3 + c
-    const int tile = (int)(wg - plane * tiles);
-    const long long b = plane / 3, c = plane - b * 3;
-    const int tile_y = tile / tiles_x, tile_x = tile - tile_y * tiles_x;
-    const int i0 = tile_y * T, j0 = tile_x * T;
+    const PlaneTile pt = plane_tile(blockIdx.x, tiles, tiles_x);
+    const long long b = pt.b, c = pt.c;
+    const int i0 = pt.ty * T, j0 = pt.tx * T;
     const int th = min(T, Hd - i0), tw = min(T, Wd - j0);
     // the source rectangle that lands on this tile: [r0, r0 + nr) x [c0, c0 + nc), from the tile's two corners
     int ra, ca, rb, cb;
@@ -177,7 +141,7 @@ __global__ __launch_bounds__(kDihedralThreads) void dihedral_kernel(const Stride
 
 // The finish of one accumulator element as the stored element's raw bits.  Float types: acc * (1 / n) (exact: n is a power of two), the
 // clamp, one rounding to the stored type -- the casts of st_f32 (mz_view.h).  uint8: (2 sum + n) / (2 n) in integers: round half up.
-template <int E> __device__ __forceinline__ uint32_t finish_raw(float a, float inv_n, int n, int log2n, int clamp) {
+template <int E> __device__ __forceinline__ uint32_t ensemble_mean_raw(float a, float inv_n, int n, int log2n, int clamp) {
     if constexpr (E == EL_U8) {
         return (uint32_t)(2 * (int)a + n) >> (log2n + 1);
     } else {
@@ -207,7 +171,7 @@ __global__ __launch_bounds__(kDihedralThreads) void ensemble_finish_kernel(const
     const long long obase = b * out.s[0] + c * out.s[1] + (long long)y * out.s[2];
     const float inv_n = 1.0f / (float)n;
     auto put = [&](int x) {
-        if constexpr (E == EL_U8) st_raw<E>((void*)out.data, obase + (long long)x * out.s[3], finish_raw<E>(arow[x], inv_n, n, log2n, clamp));
+        if constexpr (E == EL_U8) st_raw<E>((void*)out.data, obase + (long long)x * out.s[3], ensemble_mean_raw<E>(arow[x], inv_n, n, log2n, clamp));
         else st_f32<E>((void*)out.data, obase + (long long)x * out.s[3], arow[x] * inv_n, clamp);
     };
     const int xs = seg * kFinishSpan;
@@ -217,7 +181,7 @@ __global__ __launch_bounds__(kDihedralThreads) void ensemble_finish_kernel(const
             const f32x4 a = *(const f32x4*)(arow + x);
             uint32_t r[4];
 #pragma unroll
-            for (int e = 0; e < 4; ++e) r[e] = finish_raw<E>(a[e], inv_n, n, log2n, clamp);
+            for (int e = 0; e < 4; ++e) r[e] = ensemble_mean_raw<E>(a[e], inv_n, n, log2n, clamp);
             char* p = (char*)out.data + (obase + x) * kElemBytes<E>;
             if constexpr (E == EL_F32) store16(p, u32x4{r[0], r[1], r[2], r[3]});
             else if constexpr (E == EL_U8) *(uint32_t*)p = r[0] | r[1] << 8 | r[2] << 16 | r[3] << 24;
@@ -235,12 +199,6 @@ __global__ __launch_bounds__(kDihedralThreads) void ensemble_finish_kernel(const
 }
 
 // ---- launchers ------------------------------------------------------------------------------------------------------------------
-// every address of a [B,3,H,*] view's rows is a multiple of `bytes`: the base and the strides of the dimensions that have a second step
-static bool rows_aligned(const StridedView& v, int B, int H, int elem_bytes, int bytes) {
-    if ((uintptr_t)v.data % bytes) return false;
-    const long long per = bytes / elem_bytes;
-    return (B == 1 || v.s[0] % per == 0) && v.s[1] % per == 0 && (H == 1 || v.s[2] % per == 0);
-}
 static int walk_of(const StridedView& v, int B, int H, int W, int elem_bytes) {
     if (v.s[3] == 1 || W == 1) return v.s[3] == 1 && rows_aligned(v, B, H, elem_bytes, 16) ? WALK_VEC : WALK_COLS;
     return (v.s[2] == 1 || v.s[2] == -1) && H > 1 ? WALK_ROWS : WALK_COLS;
@@ -249,13 +207,12 @@ static int walk_of(const StridedView& v, int B, int H, int W, int elem_bytes) {
 template <int E, int MODE> static hipError_t launch_dihedral_em(const DihedralArgs& a, hipStream_t s) {
     int Hd, Wd;
     dihedral_shape(a.k, a.Hs, a.Ws, &Hd, &Wd);
-    const int tiles_x = (Wd + kDihedralTile - 1) / kDihedralTile, tiles_y = (Hd + kDihedralTile - 1) / kDihedralTile;
-    const long long tiles = (long long)tiles_x * tiles_y;
-    if (tiles > 0x7fffffffLL / (3LL * a.B)) return hipErrorInvalidValue;
+    TileGrid g;
+    if (!plane_tile_grid(Hd, Wd, kDihedralTile, kDihedralTile, a.B, &g)) return hipErrorInvalidValue;
     const int src_walk = walk_of(a.src, a.B, a.Hs, a.Ws, kElemBytes<E>);
     const int dst_walk = walk_of(a.dst, a.B, Hd, Wd, MODE == DM_ACC ? 4 : kElemBytes<E>);
-    hipLaunchKernelGGL((dihedral_kernel<E, MODE>), dim3((unsigned)(tiles * 3 * a.B)), dim3(kDihedralThreads), 0, s, a.src, a.dst, a.Hs, a.Ws, a.k,
-                       a.first, tiles, tiles_x, src_walk, dst_walk);
+    hipLaunchKernelGGL((dihedral_kernel<E, MODE>), dim3((unsigned)g.wgs), dim3(kDihedralThreads), 0, s, a.src, a.dst, a.Hs, a.Ws, a.k, a.first,
+                       g.tiles, g.tiles_x, src_walk, dst_walk);
     return hipGetLastError();
 }
 
@@ -266,12 +223,12 @@ int launch_dihedral(const DihedralArgs& a, void* hip_stream) {
     });
 }
 
-int launch_ensemble_finish(const FinishArgs& a, void* hip_stream) {
+int launch_ensemble_finish(const EnsembleFinishArgs& a, void* hip_stream) {
     return (int)for_elem(a.elem, [&](auto e) {
         constexpr int E = decltype(e)::value;
         const int segs = (a.w + kFinishSpan - 1) / kFinishSpan;
         const long long rows = 3LL * a.B * a.h;
-        if (rows > 0x7fffffffLL / segs) return hipErrorInvalidValue;
+        if (!grid_ok(rows, segs)) return hipErrorInvalidValue;
         int log2n = 0;
         while ((1 << log2n) < a.n) ++log2n;
         const bool vec = a.out.s[3] == 1 && rows_aligned(a.out, a.B, a.h, kElemBytes<E>, 4 * kElemBytes<E>) && (uintptr_t)a.acc % 16 == 0 &&

@@ -28,6 +28,22 @@ static int check_ranges_apart(const mz_image_view* a, int elem_a, int Ha, int Wa
     return MZ_OK;
 }
 
+// the four sizes of a resampling call (mz_resize, mz_interpolate and their mz_debug_*_taps: behind each entry's filter / mode check)
+static int check_sizes(int Hin, int Win, int Hout, int Wout) {
+    if (Hin < 1 || Win < 1 || Hout < 1 || Wout < 1)
+        return fail(MZ_ERR_INVALID_ARGUMENT, "need sizes >= 1 (got %d x %d -> %d x %d)", Hin, Win, Hout, Wout);
+    if (Hin > (1 << 28) || Win > (1 << 28) || Hout > (1 << 28) || Wout > (1 << 28))
+        return fail(MZ_ERR_INVALID_ARGUMENT, "at most 2^28 pixels a side (got %d x %d -> %d x %d)", Hin, Win, Hout, Wout);
+    return MZ_OK;
+}
+
+// the batch of a workspace query that has no views to check (mz_jpeg_workspace_bytes, mz_ensemble_workspace_bytes)
+static int check_batch_bounds(int B, int H, int W) {
+    if (B < 1 || B > 65535 || H < 1 || W < 1 || H > (1 << 28) || W > (1 << 28))
+        return fail(MZ_ERR_INVALID_ARGUMENT, "need 1 <= B <= 65535 and 1 <= H, W <= 2^28 (got %d, %d, %d)", B, H, W);
+    return MZ_OK;
+}
+
 // ------------------------------------------------------------------------------------------------
 // image-quality metrics (mz_metrics.h): no reference counterpart in model.py; stands in for torchmetrics as the reference's
 // pretrain.py:209-211, 301-329 uses it.  Stateless like the mz_op_* entries.
@@ -78,10 +94,7 @@ extern "C" int mz_metrics(const mz_image_view* pred, const mz_image_view* target
 static int check_resize_shape(int Hin, int Win, int Hout, int Wout, int filter) {
     if (filter != RF_BICUBIC && filter != RF_BILINEAR)
         return fail(MZ_ERR_INVALID_ARGUMENT, "filter must be 0 (bicubic) or 1 (bilinear), got %d", filter);
-    if (Hin < 1 || Win < 1 || Hout < 1 || Wout < 1)
-        return fail(MZ_ERR_INVALID_ARGUMENT, "need sizes >= 1 (got %d x %d -> %d x %d)", Hin, Win, Hout, Wout);
-    if (Hin > (1 << 28) || Win > (1 << 28) || Hout > (1 << 28) || Wout > (1 << 28))
-        return fail(MZ_ERR_INVALID_ARGUMENT, "at most 2^28 pixels a side (got %d x %d -> %d x %d)", Hin, Win, Hout, Wout);
+    if (int rc = check_sizes(Hin, Win, Hout, Wout)) return rc;
     if ((long long)Hin > (long long)kResizeMaxRatio * Hout || (long long)Win > (long long)kResizeMaxRatio * Wout)
         return fail(MZ_ERR_INVALID_ARGUMENT, "%d x %d -> %d x %d shrinks an axis by more than %d", Hin, Win, Hout, Wout, kResizeMaxRatio);
     return MZ_OK;
@@ -129,11 +142,7 @@ extern "C" int mz_debug_resize_taps(int n_in, int n_out, int filter, int i, int*
 static int check_interp_shape(int n_in_h, int n_in_w, int n_out_h, int n_out_w, int mode) {
     if (mode != IM_NEAREST && mode != IM_BILINEAR && mode != IM_BICUBIC)
         return fail(MZ_ERR_INVALID_ARGUMENT, "mode must be 0 (nearest), 1 (bilinear) or 2 (bicubic), got %d", mode);
-    if (n_in_h < 1 || n_in_w < 1 || n_out_h < 1 || n_out_w < 1)
-        return fail(MZ_ERR_INVALID_ARGUMENT, "need sizes >= 1 (got %d x %d -> %d x %d)", n_in_h, n_in_w, n_out_h, n_out_w);
-    if (n_in_h > (1 << 28) || n_in_w > (1 << 28) || n_out_h > (1 << 28) || n_out_w > (1 << 28))
-        return fail(MZ_ERR_INVALID_ARGUMENT, "at most 2^28 pixels a side (got %d x %d -> %d x %d)", n_in_h, n_in_w, n_out_h, n_out_w);
-    return MZ_OK;
+    return check_sizes(n_in_h, n_in_w, n_out_h, n_out_w);
 }
 
 extern "C" int mz_interpolate(const mz_image_view* x, const mz_image_view* out, int elem, int B, int Hin, int Win, int Hout, int Wout, int mode,
@@ -195,8 +204,7 @@ extern "C" int mz_noise(const mz_image_view* x, const mz_image_view* out, int el
 
 extern "C" int mz_jpeg_workspace_bytes(int B, int H, int W, size_t* bytes) {
     if (!bytes) return fail(MZ_ERR_INVALID_ARGUMENT, "null argument");
-    if (B < 1 || B > 65535 || H < 1 || W < 1 || H > (1 << 28) || W > (1 << 28))
-        return fail(MZ_ERR_INVALID_ARGUMENT, "need 1 <= B <= 65535 and 1 <= H, W <= 2^28 (got %d, %d, %d)", B, H, W);
+    if (int rc = check_batch_bounds(B, H, W)) return rc;
     *bytes = jpeg_plan(B, H, W).total;
     return MZ_OK;
 }
@@ -246,13 +254,15 @@ static int check_orientation(int k) {
     return dihedral_valid(k) ? MZ_OK : fail(MZ_ERR_INVALID_ARGUMENT, "orientation k must be 0..7, got %d", k);
 }
 
-// the accumulator of a B x H x W result as a dense float32 view, after the workspace check
-static int ensemble_accumulator(int B, int H, int W, void* workspace, size_t workspace_bytes, mz_image_view* acc) {
+// the accumulator of a B x H x W result as a dense float32 view, after the workspace check: for the kernels and, as the public struct,
+// for check_ranges_apart
+static int ensemble_accumulator(int B, int H, int W, void* workspace, size_t workspace_bytes, StridedView* dense, mz_image_view* acc) {
     size_t need = 0;
     if (!ensemble_workspace_bytes(B, H, W, &need)) return fail(MZ_ERR_INVALID_ARGUMENT, "an accumulator of %d x 3 x %d x %d float32 is beyond 2^62 bytes", B, H, W);
     if (const Refusal r = check_workspace(workspace, workspace_bytes, need)) return fail(r);
+    *dense = dense_view(workspace, H, W);
     acc->data = workspace;
-    acc->stride[0] = 3LL * H * W; acc->stride[1] = (long long)H * W; acc->stride[2] = W; acc->stride[3] = 1;
+    for (int i = 0; i < 4; ++i) acc->stride[i] = dense->s[i];
     return MZ_OK;
 }
 
@@ -271,8 +281,7 @@ extern "C" int mz_dihedral(const mz_image_view* x, const mz_image_view* out, int
 
 extern "C" int mz_ensemble_workspace_bytes(int B, int H, int W, size_t* bytes) {
     if (!bytes) return fail(MZ_ERR_INVALID_ARGUMENT, "null argument");
-    if (B < 1 || B > 65535 || H < 1 || W < 1 || H > (1 << 28) || W > (1 << 28))
-        return fail(MZ_ERR_INVALID_ARGUMENT, "need 1 <= B <= 65535 and 1 <= H, W <= 2^28 (got %d, %d, %d)", B, H, W);
+    if (int rc = check_batch_bounds(B, H, W)) return rc;
     if (!ensemble_workspace_bytes(B, H, W, bytes)) return fail(MZ_ERR_INVALID_ARGUMENT, "an accumulator of %d x 3 x %d x %d float32 is beyond 2^62 bytes", B, H, W);
     return MZ_OK;
 }
@@ -284,25 +293,23 @@ extern "C" int mz_ensemble_add(const mz_image_view* y, int elem, int B, int H, i
     if (const Refusal r = check_views(y, y, kDihedralIn, elem, B, H, W, &a.src, &unused)) return fail(r);
     if (int rc = check_orientation(k)) return rc;
     mz_image_view acc;
-    if (int rc = ensemble_accumulator(B, H, W, workspace, workspace_bytes, &acc)) return rc;
+    if (int rc = ensemble_accumulator(B, H, W, workspace, workspace_bytes, &a.dst, &acc)) return rc;
     int Hy, Wy;  // y lies in ITS orientation: T(result, k)
     dihedral_shape(k, H, W, &Hy, &Wy);
     if (int rc = check_ranges_apart(y, elem, Hy, Wy, &acc, EL_F32, H, W, B, "y and the workspace")) return rc;
-    a.dst.data = acc.data;
-    for (int i = 0; i < 4; ++i) a.dst.s[i] = acc.stride[i];
     a.elem = elem; a.mode = DM_ACC; a.B = B; a.Hs = Hy; a.Ws = Wy; a.k = dihedral_inverse(k); a.first = first != 0;
     return launched("ensemble add launch", [&] { return (hipError_t)launch_dihedral(a, hip_stream); });
 }
 
 extern "C" int mz_ensemble_finish(const mz_image_view* out, int elem, int B, int H, int W, int n, int clamp, const int32_t window[4],
                                   void* workspace, size_t workspace_bytes, void* hip_stream) {
-    FinishArgs a = {};
+    EnsembleFinishArgs a = {};
     StridedView unused;
     if (const Refusal r = check_views(out, out, kDihedralOut, elem, B, H, W, &unused, &a.out)) return fail(r);
     if (n != 1 && n != 2 && n != 4 && n != 8) return fail(MZ_ERR_INVALID_ARGUMENT, "n must be 1, 2, 4 or 8 orientations, got %d", n);
     if (const Refusal r = check_window(window, H, W, &a.y0, &a.x0, &a.h, &a.w)) return fail(r);
     mz_image_view acc;
-    if (int rc = ensemble_accumulator(B, H, W, workspace, workspace_bytes, &acc)) return rc;
+    if (int rc = ensemble_accumulator(B, H, W, workspace, workspace_bytes, &unused, &acc)) return rc;
     if (int rc = check_ranges_apart(out, elem, a.h, a.w, &acc, EL_F32, H, W, B, "out and the workspace")) return rc;
     a.acc = (const float*)workspace;
     a.elem = elem; a.B = B; a.H = H; a.W = W; a.n = n; a.clamp = clamp != 0;

@@ -6,36 +6,8 @@
 
 namespace mz {
 
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-
-template <int E> constexpr int kElemBytes = E == EL_F32 ? 4 : E == EL_U8 ? 1 : 2;
-template <int E> constexpr int kVec = 16 / kElemBytes<E>;  // elements of one 16-byte store
-
-// an element as it lies in memory, zero-extended to a dword, and back (nearest moves bit patterns)
-template <int E> __device__ __forceinline__ uint32_t ld_raw(const void* base, long long i) {
-    if constexpr (E == EL_F32) return ((const uint32_t*)base)[i];
-    else if constexpr (E == EL_U8) return ((const uint8_t*)base)[i];
-    else return ((const uint16_t*)base)[i];
-}
-template <int E> __device__ __forceinline__ void st_raw(void* base, long long i, uint32_t v) {
-    if constexpr (E == EL_F32) ((uint32_t*)base)[i] = v;
-    else if constexpr (E == EL_U8) ((uint8_t*)base)[i] = (uint8_t)v;
-    else ((uint16_t*)base)[i] = (uint16_t)v;
-}
-template <int E> __device__ __forceinline__ void vec_put(u32x4& v, int e, uint32_t raw) {
-    if constexpr (E == EL_F32) v[e] = raw;
-    else if constexpr (E == EL_U8) v[e >> 2] |= raw << (8 * (e & 3));
-    else v[e >> 1] |= raw << (16 * (e & 1));
-}
-
-// A 16-byte global store with the wait states gfx950 needs behind it PINNED (as store16() of mz_dihedral.hip):
-// the store and `s_nop 1` in one statement, which the scheduler cannot part.  Every 16-byte store of this unit goes through here.
-__device__ __forceinline__ void store16(void* p, const u32x4& v) {
-    asm volatile("global_store_dwordx4 %0, %1, off\n\ts_nop 1" ::"v"(p), "v"(v) : "memory");
-}
-
 // the one rounding of a result to the stored element, as its raw bits (f32_round_odd: mz_view.h)
-template <int E> __device__ __forceinline__ uint32_t finish_raw(double v, int clamp) {
+template <int E> __device__ __forceinline__ uint32_t interp_round_raw(double v, int clamp) {
 #pragma clang fp contract(off)
     if constexpr (E == EL_U8) {
         v = fmin(fmax(v, 0.0), 1.0);
@@ -67,12 +39,9 @@ __global__ __launch_bounds__(kInterpThreads) void interp_kernel(const StridedVie
     __shared__ double hrow[kFilter ? SR * ROWP : 1];
     auto hslot = [](int r, int cc) { return r * ROWP + (cc % V) * HP + cc / V; };
     const int tid = threadIdx.x;
-    const long long wg = blockIdx.x;
-    const long long plane = wg / tiles;  // b * 3 + c
-    const int tile = (int)(wg - plane * tiles);
-    const long long b = plane / 3, c = plane - b * 3;
-    const int tile_y = tile / tiles_x, tile_x = tile - tile_y * tiles_x;
-    const int i0 = tile_y * TH, j0 = tile_x * TW;  // inside the window
+    const PlaneTile pt = plane_tile(blockIdx.x, tiles, tiles_x);
+    const long long b = pt.b, c = pt.c;
+    const int i0 = pt.ty * TH, j0 = pt.tx * TW;  // inside the window
     const int th = min(TH, h - i0), tw = min(TW, w - j0);
 
     // ---- the taps of the tile's columns and rows ----
@@ -144,7 +113,7 @@ __global__ __launch_bounds__(kInterpThreads) void interp_kernel(const StridedVie
                 double hk[K];
 #pragma unroll
                 for (int k = 0; k < K; ++k) hk[k] = staged ? hrow[hslot(rows[k] - rmin, cc)] : hsum(rows[k], cc);
-                return finish_raw<E>(interp_dot<K>(wk, hk), clamp);
+                return interp_round_raw<E>(interp_dot<K>(wk, hk), clamp);
             }
         };
         const long long at = obase + (long long)(i0 + di) * out.s[2] + (long long)(j0 + dj) * out.s[3];  // (out.data: the window's corner)
@@ -159,21 +128,13 @@ __global__ __launch_bounds__(kInterpThreads) void interp_kernel(const StridedVie
     }
 }
 
-// every address of a [B,3,H,*] view's rows is a multiple of 16 bytes: the base and the strides of the dimensions that have a second step
-static bool rows_aligned16(const StridedView& v, int B, int H, int elem_bytes) {
-    if ((uintptr_t)v.data % 16) return false;
-    const long long per = 16 / elem_bytes;
-    return (B == 1 || v.s[0] % per == 0) && v.s[1] % per == 0 && (H == 1 || v.s[2] % per == 0);
-}
-
 template <int E, int MODE> static hipError_t launch_interp_em(const InterpArgs& a, hipStream_t s) {
-    const int tiles_x = (a.w + kInterpTileW - 1) / kInterpTileW, tiles_y = (a.h + kInterpTileH - 1) / kInterpTileH;
-    const long long tiles = (long long)tiles_x * tiles_y;
-    if (tiles <= 0 || tiles > 0x7fffffffLL / (3LL * a.B)) return hipErrorInvalidValue;
-    const int vec = a.out.s[3] == 1 && rows_aligned16(a.out, a.B, a.h, kElemBytes<E>) ? 1 : 0;
+    TileGrid g;
+    if (!plane_tile_grid(a.h, a.w, kInterpTileH, kInterpTileW, a.B, &g)) return hipErrorInvalidValue;
+    const int vec = a.out.s[3] == 1 && rows_aligned(a.out, a.B, a.h, kElemBytes<E>, 16) ? 1 : 0;
     const int stage = a.Hin <= a.Hout && a.Win <= a.Wout && getenv("MZ_INTERP_GATHER") == nullptr ? 1 : 0;
-    hipLaunchKernelGGL((interp_kernel<E, MODE>), dim3((unsigned)(tiles * 3 * a.B)), dim3(kInterpThreads), 0, s, a.x, a.out, a.Hin, a.Win, a.Hout,
-                       a.Wout, a.y0, a.x0, a.h, a.w, tiles, tiles_x, a.clamp, vec, stage);
+    hipLaunchKernelGGL((interp_kernel<E, MODE>), dim3((unsigned)g.wgs), dim3(kInterpThreads), 0, s, a.x, a.out, a.Hin, a.Win, a.Hout, a.Wout, a.y0,
+                       a.x0, a.h, a.w, g.tiles, g.tiles_x, a.clamp, vec, stage);
     return hipGetLastError();
 }
 

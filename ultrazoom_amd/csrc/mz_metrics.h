@@ -254,11 +254,9 @@ __global__ __launch_bounds__(kMetricsThreads) void moments_kernel(const StridedV
     __shared__ double hp[5][SH][TW];              // T = 17: 40 KiB -> 64 KiB in all, two workgroups per CU
     const int tid = threadIdx.x;
     const long long wg = blockIdx.x;
-    const long long plane = wg / tiles;           // b * 3 + c
-    const int tile = (int)(wg - plane * tiles);
-    const long long b = plane / 3, c = plane - b * 3;
-    const int ty = tile / tiles_x, tx = tile - ty * tiles_x;
-    const int y0 = ty * TH, x0 = tx * TW;
+    const PlaneTile pt = plane_tile(wg, tiles, tiles_x);
+    const long long b = pt.b, c = pt.c;
+    const int y0 = pt.ty * TH, x0 = pt.tx * TW;
     const int hv = H - T + 1, wv = W - T + 1;
 
     const long long pb = b * p.s[0] + c * p.s[1], tb = b * t.s[0] + c * t.s[1];
@@ -376,7 +374,7 @@ __device__ __forceinline__ double ordered_sum(const double* q, long long n, int 
     for (long long i = threadIdx.x; i < n; i += kMetricsThreads) v += q[i * stride];
     return block_reduce<OpSum>(v, sh);
 }
-struct FinishArgs {
+struct MetricsFinishArgs {
     int which;
     const double* ssim_part;
     long long ssim_tiles;
@@ -387,7 +385,7 @@ struct FinishArgs {
     long long vif_tiles[4];
 };
 // grid B
-__global__ __launch_bounds__(kMetricsThreads) void finish_kernel(const FinishArgs a, double* out) {
+__global__ __launch_bounds__(kMetricsThreads) void finish_kernel(const MetricsFinishArgs a, double* out) {
     __shared__ double sh[kMetricsThreads];
     const long long b = blockIdx.x;
     double* o = out + b * kMetricSlots;

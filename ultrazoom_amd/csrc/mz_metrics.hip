@@ -2,6 +2,7 @@
 #define MZ_METRICS_KERNELS
 #include "mz_metrics.h"
 
+#include <cassert>
 #include <cmath>
 
 namespace mz {
@@ -19,15 +20,13 @@ static MetricsTaps gaussian_taps(int n, double sigma) {
     return t;
 }
 
-static bool grid_ok(long long wgs) { return wgs > 0 && wgs <= 0x7fffffffLL; }
-
 template <int E, int T, int EPI>
 static hipError_t launch_moments(const StridedView& p, const StridedView& t, int B, int H, int W, long long tiles, const MetricsTaps& taps,
                                  double param, const double* range_dev, double* part, hipStream_t s) {
-    const long long wgs = tiles * 3 * B;
-    if (!grid_ok(wgs)) return hipErrorInvalidValue;
-    const int tiles_x = (W - T + 1 + kMetricsTileW - 1) / kMetricsTileW;
-    hipLaunchKernelGGL((moments_kernel<E, T, EPI>), dim3((unsigned)wgs), dim3(kMetricsThreads), 0, s, p, t, H, W, tiles, tiles_x, taps, param,
+    TileGrid g;  // of the (H - T + 1) x (W - T + 1) map; `tiles` is the plan's count (the workspace is laid out by it)
+    if (!plane_tile_grid(H - T + 1, W - T + 1, kMetricsTileH, kMetricsTileW, B, &g)) return hipErrorInvalidValue;
+    assert(g.tiles == tiles);
+    hipLaunchKernelGGL((moments_kernel<E, T, EPI>), dim3((unsigned)g.wgs), dim3(kMetricsThreads), 0, s, p, t, H, W, tiles, g.tiles_x, taps, param,
                        range_dev, part);
     return hipGetLastError();
 }
@@ -35,15 +34,10 @@ static hipError_t launch_moments(const StridedView& p, const StridedView& t, int
 template <int E, int T>
 static hipError_t launch_down(const StridedView& p, const StridedView& t, int B, int Ho, int Wo, double* outp, double* outt, hipStream_t s) {
     const long long blocks = ((long long)Ho * Wo + kMetricsThreads - 1) / kMetricsThreads;
-    const long long wgs = blocks * 3 * B;
-    if (!grid_ok(wgs)) return hipErrorInvalidValue;
-    hipLaunchKernelGGL((down_kernel<E, T>), dim3((unsigned)wgs), dim3(kMetricsThreads), 0, s, p, t, Ho, Wo, blocks,
+    if (!grid_ok(blocks, 3LL * B)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL((down_kernel<E, T>), dim3((unsigned)(blocks * 3 * B)), dim3(kMetricsThreads), 0, s, p, t, Ho, Wo, blocks,
                        gaussian_taps(T, T / 5.0), outp, outt);
     return hipGetLastError();
-}
-
-static StridedView dense_f64(const double* data, int h, int w) {
-    return StridedView{data, {3LL * h * w, (long long)h * w, w, 1}};
 }
 
 template <int E> static hipError_t launch_metrics_e(const MetricsArgs& a, hipStream_t s) {
@@ -74,9 +68,9 @@ template <int E> static hipError_t launch_metrics_e(const MetricsArgs& a, hipStr
             pyr[k][0] = (double*)(a.ws + pl.off_pyr[k]);
             pyr[k][1] = pyr[k][0] + (size_t)a.B * 3 * pl.vif_h[k] * pl.vif_w[k];
         }
-        const StridedView p1 = dense_f64(pyr[1][0], pl.vif_h[1], pl.vif_w[1]), t1 = dense_f64(pyr[1][1], pl.vif_h[1], pl.vif_w[1]);
-        const StridedView p2 = dense_f64(pyr[2][0], pl.vif_h[2], pl.vif_w[2]), t2 = dense_f64(pyr[2][1], pl.vif_h[2], pl.vif_w[2]);
-        const StridedView p3 = dense_f64(pyr[3][0], pl.vif_h[3], pl.vif_w[3]), t3 = dense_f64(pyr[3][1], pl.vif_h[3], pl.vif_w[3]);
+        const StridedView p1 = dense_view(pyr[1][0], pl.vif_h[1], pl.vif_w[1]), t1 = dense_view(pyr[1][1], pl.vif_h[1], pl.vif_w[1]);
+        const StridedView p2 = dense_view(pyr[2][0], pl.vif_h[2], pl.vif_w[2]), t2 = dense_view(pyr[2][1], pl.vif_h[2], pl.vif_w[2]);
+        const StridedView p3 = dense_view(pyr[3][0], pl.vif_h[3], pl.vif_w[3]), t3 = dense_view(pyr[3][1], pl.vif_h[3], pl.vif_w[3]);
         if ((e = launch_down<E, 9>(a.pred, a.target, a.B, pl.vif_h[1], pl.vif_w[1], pyr[1][0], pyr[1][1], s)) != hipSuccess) return e;
         if ((e = launch_moments<EL_F64, 9, EPI_VIF>(p1, t1, a.B, pl.vif_h[1], pl.vif_w[1], pl.vif_tiles[1], gaussian_taps(9, 9 / 5.0), a.sigma_n_sq,
                                                     nullptr, (double*)(a.ws + pl.off_vif[1]), s)) != hipSuccess) return e;
@@ -88,7 +82,7 @@ template <int E> static hipError_t launch_metrics_e(const MetricsArgs& a, hipStr
                                                     nullptr, (double*)(a.ws + pl.off_vif[3]), s)) != hipSuccess) return e;
     }
     if (a.which & (MET_SSIM | MET_VIF)) {
-        FinishArgs f = {};
+        MetricsFinishArgs f = {};
         f.which = a.which;
         f.ssim_part = (const double*)(a.ws + pl.off_ssim);
         f.ssim_tiles = pl.ssim_tiles;

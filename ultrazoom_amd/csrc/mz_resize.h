@@ -156,11 +156,9 @@ __global__ __launch_bounds__(kResizeThreads) void resize_kernel(const StridedVie
     double* wys = wxs + (size_t)taps_x * TW;     // [taps_y][TH]
     float* hrow = (float*)(wys + (size_t)taps_y * TH);  // [rows_cap][TW]: the horizontally filtered input rows of the tile
     const int tid = threadIdx.x, tx = tid & (TW - 1), ty = tid / TW;
-    const long long wg = blockIdx.x;
-    const long long plane = wg / tiles;         // b * 3 + c
-    const int tile = (int)(wg - plane * tiles);
-    const long long b = plane / 3, c = plane - b * 3;
-    const int tile_y = tile / tiles_x, tile_x = tile - tile_y * tiles_x;
+    const PlaneTile pt = plane_tile(blockIdx.x, tiles, tiles_x);
+    const long long b = pt.b, c = pt.c;
+    const int tile_y = pt.ty, tile_x = pt.tx;
     const int wy_ = tile_y * TH + ty, wx_ = tile_x * TW + tx;  // inside the window
     const int oy = y0 + wy_, ox = x0 + wx_;                      // inside the Hout x Wout result
 

@@ -10,17 +10,15 @@ template <int E> static hipError_t launch_resize_e(const ResizeArgs& a, hipStrea
     int* span_y = (int*)(a.ws + pl.off_span_y);
     double* w_x = (double*)(a.ws + pl.off_w_x);
     double* w_y = (double*)(a.ws + pl.off_w_y);
-    const int tiles_x = (a.w + kResizeTileW - 1) / kResizeTileW, tiles_y = (a.h + kResizeTileH - 1) / kResizeTileH;
-    const long long tiles = (long long)tiles_x * tiles_y;
-    const long long wgs = tiles * 3 * a.B;
-    if (wgs <= 0 || wgs > 0x7fffffffLL || pl.lds_bytes > 64 * 1024) return hipErrorInvalidValue;
+    TileGrid g;
+    if (!plane_tile_grid(a.h, a.w, kResizeTileH, kResizeTileW, a.B, &g) || pl.lds_bytes > 64 * 1024) return hipErrorInvalidValue;
     const long long table_wgs = ((long long)a.Wout + a.Hout + kResizeThreads - 1) / kResizeThreads;
     hipLaunchKernelGGL(resize_table_kernel, dim3((unsigned)table_wgs), dim3(kResizeThreads), 0, s, a.Hin, a.Win, a.Hout, a.Wout, a.filter,
                        pl.taps_x, pl.taps_y, span_x, w_x, span_y, w_y);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((resize_kernel<E>), dim3((unsigned)wgs), dim3(kResizeThreads), pl.lds_bytes, s, a.x, a.out, a.y0, a.x0, a.h, a.w, tiles,
-                       tiles_x, a.clamp, pl.taps_x, pl.taps_y, pl.rows_cap, (const int*)span_x, (const double*)w_x, (const int*)span_y,
+    hipLaunchKernelGGL((resize_kernel<E>), dim3((unsigned)g.wgs), dim3(kResizeThreads), pl.lds_bytes, s, a.x, a.out, a.y0, a.x0, a.h, a.w, g.tiles,
+                       g.tiles_x, a.clamp, pl.taps_x, pl.taps_y, pl.rows_cap, (const int*)span_x, (const double*)w_x, (const int*)span_y,
                        (const double*)w_y);
     return hipGetLastError();
 }

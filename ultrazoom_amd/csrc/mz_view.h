@@ -1,9 +1,13 @@
-// An image view as the kernels of mz_metrics.h, mz_resize.h and mz_degrade.h take it, the element codes, and every conversion between a
-// stored element and the value it stands for -- stated here once (the convolution kernels' view path, ImageViews / StemView, is
-// separate; mz_view_check.h holds the host's checks of the public mz_image_view).  A uint8 element v stands for v / 255: read by a
-// TRUE division, stored as clamp -> * 255 + 0.5 -> truncate, exactly mz_forward_u8's rule; the float accessors do that in float32,
-// the double ones in float64.  The struct and the enum need no HIP header; the accessors exist under hipcc only, for translation
-// units that have included <hip/hip_runtime.h>.
+// An image view as the kernels of mz_metrics.h, mz_resize.h, mz_degrade.h, mz_interp.h and mz_dihedral.h take it, the element codes,
+// every conversion between a stored element and the value it stands for, and what those kernels and their launchers share below that
+// -- stated here once (the convolution kernels' view path, ImageViews / StemView, is separate; mz_view_check.h holds the host's checks
+// of the public mz_image_view).  A uint8 element v stands for v / 255: read by a TRUE division, stored as clamp -> * 255 + 0.5 ->
+// truncate, exactly mz_forward_u8's rule; the float accessors do that in float32, the double ones in float64.
+//   host (no HIP header: plain g++ compiles it, tests/view_check_main.cpp runs it under the sanitizers): the struct, the enum, the grid
+//     of a plane-tile launch (plane_tile_grid, grid_ok), rows_aligned, dense_view
+//   device (under hipcc only, for translation units that have included <hip/hip_runtime.h>): the accessors, the raw-element and 16-byte
+//     vector helpers, store16() -- the ONE place a 16-byte global store of an image kernel is written -- and plane_tile(), the walk that
+//     takes a workgroup index apart
 #pragma once
 #include <stdint.h>
 
@@ -16,6 +20,34 @@ struct StridedView {
 
 // the `elem` of the view entries; EL_F64 is internal (the VIF pyramid in mz_metrics' workspace)
 enum Elem : int { EL_F32 = 0, EL_BF16 = 1, EL_F16 = 2, EL_U8 = 3, EL_F64 = 4 };
+
+// ---- the launchers' side --------------------------------------------------------------------------------------------------------
+// a grid of wgs * per workgroups can be launched: 1 .. 2^31 - 1 (no product is formed here: the caller's fits once this says so)
+inline bool grid_ok(long long wgs, long long per = 1) { return wgs > 0 && per > 0 && wgs <= 0x7fffffffLL / per; }
+
+// THE GRID CONVENTION of the plane-tile kernels (interp, dihedral, resize, blur, moments): tiles * 3 * B workgroups, tile fastest -- the
+// tile_h x tile_w tiles of an h x w rectangle row by row, then the channel, then the image; plane_tile() below takes an index apart.
+struct TileGrid { int tiles_x, tiles_y; long long tiles, wgs; };  // tiles = tiles_x * tiles_y; wgs = tiles * 3 * B
+// false where wgs is not in [1, 2^31 - 1] (nothing is multiplied before it is known to fit: sides of 2^28 in 1 x 1 tiles are refused)
+inline bool plane_tile_grid(int h, int w, int tile_h, int tile_w, int B, TileGrid* g) {
+    if (h < 1 || w < 1 || tile_h < 1 || tile_w < 1 || B < 1) return false;
+    g->tiles_x = (int)(((long long)w + tile_w - 1) / tile_w);
+    g->tiles_y = (int)(((long long)h + tile_h - 1) / tile_h);
+    g->tiles = (long long)g->tiles_x * g->tiles_y;
+    if (!grid_ok(g->tiles, 3LL * B)) return false;
+    g->wgs = g->tiles * 3 * B;
+    return true;
+}
+
+// every address of a [B,3,H,*] view's rows is a multiple of `bytes`: the base and the strides of the dimensions that have a second step
+inline bool rows_aligned(const StridedView& v, int B, int H, int elem_bytes, int bytes) {
+    if ((uintptr_t)v.data % bytes) return false;
+    const long long per = bytes / elem_bytes;
+    return (B == 1 || v.s[0] % per == 0) && v.s[1] % per == 0 && (H == 1 || v.s[2] % per == 0);
+}
+
+// a dense [B,3,H,W] array as a view (sides of 2^28: the image stride is 3 * 2^56)
+inline StridedView dense_view(const void* data, int H, int W) { return StridedView{data, {3LL * H * W, (long long)H * W, W, 1}}; }
 
 #ifdef __HIPCC__
 #include <type_traits>
@@ -80,6 +112,53 @@ template <int E> __device__ __forceinline__ int ld_8bit(const void* base, long l
 template <int E> __device__ __forceinline__ void st_8bit(void* base, long long i, int v) {
     if constexpr (E == EL_U8) ((uint8_t*)base)[i] = (uint8_t)v;
     else st_f32<E>(base, i, unit_of_u8(v), 0);
+}
+
+// ---- raw elements and 16-byte vectors of them (the kernels that move bit patterns: interp's nearest, dihedral) ----------------------
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+
+template <int E> constexpr int kElemBytes = E == EL_F32 ? 4 : E == EL_U8 ? 1 : 2;
+template <int E> constexpr int kVec = 16 / kElemBytes<E>;  // elements of one 16-byte access
+
+// an element as it lies in memory, zero-extended to a dword, and back (nearest moves bit patterns)
+template <int E> __device__ __forceinline__ uint32_t ld_raw(const void* base, long long i) {
+    if constexpr (E == EL_F32) return ((const uint32_t*)base)[i];
+    else if constexpr (E == EL_U8) return ((const uint8_t*)base)[i];
+    else return ((const uint16_t*)base)[i];
+}
+template <int E> __device__ __forceinline__ void st_raw(void* base, long long i, uint32_t v) {
+    if constexpr (E == EL_F32) ((uint32_t*)base)[i] = v;
+    else if constexpr (E == EL_U8) ((uint8_t*)base)[i] = (uint8_t)v;
+    else ((uint16_t*)base)[i] = (uint16_t)v;
+}
+// element e of a 16-byte vector of kVec<E> elements, and its place in one
+template <int E> __device__ __forceinline__ uint32_t vec_get(const u32x4& v, int e) {
+    if constexpr (E == EL_F32) return v[e];
+    else if constexpr (E == EL_U8) return (v[e >> 2] >> (8 * (e & 3))) & 0xffu;
+    else return (v[e >> 1] >> (16 * (e & 1))) & 0xffffu;
+}
+template <int E> __device__ __forceinline__ void vec_put(u32x4& v, int e, uint32_t raw) {
+    if constexpr (E == EL_F32) v[e] = raw;
+    else if constexpr (E == EL_U8) v[e >> 2] |= raw << (8 * (e & 3));
+    else v[e >> 1] |= raw << (16 * (e & 1));
+}
+
+// A 16-byte global store with the wait states gfx950 needs behind it PINNED (the store reads its data registers
+// late; hipcc pads one wait state, the probe of tests/test_store_hazard_gpu.py wants two): the store and `s_nop 1` in one statement,
+// which the scheduler cannot part.  Every 16-byte store of the image kernels goes through here; tools/asm_store_hazard.py re-checks
+// the listings.
+__device__ __forceinline__ void store16(void* p, const u32x4& v) {
+    asm volatile("global_store_dwordx4 %0, %1, off\n\ts_nop 1" ::"v"(p), "v"(v) : "memory");
+}
+
+// ---- the tile walk: workgroup wg of the grid plane_tile_grid() describes (tiles * 3 * B workgroups, tile fastest) -------------------
+struct PlaneTile { long long b, c; int ty, tx; };  // image, channel, tile row, tile column
+__device__ __forceinline__ PlaneTile plane_tile(long long wg, long long tiles, int tiles_x) {
+    const long long plane = wg / tiles;  // b * 3 + c
+    const int tile = (int)(wg - plane * tiles);
+    const long long b = plane / 3, c = plane - b * 3;
+    const int ty = tile / tiles_x, tx = tile - ty * tiles_x;
+    return PlaneTile{b, c, ty, tx};
 }
 
 // f(std::integral_constant<int, E>()) of an entry's element code E = 0..3: how a launcher picks its kernels' instantiation

@@ -42,20 +42,7 @@ def interpolate(x: Tensor, size: Optional[Tuple[int, int]] = None, scale_factor:
     elem, B, H, W = _ffi.check_image_batch(x, "interpolate")
     if scale_factor is not None:
         size = (H * scale_factor, W * scale_factor)
-    size = tuple(int(v) for v in size)
-    if len(size) != 2 or min(size) < 1:
-        raise ValueError(f"size is (Hout, Wout) with both at least 1, got {size}")
-    Hout, Wout = size
-    if window is None:
-        want = (B, 3, Hout, Wout)
-    else:
-        window = tuple(int(v) for v in window)
-        if len(window) != 4:
-            raise ValueError("window is (y0, x0, h, w) in output pixels")
-        y0, x0, h, w = window
-        if h < 1 or w < 1 or y0 < 0 or x0 < 0 or y0 + h > Hout or x0 + w > Wout:
-            raise ValueError(f"window {window} is empty or not inside the {Hout} x {Wout} result")
-        want = (B, 3, h, w)
+    Hout, Wout, window, want = _ffi.output_shape(B, size, window)
     if out is not None:
         _ffi.check_same_batch(x, out, want)
     with torch.cuda.device(x.device):

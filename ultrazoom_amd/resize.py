@@ -30,22 +30,11 @@ def resize(x: Tensor, size: Tuple[int, int], *, filter: str = "bicubic", clamp: 
     if filter not in _FILTERS:
         raise ValueError(f"filter is 'bicubic' or 'bilinear', got {filter!r}")
     elem, B, H, W = _ffi.check_image_batch(x, "resize")
-    size = tuple(int(v) for v in size)
-    if len(size) != 2 or min(size) < 1:
-        raise ValueError(f"size is (Hout, Wout) with both at least 1, got {size}")
-    Hout, Wout = size
-    if H > MAX_RATIO * Hout or W > MAX_RATIO * Wout:
-        raise ValueError(f"{(H, W)} -> {size} shrinks an axis by more than {MAX_RATIO}: resize in two steps")
-    if window is None:
-        want = (B, 3, Hout, Wout)
-    else:
-        window = tuple(int(v) for v in window)
-        if len(window) != 4:
-            raise ValueError("window is (y0, x0, h, w) in output pixels")
-        y0, x0, h, w = window
-        if h < 1 or w < 1 or y0 < 0 or x0 < 0 or y0 + h > Hout or x0 + w > Wout:
-            raise ValueError(f"window {window} is empty or not inside the {Hout} x {Wout} result")
-        want = (B, 3, h, w)
+    def ratio_check(Hout, Wout):
+        if H > MAX_RATIO * Hout or W > MAX_RATIO * Wout:
+            raise ValueError(f"{(H, W)} -> {(Hout, Wout)} shrinks an axis by more than {MAX_RATIO}: resize in two steps")
+
+    Hout, Wout, window, want = _ffi.output_shape(B, size, window, ratio_check)
     if out is not None:
         _ffi.check_same_batch(x, out, want)
     with torch.cuda.device(x.device):
