@@ -94,12 +94,14 @@ int mz_weights_complete(const mz_handle* h);
  * micro-batches of at most `max_images_in_flight` images (0 = library default), so memory does
  * not grow beyond that.
  *
- * What a call touches (mz_forward, mz_forward_u8, mz_forward_view, mz_metrics, mz_resize, mz_interpolate, mz_blur, mz_noise, mz_jpeg and the mz_op_* entries alike): it READS only its
+ * What a call touches (mz_forward, mz_forward_u8, mz_forward_view, mz_metrics, mz_metrics_luma, mz_luma, mz_resize, mz_interpolate, mz_blur, mz_noise,
+ * mz_jpeg and the mz_op_* entries alike): it READS only its
  * input tensors -- the elements its shape and strides name, never a byte next to them -- and the workspace bytes it has itself
  * written during that call; it WRITES only its outputs (of a view: the elements of the window) and its workspace, never an input.
  * The workspace needs no initialisation and carries nothing from one call to the next: whatever it holds, NaN patterns included,
- * the results have the same bits.  mz_metrics writes the `out` slots of the metrics `which` selects and leaves the others alone.
- * tests/test_poison_ops_gpu.py, tests/test_poison_forward_gpu.py and tests/test_metrics_gpu.py hold every entry to this.
+ * the results have the same bits.  mz_metrics and mz_metrics_luma write the `out` slots of the metrics `which` selects and leave the
+ * others alone.  tests/test_poison_ops_gpu.py, tests/test_poison_forward_gpu.py, tests/test_metrics_gpu.py and
+ * tests/test_poison_color_gpu.py hold every entry to this.
  *
  * Number range (the convolution, mix, stem and head kernels, in every storage type): subnormals of the storage type are operands and
  * results like any other value -- nothing is flushed on the way in, in the matrix unit's operands, or at the store.  Accumulation is
@@ -137,10 +139,11 @@ int mz_forward_u8(mz_handle* h, const uint8_t* x, uint8_t* out_sr, float* out_qa
  * and out, or between elements of out, is the caller's responsibility and is not checked (beyond refusing an output stride of 0;
  * mz_blur, mz_noise and mz_jpeg also compare the two byte ranges).
  *
- * THE VIEW REFUSALS.  Every entry that takes views (mz_forward_view, mz_metrics, mz_resize, mz_interpolate, mz_blur, mz_noise, mz_jpeg, mz_dihedral,
- * mz_ensemble_add, mz_ensemble_finish) returns
+ * THE VIEW REFUSALS.  Every entry that takes views (mz_forward_view, mz_metrics, mz_metrics_luma, mz_luma, mz_resize, mz_interpolate, mz_blur,
+ * mz_noise, mz_jpeg, mz_dihedral, mz_ensemble_add, mz_ensemble_finish) returns
  * MZ_ERR_INVALID_ARGUMENT, before anything touches the GPU, for: a null view or null data; an `elem` outside the entry's codes; a view
- * that is WRITTEN whose channel, row or column stride is 0, or whose image stride is 0 when B > 1 (strides of a view that is only read
+ * that is WRITTEN whose channel, row or column stride is 0, or whose image stride is 0 when B > 1 (mz_luma's one-channel output: its
+ * channel stride is never used and may be anything; strides of a view that is only read
  * may be 0, and any stride may be negative); where the entry takes a window: one that is empty or not inside the result.  Each entry
  * below lists only what it refuses beyond these.  A workspace that is null or smaller than the entry's *_workspace_bytes is
  * MZ_ERR_WORKSPACE_TOO_SMALL.  (ultrazoom_amd/csrc/mz_view_check.h is the one statement of these checks.) */
@@ -230,6 +233,36 @@ int mz_metrics_workspace_bytes(int B, int H, int W, int which, size_t* bytes);
  * the device, as torchmetrics' data_range=None.  sigma_n_sq (VIF): the reference's default is 2.0. */
 int mz_metrics(const mz_image_view* pred, const mz_image_view* target, int elem, int B, int H, int W, int which,
                double data_range, double sigma_n_sq, double* out_dev, void* workspace, size_t workspace_bytes, void* hip_stream);
+
+/* ---- luma (Y): no reference counterpart (the reference's validate.py measures RGB over the full frame); the channel every
+ *      super-resolution paper reports PSNR / SSIM on.  ultrazoom_amd/csrc/mz_color.h is the one statement of the arithmetic -----------
+ * standard   0 "bt601": studio range, MATLAB's rgb2ycbcr and basicsr's bgr2ycbcr(y_only=True), for R, G, B in units of [0, 1]
+ *                       Y = 16/255 + (65.481/255) R + (128.553/255) G + (24.966/255) B          (white 235/255, black 16/255)
+ *            1 "full":  full range, BT.601 / JFIF / Pillow's "L":   Y = 0.299 R + 0.587 G + 0.114 B
+ * The constants are the float64 results of the divisions as written; the sum is float64, acc = off, then acc = fma(k, v, acc) for R, G,
+ * B in this order; a uint8 element v is v / 255.0 by true division.
+ *
+ * mz_luma: x, a view of [B,3,H,W], to out, a view of [B,1,H,W] of the same element type (elem 0..3; out's channel stride is never used).
+ * The float64 sum is rounded ONCE on store: a float type by one rounding to nearest even, after a clamp to [0, 1] when clamp != 0 (a NaN
+ * becomes 0); uint8 always clamps, then * 255 + 0.5, then truncates, in float64.  Stateless, no workspace; enqueues on the given stream;
+ * reads exactly the B 3 H W elements named and writes exactly B H W.
+ * Refuses the view refusals above (elem outside 0..3), and: B < 1 or > 65535; H or W < 1 or > 2^28; a standard outside 0..1; ANY overlap
+ * of the byte ranges of x and out (the entry does not work in place).
+ *
+ * mz_metrics_luma: mz_metrics of the Y planes of pred and target.  A first kernel writes both planes UNROUNDED, float64, into the
+ * workspace (so the metric sees Y in float64 whatever the element type); the kernels of mz_metrics then run on one plane instead of three.
+ * The workspace is that of one plane plus the two Y planes, 2 * 8 B H W bytes (mz_metrics_luma_workspace_bytes).  out_dev has mz_metrics'
+ * slots with these differences: slot 1 is H W; slot 7 is (H-10) (W-10); VIF writes slots 8 and 11 only (VIF = slot 8 / slot 11) and
+ * slots 9, 10, 12, 13 are left alone.  data_range <= 0 takes the range of the Y planes of the batch.  Everything mz_metrics promises
+ * about what a call touches, equal bits of two calls and independence of the batch holds.
+ * Refuses what mz_metrics refuses, and: a standard outside 0..1; B H W beyond 2^58 (the two planes would pass 2^62 bytes). */
+int mz_luma(const mz_image_view* x, const mz_image_view* out, int elem, int B, int H, int W, int standard, int clamp,
+            void* hip_stream);
+int mz_metrics_luma_workspace_bytes(int B, int H, int W, int which, size_t* bytes);
+int mz_metrics_luma(const mz_image_view* pred, const mz_image_view* target, int elem, int B, int H, int W, int which, int standard,
+                    double data_range, double sigma_n_sq, double* out_dev, void* workspace, size_t workspace_bytes, void* hip_stream);
+/* Host only: {off, kr, kg, kb} of a standard, the constants the kernels compile. */
+int mz_debug_luma_coeffs(int standard, double out[4]);
 
 /* ---- antialiased resampling to any size: no reference counterpart in `model.py`; stands in for torchvision's antialiased `Resize`
  *      as the reference's `data.py:91-108` uses it (HR -> LR for validation), and serves "a 3X or a true-4K result from a 4X model"

@@ -7,10 +7,11 @@
 All arithmetic runs in hand-written gfx950 kernels behind the C ABI in include/mewzoom_hip.h.
 """
 
+from .color import rgb_to_y  # noqa: F401
 from .degrade import Degradation, gaussian_blur, gaussian_noise, jpeg  # noqa: F401
 from .ensemble import dihedral, dihedral_inverse, upscale_ensemble  # noqa: F401
 from .interpolate import interpolate  # noqa: F401
 from .model import MewZoom, bake_state_dict  # noqa: F401
 
 __all__ = ["MewZoom", "bake_state_dict", "Degradation", "gaussian_blur", "gaussian_noise", "jpeg", "dihedral", "dihedral_inverse",
-           "upscale_ensemble", "interpolate"]
+           "upscale_ensemble", "interpolate", "rgb_to_y"]

@@ -25,6 +25,7 @@ MZ_METRIC_PSNR, MZ_METRIC_SSIM, MZ_METRIC_VIF = 1, 2, 4
 MZ_RESIZE_BICUBIC, MZ_RESIZE_BILINEAR = 0, 1
 MZ_RESIZE_MAX_TAPS = 66  # taps of one output at the largest accepted ratio (n_in / n_out = 16, bicubic)
 MZ_INTERP_NEAREST, MZ_INTERP_BILINEAR, MZ_INTERP_BICUBIC = 0, 1, 2
+MZ_LUMA_STANDARDS = {"bt601": 0, "full": 1}  # studio range (MATLAB rgb2ycbcr, basicsr) / full range (JFIF, Pillow's "L")
 
 
 class MzConfig(Structure):
@@ -85,6 +86,15 @@ def _declare(lib) -> None:
     lib.mz_metrics.argtypes = [POINTER(MzImageView), POINTER(MzImageView), c_int, c_int, c_int, c_int, c_int, c_double, c_double,
                                c_void_p, c_void_p, c_size_t, c_void_p]
     lib.mz_metrics.restype = c_int
+    lib.mz_luma.argtypes = [POINTER(MzImageView), POINTER(MzImageView), c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]
+    lib.mz_luma.restype = c_int
+    lib.mz_metrics_luma_workspace_bytes.argtypes = [c_int, c_int, c_int, c_int, POINTER(c_size_t)]
+    lib.mz_metrics_luma_workspace_bytes.restype = c_int
+    lib.mz_metrics_luma.argtypes = [POINTER(MzImageView), POINTER(MzImageView), c_int, c_int, c_int, c_int, c_int, c_int, c_double, c_double,
+                                    c_void_p, c_void_p, c_size_t, c_void_p]
+    lib.mz_metrics_luma.restype = c_int
+    lib.mz_debug_luma_coeffs.argtypes = [c_int, POINTER(c_double)]
+    lib.mz_debug_luma_coeffs.restype = c_int
     lib.mz_resize_workspace_bytes.argtypes = [c_int, c_int, c_int, c_int, c_int, POINTER(c_size_t)]
     lib.mz_resize_workspace_bytes.restype = c_int
     lib.mz_resize.argtypes = [POINTER(MzImageView), POINTER(MzImageView), c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
@@ -259,6 +269,44 @@ def metrics(pred_ptr, pred_strides, target_ptr, target_strides, elem, B, H, W, w
     check(
         lib().mz_metrics(
             byref(pv), byref(tv), int(elem), B, H, W, int(which), float(data_range), float(sigma_n_sq), c_void_p(out_ptr),
+            c_void_p(ws_ptr), ws_bytes, c_void_p(stream),
+        )
+    )
+
+
+def luma_standard(standard) -> int:
+    """The `standard` code of the luma entries: "bt601" -> 0, "full" -> 1."""
+    if standard not in MZ_LUMA_STANDARDS:
+        raise ValueError(f"luma standard is 'bt601' (studio range) or 'full' (full range), got {standard!r}")
+    return MZ_LUMA_STANDARDS[standard]
+
+
+def luma(x_ptr, x_strides, out_ptr, out_strides, elem, B, H, W, standard, clamp, stream) -> None:
+    """mz_luma: x a view of [B,3,H,W], out a view of [B,1,H,W], as for `resize`; `standard` 0 bt601, 1 full; no workspace."""
+    xv, ov = view(x_ptr, x_strides), view(out_ptr, out_strides)
+    check(lib().mz_luma(byref(xv), byref(ov), int(elem), B, H, W, int(standard), int(bool(clamp)), c_void_p(stream)))
+
+
+def luma_coeffs(standard: int):
+    """mz_debug_luma_coeffs (host only): [off, kr, kg, kb], the constants the kernels compile."""
+    out = (c_double * 4)()
+    check(lib().mz_debug_luma_coeffs(int(standard), out))
+    return [float(v) for v in out]
+
+
+def metrics_luma_workspace_bytes(B: int, H: int, W: int, which: int) -> int:
+    out = c_size_t()
+    check(lib().mz_metrics_luma_workspace_bytes(B, H, W, which, byref(out)))
+    return int(out.value)
+
+
+def metrics_luma(pred_ptr, pred_strides, target_ptr, target_strides, elem, B, H, W, which, standard, data_range, sigma_n_sq, out_ptr, ws_ptr,
+                 ws_bytes, stream) -> None:
+    """mz_metrics_luma: `metrics` on the float64 Y planes of the two [B,3,H,W] views."""
+    pv, tv = view(pred_ptr, pred_strides), view(target_ptr, target_strides)
+    check(
+        lib().mz_metrics_luma(
+            byref(pv), byref(tv), int(elem), B, H, W, int(which), int(standard), float(data_range), float(sigma_n_sq), c_void_p(out_ptr),
             c_void_p(ws_ptr), ws_bytes, c_void_p(stream),
         )
     )

@@ -1,8 +1,9 @@
-// Stateless image entry points of libmewzoom_hip.so: image-quality metrics, antialiased resizing, plain interpolation, the degradation
-// chain, the dihedral transforms with the self-ensemble accumulator, and the
+// Stateless image entry points of libmewzoom_hip.so: image-quality metrics (RGB and luma), the luma plane, antialiased resizing, plain
+// interpolation, the degradation chain, the dihedral transforms with the self-ensemble accumulator, and the
 // host-only mz_debug_* views of what their kernels are handed.  Every check comes before anything touches the GPU.
 #include <cstring>
 
+#include "mz_color.h"
 #include "mz_degrade.h"
 #include "mz_dihedral.h"
 #include "mz_err.h"
@@ -18,11 +19,11 @@ template <class Launch> static int launched(const char* what, Launch launch) {
     return hip_rc(launch(), what);
 }
 
-// the two byte ranges of a call, each from its own shape (mz_interpolate, mz_dihedral, the ensemble entries)
+// the two byte ranges of a call, each from its own shape (mz_interpolate, mz_dihedral, the ensemble entries; mz_luma: b has Cb = 1 channel)
 static int check_ranges_apart(const mz_image_view* a, int elem_a, int Ha, int Wa, const mz_image_view* b, int elem_b, int Hb, int Wb, int B,
-                              const char* what) {
+                              const char* what, int Cb = 3) {
     long long al, ah, bl, bh;
-    if (!view_extent(a, elem_a, B, Ha, Wa, &al, &ah) || !view_extent(b, elem_b, B, Hb, Wb, &bl, &bh))
+    if (!view_extent(a, elem_a, B, Ha, Wa, &al, &ah) || !view_extent(b, elem_b, B, Hb, Wb, &bl, &bh, Cb))
         return fail(MZ_ERR_INVALID_ARGUMENT, "a view's byte range does not fit in 63 bits");
     if (al < bh && bl < ah) return fail(MZ_ERR_INVALID_ARGUMENT, "%s overlap: this entry does not work in place", what);
     return MZ_OK;
@@ -85,6 +86,73 @@ extern "C" int mz_metrics(const mz_image_view* pred, const mz_image_view* target
     a.out = out_dev;
     a.ws = (char*)workspace;
     return launched("metrics launch", [&] { return launch_metrics(a, (hipStream_t)hip_stream); });
+}
+
+// ------------------------------------------------------------------------------------------------
+// luma (mz_color.h): the Y plane of an RGB view, and the metrics of the Y planes of two views.  No reference counterpart: the reference's
+// validate.py measures RGB over the full frame.  Stateless like mz_metrics.  Every check comes before anything touches the GPU.
+// ------------------------------------------------------------------------------------------------
+static int check_standard(int standard) {
+    return luma_valid(standard) ? MZ_OK : fail(MZ_ERR_INVALID_ARGUMENT, "standard must be 0 (bt601, studio range) or 1 (full range), got %d", standard);
+}
+
+extern "C" int mz_luma(const mz_image_view* x, const mz_image_view* out, int elem, int B, int H, int W, int standard, int clamp,
+                       void* hip_stream) {
+    static const ViewRules rules = {3, MZ_ELEM_NAMES_0_3, /*second_is_output*/ true, /*batch_bound*/ true, /*side_bound*/ true};
+    if (!x || !out) return fail(MZ_ERR_INVALID_ARGUMENT, "null image view");
+    mz_image_view y = *out;
+    y.stride[1] = 1;  // one channel: its stride is never used, any value is accepted
+    LumaArgs a = {};
+    if (const Refusal r = check_views(x, &y, rules, elem, B, H, W, &a.x, &a.out)) return fail(r);
+    if (int rc = check_standard(standard)) return rc;
+    if (int rc = check_ranges_apart(x, elem, H, W, &y, elem, H, W, B, "x and out", 1)) return rc;
+    a.elem = elem; a.B = B; a.H = H; a.W = W;
+    a.standard = standard;
+    a.clamp = clamp != 0;
+    return launched("luma launch", [&] { return (hipError_t)launch_luma(a, hip_stream); });
+}
+
+// Host only: {off, kr, kg, kb} of a standard, the constants the kernels compile
+extern "C" int mz_debug_luma_coeffs(int standard, double out[4]) {
+    if (!out) return fail(MZ_ERR_INVALID_ARGUMENT, "null argument");
+    if (int rc = check_standard(standard)) return rc;
+    const LumaCoeffs k = luma_coeffs(standard);
+    out[0] = k.off; out[1] = k.kr; out[2] = k.kg; out[3] = k.kb;
+    return MZ_OK;
+}
+
+static int check_metrics_luma_shape(int B, int H, int W, int which) {
+    if (int rc = check_metrics_shape(B, H, W, which)) return rc;
+    if (!luma_planes_fit(B, H, W)) return fail(MZ_ERR_INVALID_ARGUMENT, "two float64 Y planes of %d x %d x %d are beyond 2^62 bytes", B, H, W);
+    return MZ_OK;
+}
+
+extern "C" int mz_metrics_luma_workspace_bytes(int B, int H, int W, int which, size_t* bytes) {
+    if (!bytes) return fail(MZ_ERR_INVALID_ARGUMENT, "null argument");
+    if (int rc = check_metrics_luma_shape(B, H, W, which)) return rc;
+    *bytes = metrics_plan(B, H, W, which, 1).total;
+    return MZ_OK;
+}
+
+extern "C" int mz_metrics_luma(const mz_image_view* pred, const mz_image_view* target, int elem, int B, int H, int W, int which, int standard,
+                               double data_range, double sigma_n_sq, double* out_dev, void* workspace, size_t workspace_bytes,
+                               void* hip_stream) {
+    static const ViewRules rules = {3, MZ_ELEM_NAMES_0_3, /*second_is_output*/ false, /*batch_bound*/ false, /*side_bound*/ false};
+    MetricsArgs a = {};
+    if (const Refusal r = check_views(pred, target, rules, elem, B, H, W, &a.pred, &a.target)) return fail(r);
+    if (int rc = check_metrics_luma_shape(B, H, W, which)) return rc;
+    if (int rc = check_standard(standard)) return rc;
+    if (!out_dev) return fail(MZ_ERR_INVALID_ARGUMENT, "null out_dev");
+    a.plan = metrics_plan(B, H, W, which, 1);
+    if (const Refusal r = check_workspace(workspace, workspace_bytes, a.plan.total)) return fail(r);
+    a.elem = elem; a.B = B; a.H = H; a.W = W;
+    a.standard = standard;
+    a.which = which;
+    a.data_range = data_range;
+    a.sigma_n_sq = sigma_n_sq;
+    a.out = out_dev;
+    a.ws = (char*)workspace;
+    return launched("luma metrics launch", [&] { return launch_metrics_luma(a, (hipStream_t)hip_stream); });
 }
 
 // ------------------------------------------------------------------------------------------------

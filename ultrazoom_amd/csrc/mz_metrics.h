@@ -18,11 +18,19 @@
 //   finish_kernel      per image: the tile partials in a fixed order -> out slots 6.. (no floating-point atomics anywhere: two calls
 //                      give the same bits, and an image's sums do not depend on the batch it is in)
 // All address arithmetic is 64-bit and signed (element strides of a view may be negative and larger than 2^31).
+//
+// CHANNELS.  The plan, the arguments and the kernels carry a channel count C: 3 for mz_metrics, 1 for mz_metrics_luma, where
+// luma_planes_kernel first writes the UNROUNDED float64 Y planes (mz_color.h) of both images, dense [B][1][H][W], into the workspace and
+// the kernels above then run on those planes with E = EL_F64.  C is a template argument: the C = 3 kernels are compiled as before, in
+// mz_metrics.hip; the C = 1 instantiations and luma_planes_kernel are compiled in mz_color.hip, the luma unit.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <assert.h>
+#include <math.h>
 #include <stddef.h>
 #include <stdint.h>
 
+#include "mz_color.h"
 #include "mz_view.h"
 
 namespace mz {
@@ -52,24 +60,31 @@ inline long long metrics_tiles(int H, int W, int taps) {
     return ((hv + kMetricsTileH - 1) / kMetricsTileH) * ((wv + kMetricsTileW - 1) / kMetricsTileW);
 }
 
-// Workspace layout of one call (bytes from the start, every part 256-byte aligned); depends on B, H, W, which only
+// Workspace layout of one call (bytes from the start, every part 256-byte aligned); depends on B, H, W, which and C only.  C = 1 is the
+// plan of mz_metrics_luma: the layout of one plane, and behind it the two Y planes (off_luma: p then t, float64 [B][1][H][W] each) --
+// the workspace of a luma call is larger than that of one RGB plane by these 2 * 8 B H W bytes (rounded up to 256).
 struct MetricsPlan {
-    int psnr_blocks;           // psnr_kernel workgroups per image: a function of H alone
+    int C;                     // channels: 3, or 1 (luma)
+    int psnr_blocks;           // psnr_kernel workgroups per image: a function of C H alone
     long long ssim_tiles;      // per channel
     int vif_h[4], vif_w[4];    // the image at each VIF scale
     long long vif_tiles[4];    // per channel
-    size_t off_psnr, off_range, off_ssim, off_vif[4], off_pyr[4];  // off_pyr[s]: p then t of scale s, float64 [B][3][h][w] each (s = 1..3)
+    size_t off_psnr, off_range, off_ssim, off_vif[4], off_pyr[4];  // off_pyr[s]: p then t of scale s, float64 [B][C][h][w] each (s = 1..3)
+    size_t off_luma;           // C = 1 only
     size_t total;
 };
-inline MetricsPlan metrics_plan(int B, int H, int W, int which) {
+// the two Y planes of a luma call fit a size_t worth allocating (2^62 bytes); every other part of the plan is smaller than they are
+inline bool luma_planes_fit(int B, int H, int W) { return (__int128)16 * B * H * W <= ((__int128)1 << 62); }
+inline MetricsPlan metrics_plan(int B, int H, int W, int which, int C = 3) {
     MetricsPlan p = {};
+    p.C = C;
     auto take = [&](size_t bytes) {
         const size_t at = p.total;
         p.total += (bytes + 255) & ~(size_t)255;
         return at;
     };
-    const size_t planes = (size_t)B * 3;
-    p.psnr_blocks = 3 * (long long)H < kPsnrBlocksMax ? 3 * H : kPsnrBlocksMax;
+    const size_t planes = (size_t)B * C;
+    p.psnr_blocks = C * (long long)H < kPsnrBlocksMax ? C * H : kPsnrBlocksMax;
     p.off_psnr = take((size_t)B * p.psnr_blocks * 5 * sizeof(double));
     p.off_range = take(sizeof(double));
     if (which & MET_SSIM) {
@@ -90,6 +105,7 @@ inline MetricsPlan metrics_plan(int B, int H, int W, int which) {
             p.off_vif[s] = take(planes * p.vif_tiles[s] * 2 * sizeof(double));
         }
     }
+    if (C == 1) p.off_luma = take(2 * planes * H * W * sizeof(double));
     return p;
 }
 
@@ -97,6 +113,7 @@ struct MetricsArgs {
     StridedView pred, target;
     int elem;            // Elem 0..3
     int B, H, W;
+    int standard;        // LumaStandard (plan.C == 1 only)
     int which;           // MetricBits
     double data_range;   // SSIM: > 0 fixed, <= 0 from the batch
     double sigma_n_sq;   // VIF
@@ -104,8 +121,10 @@ struct MetricsArgs {
     char* ws;
     MetricsPlan plan;
 };
-// Enqueues the whole call; hipErrorInvalidValue for a grid beyond 2^31 - 1 workgroups
+// Enqueues the whole call; hipErrorInvalidValue for a grid beyond 2^31 - 1 workgroups.  launch_metrics: mz_metrics (plan.C = 3,
+// mz_metrics.hip); launch_metrics_luma: mz_metrics_luma (plan.C = 1; mz_color.hip, which compiles the C = 1 kernels)
 hipError_t launch_metrics(const MetricsArgs& a, hipStream_t s);
+hipError_t launch_metrics_luma(const MetricsArgs& a, hipStream_t s);
 
 #ifdef MZ_METRICS_KERNELS  // mz_metrics.hip only: the host runtime includes the plan above without the device code
 
@@ -127,13 +146,13 @@ template <class OP> __device__ __forceinline__ double block_reduce(double v, dou
 }
 
 // ---- PSNR part ----------------------------------------------------------------------------------------------------------------------
-// grid (psnr_blocks, B): workgroup i takes rows i, i + psnr_blocks, .. of the 3 H channel rows of its image
-template <int E> __global__ __launch_bounds__(kMetricsThreads) void psnr_kernel(const StridedView p, const StridedView t, int H, int W,
+// grid (psnr_blocks, B): workgroup i takes rows i, i + psnr_blocks, .. of the C H channel rows of its image
+template <int E, int C = 3> __global__ __launch_bounds__(kMetricsThreads) void psnr_kernel(const StridedView p, const StridedView t, int H, int W,
                                                                                   double* part) {
     __shared__ double sh[kMetricsThreads];
     const long long b = blockIdx.y;
     double sq = 0.0, pmin = __builtin_inf(), pmax = -__builtin_inf(), tmin = __builtin_inf(), tmax = -__builtin_inf();
-    for (int r = blockIdx.x; r < 3 * H; r += gridDim.x) {
+    for (int r = blockIdx.x; r < C * H; r += gridDim.x) {
         const long long c = r / H, y = r - c * H;
         const long long po = b * p.s[0] + c * p.s[1] + y * p.s[2], to = b * t.s[0] + c * t.s[1] + y * t.s[2];
         for (long long x = threadIdx.x; x < W; x += kMetricsThreads) {
@@ -161,48 +180,11 @@ template <int E> __global__ __launch_bounds__(kMetricsThreads) void psnr_kernel(
     }
 }
 
-// grid B: the partials of image b in a fixed order (thread i: partials i, i + 256; then the tree)
-__global__ __launch_bounds__(kMetricsThreads) void psnr_reduce_kernel(const double* part, int blocks, double numel, double* out) {
-    __shared__ double sh[kMetricsThreads];
-    const long long b = blockIdx.x;
-    double sq = 0.0, pmin = __builtin_inf(), pmax = -__builtin_inf(), tmin = __builtin_inf(), tmax = -__builtin_inf();
-    for (int i = threadIdx.x; i < blocks; i += kMetricsThreads) {
-        const double* q = part + (b * blocks + i) * 5;
-        sq += q[0];
-        pmin = OpMin::f(pmin, q[1]);
-        pmax = OpMax::f(pmax, q[2]);
-        tmin = OpMin::f(tmin, q[3]);
-        tmax = OpMax::f(tmax, q[4]);
-    }
-    sq = block_reduce<OpSum>(sq, sh);
-    pmin = block_reduce<OpMin>(pmin, sh);
-    pmax = block_reduce<OpMax>(pmax, sh);
-    tmin = block_reduce<OpMin>(tmin, sh);
-    tmax = block_reduce<OpMax>(tmax, sh);
-    if (threadIdx.x == 0) {
-        double* o = out + b * kMetricSlots;
-        o[MS_SQ_ERR] = sq;
-        o[MS_NUMEL] = numel;
-        o[MS_P_MIN] = pmin;
-        o[MS_P_MAX] = pmax;
-        o[MS_T_MIN] = tmin;
-        o[MS_T_MAX] = tmax;
-    }
-}
-
-// one thread: max(p.max() - p.min(), t.max() - t.min()) over the whole batch, as ssim_per_image's data_range=None
-__global__ void range_kernel(const double* out, int B, double* range) {
-    if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    double pmin = __builtin_inf(), pmax = -__builtin_inf(), tmin = __builtin_inf(), tmax = -__builtin_inf();
-    for (int b = 0; b < B; ++b) {
-        const double* o = out + (long long)b * kMetricSlots;
-        pmin = OpMin::f(pmin, o[MS_P_MIN]);
-        pmax = OpMax::f(pmax, o[MS_P_MAX]);
-        tmin = OpMin::f(tmin, o[MS_T_MIN]);
-        tmax = OpMax::f(tmax, o[MS_T_MAX]);
-    }
-    *range = OpMax::f(pmax - pmin, tmax - tmin);
-}
+// psnr_reduce_kernel (grid B: the partials of image b in a fixed order -> out slots 0..5) and range_kernel (one thread: max(p.max() -
+// p.min(), t.max() - t.min()) over the whole batch, as ssim_per_image's data_range=None) are no templates: mz_metrics.hip holds them, and
+// these two launch them for every translation unit
+hipError_t launch_psnr_reduce(const double* part, int blocks, double numel, double* out, int B, hipStream_t s);
+hipError_t launch_range(const double* out, int B, double* range, hipStream_t s);
 
 // ---- windowed moments + epilogue ------------------------------------------------------------------------------------------------------
 enum MomentsEpilogue : int { EPI_SSIM = 0, EPI_VIF = 1 };
@@ -240,10 +222,10 @@ __device__ __forceinline__ void vif_pixel(const double m[5], double sigma_n_sq, 
     den = log10(1.0 + s_tt / sigma_n_sq);
 }
 
-// grid: tiles * 3 * B workgroups, tile fastest.  H, W: the image; the map is (H - T + 1) x (W - T + 1).
+// grid: tiles * C * B workgroups, tile fastest.  H, W: the image; the map is (H - T + 1) x (W - T + 1).
 // param: EPI_SSIM the fixed data range (> 0) or <= 0 = read *range_dev; EPI_VIF sigma_n_sq.
-// part: EPI_SSIM [B * 3][tiles], EPI_VIF [B * 3][tiles][2]
-template <int E, int T, int EPI>
+// part: EPI_SSIM [B * C][tiles], EPI_VIF [B * C][tiles][2]
+template <int E, int T, int EPI, int C = 3>
 __global__ __launch_bounds__(kMetricsThreads) void moments_kernel(const StridedView p, const StridedView t, int H, int W, long long tiles,
                                                                     int tiles_x, const MetricsTaps taps, double param,
                                                                     const double* range_dev, double* part) {
@@ -254,7 +236,7 @@ __global__ __launch_bounds__(kMetricsThreads) void moments_kernel(const StridedV
     __shared__ double hp[5][SH][TW];              // T = 17: 40 KiB -> 64 KiB in all, two workgroups per CU
     const int tid = threadIdx.x;
     const long long wg = blockIdx.x;
-    const PlaneTile pt = plane_tile(wg, tiles, tiles_x);
+    const PlaneTile pt = plane_tile(wg, tiles, tiles_x, C);
     const long long b = pt.b, c = pt.c;
     const int y0 = pt.ty * TH, x0 = pt.tx * TW;
     const int hv = H - T + 1, wv = W - T + 1;
@@ -338,8 +320,8 @@ __global__ __launch_bounds__(kMetricsThreads) void moments_kernel(const StridedV
 }
 
 // ---- VIF: the next scale --------------------------------------------------------------------------------------------------------------
-// out[plane][y][x] = sum_ij w[i] w[j] src[plane][2 y + i][2 x + j] for both images; grid: ceil(Ho * Wo / 256) * 3 * B workgroups
-template <int E, int T>
+// out[plane][y][x] = sum_ij w[i] w[j] src[plane][2 y + i][2 x + j] for both images; grid: ceil(Ho * Wo / 256) * C * B workgroups
+template <int E, int T, int C = 3>
 __global__ __launch_bounds__(kMetricsThreads) void down_kernel(const StridedView p, const StridedView t, int Ho, int Wo, long long blocks,
                                                                  const MetricsTaps taps, double* outp, double* outt) {
     const long long wg = blockIdx.x;
@@ -347,7 +329,7 @@ __global__ __launch_bounds__(kMetricsThreads) void down_kernel(const StridedView
     const long long i = (wg - plane * blocks) * kMetricsThreads + threadIdx.x;
     const long long hw = (long long)Ho * Wo;
     if (i >= hw) return;
-    const long long b = plane / 3, c = plane - b * 3;
+    const long long b = plane / C, c = plane - b * C;
     const long long y = i / Wo, x = i - y * Wo;
     const long long pb = b * p.s[0] + c * p.s[1] + 2 * y * p.s[2] + 2 * x * p.s[3];
     const long long tb = b * t.s[0] + c * t.s[1] + 2 * y * t.s[2] + 2 * x * t.s[3];
@@ -385,12 +367,12 @@ struct MetricsFinishArgs {
     long long vif_tiles[4];
 };
 // grid B
-__global__ __launch_bounds__(kMetricsThreads) void finish_kernel(const MetricsFinishArgs a, double* out) {
+template <int C = 3> __global__ __launch_bounds__(kMetricsThreads) void finish_kernel(const MetricsFinishArgs a, double* out) {
     __shared__ double sh[kMetricsThreads];
     const long long b = blockIdx.x;
     double* o = out + b * kMetricSlots;
     if (a.which & MET_SSIM) {
-        const double v = ordered_sum(a.ssim_part + b * 3 * a.ssim_tiles, 3 * a.ssim_tiles, 1, sh);
+        const double v = ordered_sum(a.ssim_part + b * C * a.ssim_tiles, C * a.ssim_tiles, 1, sh);
         if (threadIdx.x == 0) {
             o[MS_SSIM_SUM] = v;
             o[MS_SSIM_COUNT] = a.ssim_count;
@@ -398,10 +380,10 @@ __global__ __launch_bounds__(kMetricsThreads) void finish_kernel(const MetricsFi
         }
     }
     if (a.which & MET_VIF) {
-        for (int c = 0; c < 3; ++c) {
+        for (int c = 0; c < C; ++c) {
             double num = 0.0, den = 0.0;
             for (int s = 0; s < 4; ++s) {  // scale by scale, as vif_per_image accumulates
-                const double* q = a.vif_part[s] + (b * 3 + c) * a.vif_tiles[s] * 2;
+                const double* q = a.vif_part[s] + (b * C + c) * a.vif_tiles[s] * 2;
                 num += ordered_sum(q, a.vif_tiles[s], 2, sh);
                 den += ordered_sum(q + 1, a.vif_tiles[s], 2, sh);
             }
@@ -411,6 +393,113 @@ __global__ __launch_bounds__(kMetricsThreads) void finish_kernel(const MetricsFi
             }
         }
     }
+}
+
+// ---- the launchers of one call with C channels (mz_metrics.hip: C = 3; mz_color.hip: C = 1 on the Y planes) ----------------------------
+// g / g.sum() of evaluate.py's _gaussian_window, in double (the 2-D VIF window normalised in 2-D is its outer product)
+static inline MetricsTaps gaussian_taps(int n, double sigma) {
+    MetricsTaps t = {};
+    double sum = 0.0;
+    for (int i = 0; i < n; ++i) {
+        const double x = i - (n - 1) / 2.0;
+        t.w[i] = exp(-(x * x) / (2.0 * sigma * sigma));
+        sum += t.w[i];
+    }
+    for (int i = 0; i < n; ++i) t.w[i] /= sum;
+    return t;
+}
+
+template <int E, int T, int EPI, int C>
+static hipError_t launch_moments(const StridedView& p, const StridedView& t, int B, int H, int W, long long tiles, const MetricsTaps& taps,
+                                 double param, const double* range_dev, double* part, hipStream_t s) {
+    TileGrid g;  // of the (H - T + 1) x (W - T + 1) map; `tiles` is the plan's count (the workspace is laid out by it)
+    if (!plane_tile_grid(H - T + 1, W - T + 1, kMetricsTileH, kMetricsTileW, B, &g, C)) return hipErrorInvalidValue;
+    assert(g.tiles == tiles);
+    hipLaunchKernelGGL((moments_kernel<E, T, EPI, C>), dim3((unsigned)g.wgs), dim3(kMetricsThreads), 0, s, p, t, H, W, tiles, g.tiles_x, taps, param,
+                       range_dev, part);
+    return hipGetLastError();
+}
+
+template <int E, int T, int C>
+static hipError_t launch_down(const StridedView& p, const StridedView& t, int B, int Ho, int Wo, double* outp, double* outt, hipStream_t s) {
+    const long long blocks = ((long long)Ho * Wo + kMetricsThreads - 1) / kMetricsThreads;
+    if (!grid_ok(blocks, (long long)C * B)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL((down_kernel<E, T, C>), dim3((unsigned)(blocks * C * B)), dim3(kMetricsThreads), 0, s, p, t, Ho, Wo, blocks,
+                       gaussian_taps(T, T / 5.0), outp, outt);
+    return hipGetLastError();
+}
+
+template <int E, int C> static hipError_t launch_metrics_e(const MetricsArgs& a, hipStream_t s) {
+    const MetricsPlan& pl = a.plan;
+    hipError_t e = hipSuccess;
+    double* range_dev = (double*)(a.ws + pl.off_range);
+    const bool batch_range = (a.which & MET_SSIM) && !(a.data_range > 0.0);
+    if ((a.which & MET_PSNR) || batch_range) {
+        double* part = (double*)(a.ws + pl.off_psnr);
+        if (a.B > 65535) return hipErrorInvalidValue;
+        hipLaunchKernelGGL((psnr_kernel<E, C>), dim3(pl.psnr_blocks, a.B), dim3(kMetricsThreads), 0, s, a.pred, a.target, a.H, a.W, part);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+        if ((e = launch_psnr_reduce(part, pl.psnr_blocks, (double)C * (double)a.H * (double)a.W, a.out, a.B, s)) != hipSuccess) return e;
+        if (batch_range && (e = launch_range(a.out, a.B, range_dev, s)) != hipSuccess) return e;
+    }
+    if (a.which & MET_SSIM) {
+        e = launch_moments<E, 11, EPI_SSIM, C>(a.pred, a.target, a.B, a.H, a.W, pl.ssim_tiles, gaussian_taps(11, 1.5), a.data_range, range_dev,
+                                            (double*)(a.ws + pl.off_ssim), s);
+        if (e != hipSuccess) return e;
+    }
+    if (a.which & MET_VIF) {
+        e = launch_moments<E, 17, EPI_VIF, C>(a.pred, a.target, a.B, a.H, a.W, pl.vif_tiles[0], gaussian_taps(17, 17 / 5.0), a.sigma_n_sq,
+                                           nullptr, (double*)(a.ws + pl.off_vif[0]), s);
+        if (e != hipSuccess) return e;
+        double* pyr[4][2] = {};
+        for (int k = 1; k < 4; ++k) {
+            pyr[k][0] = (double*)(a.ws + pl.off_pyr[k]);
+            pyr[k][1] = pyr[k][0] + (size_t)a.B * C * pl.vif_h[k] * pl.vif_w[k];
+        }
+        const StridedView p1 = dense_view(pyr[1][0], pl.vif_h[1], pl.vif_w[1], C), t1 = dense_view(pyr[1][1], pl.vif_h[1], pl.vif_w[1], C);
+        const StridedView p2 = dense_view(pyr[2][0], pl.vif_h[2], pl.vif_w[2], C), t2 = dense_view(pyr[2][1], pl.vif_h[2], pl.vif_w[2], C);
+        const StridedView p3 = dense_view(pyr[3][0], pl.vif_h[3], pl.vif_w[3], C), t3 = dense_view(pyr[3][1], pl.vif_h[3], pl.vif_w[3], C);
+        if ((e = launch_down<E, 9, C>(a.pred, a.target, a.B, pl.vif_h[1], pl.vif_w[1], pyr[1][0], pyr[1][1], s)) != hipSuccess) return e;
+        if ((e = launch_moments<EL_F64, 9, EPI_VIF, C>(p1, t1, a.B, pl.vif_h[1], pl.vif_w[1], pl.vif_tiles[1], gaussian_taps(9, 9 / 5.0), a.sigma_n_sq,
+                                                    nullptr, (double*)(a.ws + pl.off_vif[1]), s)) != hipSuccess) return e;
+        if ((e = launch_down<EL_F64, 5, C>(p1, t1, a.B, pl.vif_h[2], pl.vif_w[2], pyr[2][0], pyr[2][1], s)) != hipSuccess) return e;
+        if ((e = launch_moments<EL_F64, 5, EPI_VIF, C>(p2, t2, a.B, pl.vif_h[2], pl.vif_w[2], pl.vif_tiles[2], gaussian_taps(5, 5 / 5.0), a.sigma_n_sq,
+                                                    nullptr, (double*)(a.ws + pl.off_vif[2]), s)) != hipSuccess) return e;
+        if ((e = launch_down<EL_F64, 3, C>(p2, t2, a.B, pl.vif_h[3], pl.vif_w[3], pyr[3][0], pyr[3][1], s)) != hipSuccess) return e;
+        if ((e = launch_moments<EL_F64, 3, EPI_VIF, C>(p3, t3, a.B, pl.vif_h[3], pl.vif_w[3], pl.vif_tiles[3], gaussian_taps(3, 3 / 5.0), a.sigma_n_sq,
+                                                    nullptr, (double*)(a.ws + pl.off_vif[3]), s)) != hipSuccess) return e;
+    }
+    if (a.which & (MET_SSIM | MET_VIF)) {
+        MetricsFinishArgs f = {};
+        f.which = a.which;
+        f.ssim_part = (const double*)(a.ws + pl.off_ssim);
+        f.ssim_tiles = pl.ssim_tiles;
+        f.ssim_count = (double)C * (double)(a.H - 10) * (double)(a.W - 10);
+        f.fixed_range = a.data_range;
+        f.range_dev = range_dev;
+        for (int k = 0; k < 4; ++k) {
+            f.vif_part[k] = (const double*)(a.ws + pl.off_vif[k]);
+            f.vif_tiles[k] = pl.vif_tiles[k];
+        }
+        hipLaunchKernelGGL((finish_kernel<C>), dim3(a.B), dim3(kMetricsThreads), 0, s, f, a.out);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
+// ---- luma: the Y planes of both images --------------------------------------------------------------------------------------------------
+// yp[b][y][x], yt[b][y][x] = the unrounded float64 Y (mz_color.h) of p and t; grid: ceil(H * W / 256) * B workgroups, one pixel a thread
+template <int E>
+__global__ __launch_bounds__(kMetricsThreads) void luma_planes_kernel(const StridedView p, const StridedView t, int H, int W, long long blocks,
+                                                                        const LumaCoeffs k, double* yp, double* yt) {
+    const long long wg = blockIdx.x;
+    const long long b = wg / blocks;
+    const long long i = (wg - b * blocks) * kMetricsThreads + threadIdx.x;
+    const long long hw = (long long)H * W;
+    if (i >= hw) return;
+    const long long y = i / W, x = i - y * W;
+    yp[b * hw + i] = luma_at<E>(p, b * p.s[0] + y * p.s[2] + x * p.s[3], k);
+    yt[b * hw + i] = luma_at<E>(t, b * t.s[0] + y * t.s[2] + x * t.s[3], k);
 }
 
 #endif  // MZ_METRICS_KERNELS

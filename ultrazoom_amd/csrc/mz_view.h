@@ -25,17 +25,18 @@ enum Elem : int { EL_F32 = 0, EL_BF16 = 1, EL_F16 = 2, EL_U8 = 3, EL_F64 = 4 };
 // a grid of wgs * per workgroups can be launched: 1 .. 2^31 - 1 (no product is formed here: the caller's fits once this says so)
 inline bool grid_ok(long long wgs, long long per = 1) { return wgs > 0 && per > 0 && wgs <= 0x7fffffffLL / per; }
 
-// THE GRID CONVENTION of the plane-tile kernels (interp, dihedral, resize, blur, moments): tiles * 3 * B workgroups, tile fastest -- the
+// THE GRID CONVENTION of the plane-tile kernels (interp, dihedral, resize, blur, moments): tiles * C * B workgroups, tile fastest -- the
 // tile_h x tile_w tiles of an h x w rectangle row by row, then the channel, then the image; plane_tile() below takes an index apart.
-struct TileGrid { int tiles_x, tiles_y; long long tiles, wgs; };  // tiles = tiles_x * tiles_y; wgs = tiles * 3 * B
+// C is 3 everywhere but in the metrics of a luma plane (mz_metrics_luma: C = 1).
+struct TileGrid { int tiles_x, tiles_y; long long tiles, wgs; };  // tiles = tiles_x * tiles_y; wgs = tiles * C * B
 // false where wgs is not in [1, 2^31 - 1] (nothing is multiplied before it is known to fit: sides of 2^28 in 1 x 1 tiles are refused)
-inline bool plane_tile_grid(int h, int w, int tile_h, int tile_w, int B, TileGrid* g) {
-    if (h < 1 || w < 1 || tile_h < 1 || tile_w < 1 || B < 1) return false;
+inline bool plane_tile_grid(int h, int w, int tile_h, int tile_w, int B, TileGrid* g, int C = 3) {
+    if (h < 1 || w < 1 || tile_h < 1 || tile_w < 1 || B < 1 || C < 1) return false;
     g->tiles_x = (int)(((long long)w + tile_w - 1) / tile_w);
     g->tiles_y = (int)(((long long)h + tile_h - 1) / tile_h);
     g->tiles = (long long)g->tiles_x * g->tiles_y;
-    if (!grid_ok(g->tiles, 3LL * B)) return false;
-    g->wgs = g->tiles * 3 * B;
+    if (!grid_ok(g->tiles, (long long)C * B)) return false;
+    g->wgs = g->tiles * C * B;
     return true;
 }
 
@@ -46,8 +47,10 @@ inline bool rows_aligned(const StridedView& v, int B, int H, int elem_bytes, int
     return (B == 1 || v.s[0] % per == 0) && v.s[1] % per == 0 && (H == 1 || v.s[2] % per == 0);
 }
 
-// a dense [B,3,H,W] array as a view (sides of 2^28: the image stride is 3 * 2^56)
-inline StridedView dense_view(const void* data, int H, int W) { return StridedView{data, {3LL * H * W, (long long)H * W, W, 1}}; }
+// a dense [B,C,H,W] array as a view (sides of 2^28: the image stride is C * 2^56)
+inline StridedView dense_view(const void* data, int H, int W, int C = 3) {
+    return StridedView{data, {(long long)C * H * W, (long long)H * W, W, 1}};
+}
 
 #ifdef __HIPCC__
 #include <type_traits>
@@ -151,12 +154,12 @@ __device__ __forceinline__ void store16(void* p, const u32x4& v) {
     asm volatile("global_store_dwordx4 %0, %1, off\n\ts_nop 1" ::"v"(p), "v"(v) : "memory");
 }
 
-// ---- the tile walk: workgroup wg of the grid plane_tile_grid() describes (tiles * 3 * B workgroups, tile fastest) -------------------
+// ---- the tile walk: workgroup wg of the grid plane_tile_grid() describes (tiles * C * B workgroups, tile fastest) -------------------
 struct PlaneTile { long long b, c; int ty, tx; };  // image, channel, tile row, tile column
-__device__ __forceinline__ PlaneTile plane_tile(long long wg, long long tiles, int tiles_x) {
-    const long long plane = wg / tiles;  // b * 3 + c
+__device__ __forceinline__ PlaneTile plane_tile(long long wg, long long tiles, int tiles_x, int C = 3) {
+    const long long plane = wg / tiles;  // b * C + c
     const int tile = (int)(wg - plane * tiles);
-    const long long b = plane / 3, c = plane - b * 3;
+    const long long b = plane / C, c = plane - b * C;
     const int ty = tile / tiles_x, tx = tile - ty * tiles_x;
     return PlaneTile{b, c, ty, tx};
 }

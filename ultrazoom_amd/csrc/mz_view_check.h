@@ -1,4 +1,4 @@
-// What every entry that takes mz_image_view refuses (include/mewzoom_hip.h, next to mz_image_view), stated once and called by all six
+// What every entry that takes mz_image_view refuses (include/mewzoom_hip.h, next to mz_image_view), stated once and called by all of them
 // before anything touches the GPU.  Host code without a HIP header (plain g++ compiles it: tests/view_check_main.cpp runs it under
 // the sanitizers); a check returns its code and message, the caller hands them to fail() (mz_err.h).
 #pragma once
@@ -70,9 +70,10 @@ inline Refusal check_window(const int32_t window[4], int H, int W, int* y0, int*
     return Refusal();
 }
 
-// the byte range [lo, hi) the elements of a [B,3,H,W] view lie in; false where it is no range of signed 64-bit addresses
-inline bool view_extent(const mz_image_view* v, int elem, int B, int H, int W, long long* lo, long long* hi) {
-    const long long n[4] = {B, 3, H, W};
+// the byte range [lo, hi) the elements of a [B,C,H,W] view lie in (C = 1: mz_luma's output; its channel stride names nothing); false
+// where it is no range of signed 64-bit addresses
+inline bool view_extent(const mz_image_view* v, int elem, int B, int H, int W, long long* lo, long long* hi, int C = 3) {
+    const long long n[4] = {B, C, H, W};
     __int128 a = 0, b = 0;  // |(n - 1) stride| < 2^28 2^63: four of them fit easily
     for (int i = 0; i < 4; ++i) {
         const __int128 span = (__int128)(n[i] - 1) * v->stride[i];

@@ -14,7 +14,16 @@ The reference takes both metrics from `torchmetrics` (absent from this image), w
 The arithmetic here is plain torch and runs wherever the tensors live; it is the evaluation harness, not part of the
 kernel path, and the float64 checker of the HIP kernels that compute the same metrics (`ultrazoom_amd/metrics.py`,
 `evaluate(..., backend="hip")`).  torchmetrics is absent from this image: the three metrics are checked against independent numpy / scipy
-computations of the same published definitions ("parity unpinned" for the metrics themselves)."""
+computations of the same published definitions ("parity unpinned" for the metrics themselves).
+
+LUMA AND SHAVE.  Super-resolution papers and leaderboards (Set5, Set14, DIV2K ..) report PSNR and SSIM on the Y channel of BT.601
+YCbCr with `scale` border pixels shaved off; the reference's validate.py measures RGB over the full frame, and so does everything above
+by default.  `evaluate(..., luma="bt601", shave=model.upscale_ratio)` is the usual protocol: `luma` = "bt601" (studio range: MATLAB's
+rgb2ycbcr, basicsr's bgr2ycbcr(y_only=True)) or "full" (JFIF / Pillow's "L") measures the float64 Y plane (`luma_plane` here,
+`mz_metrics_luma` on the device; the PSNR peak stays 1.0), `shave=k` measures `[..., k:H-k, k:W-k]` of both images.  MATLAB rounds Y to
+uint8 before it measures; on uint8 images that variant is
+`image_metrics(rgb_to_y(p).expand(-1, 3, -1, -1), rgb_to_y(t).expand(-1, 3, -1, -1))` (`ultrazoom_amd.color.rgb_to_y`; a read view may
+have stride 0)."""
 
 from __future__ import annotations
 
@@ -162,6 +171,38 @@ class VIF:
         return self.total / self.n if self.n else float("nan")
 
 
+# {off, kr, kg, kb} of a luma standard: the divisions as ultrazoom_amd/csrc/mz_color.h writes them
+LUMA_COEFFS = {"bt601": (16.0 / 255.0, 65.481 / 255.0, 128.553 / 255.0, 24.966 / 255.0), "full": (0.0, 0.299, 0.587, 0.114)}
+
+
+def _check_luma(luma) -> None:
+    if luma is not None and luma not in LUMA_COEFFS:
+        raise ValueError(f"luma is None, 'bt601' (studio range) or 'full' (full range), got {luma!r}")
+
+
+def luma_plane(x: Tensor, standard: str = "bt601") -> Tensor:
+    """The float64 Y plane [B, 1, H, W] of a [B, 3, H, W] tensor (R, G, B): off + kr R + kg G + kb B, added in this order, in plain torch
+    arithmetic wherever the tensor lives (a product is rounded before it is added: the kernels fuse the two, which moves Y by at most
+    three roundings of 2^-54).  A uint8 value v means v / 255."""
+    if standard not in LUMA_COEFFS:
+        raise ValueError(f"luma standard is 'bt601' (studio range) or 'full' (full range), got {standard!r}")
+    if x.dim() != 4 or x.shape[1] != 3:
+        raise ValueError(f"expected a [B, 3, H, W] tensor, got {tuple(x.shape)}")
+    off, kr, kg, kb = LUMA_COEFFS[standard]
+    v = x.double() / 255 if x.dtype == torch.uint8 else x.double()
+    y = off + kr * v[:, 0:1]
+    y = y + kg * v[:, 1:2]
+    return y + kb * v[:, 2:3]
+
+
+def _measured(img: Tensor, luma, shave: int) -> Tensor:
+    """what the torch backend's meters see of an image: the shaved view, its Y plane with `luma`"""
+    from .metrics import shaved
+
+    img = shaved(img, shave)
+    return img if luma is None else luma_plane(img, luma)
+
+
 def _bicubic_keys(res: dict) -> dict:
     return {"bicubic_" + k: res[k] for k in ("psnr", "ssim", "vif")}
 
@@ -183,7 +224,8 @@ def bicubic_baseline(x: Tensor, size, backend: str = "torch") -> Tensor:
 
 
 @torch.inference_mode()
-def evaluate(model, pairs: Iterable[Tuple[Tensor, Tensor]], backend: str = "torch", ensemble: int = 1, baseline: bool = False) -> dict:
+def evaluate(model, pairs: Iterable[Tuple[Tensor, Tensor]], backend: str = "torch", ensemble: int = 1, baseline: bool = False,
+             luma: Optional[str] = None, shave: int = 0) -> dict:
     """`pairs` yields (low-resolution input, high-resolution target) batches already on the model's device/dtype;
     returns {"psnr": ..., "ssim": ..., "vif": ..., "images": n} as the reference's test loop accumulates them (pretrain.py:301-329;
     "vif" is None when the images are smaller than the 41 x 41 pixels the metric needs).  `backend="torch"`: the functions above,
@@ -191,9 +233,12 @@ def evaluate(model, pairs: Iterable[Tuple[Tensor, Tensor]], backend: str = "torc
     only), accumulated on the device and read once at the end.  `ensemble` = 2, 4 or 8: the predictions are the self-ensemble of that
     many orientations (`ultrazoom_amd.ensemble.upscale_ensemble`, CUDA tensors only); 1 is the plain `model.upscale`.  `baseline=True`:
     the result also holds "bicubic_psnr", "bicubic_ssim" and "bicubic_vif", the same metrics of `bicubic_baseline(x, y's size, backend)`
-    against y, accumulated beside the others (on the device with `backend="hip"`: nothing is read inside the loop)."""
+    against y, accumulated beside the others (on the device with `backend="hip"`: nothing is read inside the loop).  `luma`, `shave`:
+    every metric, the "bicubic_*" ones included, is taken on the Y plane and without `shave` border pixels (the module's docstring);
+    the keys of the result are the same, and "vif" is None when fewer than 41 x 41 pixels are left."""
     if backend not in ("torch", "hip"):
         raise ValueError(f"backend is 'torch' or 'hip', got {backend!r}")
+    _check_luma(luma)
     predict = model.upscale
     if ensemble != 1:
         if ensemble not in (2, 4, 8):
@@ -205,7 +250,7 @@ def evaluate(model, pairs: Iterable[Tuple[Tensor, Tensor]], backend: str = "torc
     if backend == "hip":
         from .metrics import MetricsAccumulator
 
-        acc, base = MetricsAccumulator(1.0), MetricsAccumulator(1.0)
+        acc, base = MetricsAccumulator(1.0, luma=luma, shave=shave), MetricsAccumulator(1.0, luma=luma, shave=shave)
         n = 0
         for x, y in pairs:
             acc.update(predict(x), y)
@@ -218,7 +263,9 @@ def evaluate(model, pairs: Iterable[Tuple[Tensor, Tensor]], backend: str = "torc
     n = 0
     for x, y in pairs:
         images = [predict(x)] + ([bicubic_baseline(x, y.shape[-2:])] if baseline else [])
+        y = _measured(y, luma, shave)
         for (psnr, ssim, vif), img in zip(meters, images):
+            img = _measured(img, luma, shave)
             psnr.update(img, y)
             ssim.update(img, y)
             if min(y.shape[-2:]) >= 41:
@@ -257,7 +304,7 @@ def lr_from_hr(hr: Tensor, ratio: int, filter: str = "bicubic", backend: str = "
 
 
 def evaluate_hr(model, hr_batches: Iterable[Tensor], *, filter: str = "bicubic", backend: str = "torch", degrade=None,
-                ensemble: int = 1, baseline: bool = False) -> dict:
+                ensemble: int = 1, baseline: bool = False, luma: Optional[str] = None, shave: int = 0) -> dict:
     """`evaluate` on high-resolution batches alone: each is turned into its (LR, HR) pair by `lr_from_hr` at the model's ratio.  With
     `backend="hip"` the chain HR -> LR -> upscale -> metrics stays on the device and is read once, at the end.
 
@@ -271,21 +318,27 @@ def evaluate_hr(model, hr_batches: Iterable[Tensor], *, filter: str = "bicubic",
     degraded input as it is.
 
     `baseline` as for `evaluate`: the "bicubic_*" metrics of the low-resolution input (with `degrade`: the degraded one) enlarged to the
-    target's size with plain bicubic interpolation."""
+    target's size with plain bicubic interpolation.
+
+    `luma`, `shave` as for `evaluate` (the usual protocol: `luma="bt601", shave=model.upscale_ratio`), with `degrade` too; "deg_l2" does
+    not depend on them."""
+    _check_luma(luma)
     if degrade is None:
-        return evaluate(model, (lr_from_hr(hr, model.upscale_ratio, filter, backend) for hr in hr_batches), backend, ensemble, baseline)
+        return evaluate(model, (lr_from_hr(hr, model.upscale_ratio, filter, backend) for hr in hr_batches), backend, ensemble, baseline,
+                        luma, shave)
     if backend != "hip":
         raise ValueError("degrade runs on the device only: use backend='hip'. There is no CPU path.")
     if ensemble not in (1, 2, 4, 8):
         raise ValueError(f"ensemble is 1, 2, 4 or 8 orientations, got {ensemble}")
-    return _evaluate_degraded(model, hr_batches, degrade, int(ensemble), bool(baseline))
+    return _evaluate_degraded(model, hr_batches, degrade, int(ensemble), bool(baseline), luma, shave)
 
 
 @torch.inference_mode()
-def _evaluate_degraded(model, hr_batches: Iterable[Tensor], degrade, ensemble: int = 1, baseline: bool = False) -> dict:
+def _evaluate_degraded(model, hr_batches: Iterable[Tensor], degrade, ensemble: int = 1, baseline: bool = False, luma: Optional[str] = None,
+                       shave: int = 0) -> dict:
     from .metrics import MetricsAccumulator
 
-    acc, base = MetricsAccumulator(1.0), MetricsAccumulator(1.0)
+    acc, base = MetricsAccumulator(1.0, luma=luma, shave=shave), MetricsAccumulator(1.0, luma=luma, shave=shave)
     sq, count, n = None, 0, 0
     for hr in hr_batches:
         lr, target, want = degrade.apply(hr, model.upscale_ratio, index=n)
