@@ -2,8 +2,6 @@
 
 from __future__ import annotations
 
-import ctypes
-
 import torch
 
 from ultrazoom_amd import _ffi
@@ -93,6 +91,4 @@ def stream_ptr() -> int:
 
 def last_kernel() -> str:
     """Kernel family of the most recent convolution / mix launch of this thread (mz_debug_last_kernel)."""
-    lib = _ffi.lib()
-    lib.mz_debug_last_kernel.restype = ctypes.c_char_p
-    return lib.mz_debug_last_kernel().decode()
+    return _ffi.lib().mz_debug_last_kernel().decode()

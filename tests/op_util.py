@@ -212,9 +212,7 @@ class Op:
 
 def select_op(dtype_code, op, cin, cout, B, H, W, cus=256):
     """mz_debug_select: the family the host chooses on `cus` CUs (256: an MI355X), None where it refuses.  Needs no GPU."""
-    lib = _ffi.lib()
-    lib.mz_debug_select.restype = ctypes.c_char_p
-    got = lib.mz_debug_select(dtype_code, op, cin, cout, B, H, W, cus)
+    got = _ffi.lib().mz_debug_select(dtype_code, op, cin, cout, B, H, W, cus)
     return None if got is None else got.decode()
 
 

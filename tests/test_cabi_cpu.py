@@ -116,8 +116,7 @@ def test_tile_list_lists_every_tile_once(geom):
     grid come from group_walk(), which pick_order() uses for a launch): every (image, tile row, tile column, N tile) exactly once, tile
     origins on the tile grid, and the N tiles of a group's pixel tile next to each other."""
     B, ty, tx, ntiles, gm, gn, blk4, th, tw = geom
-    lib = ctypes.CDLL(str(_ffi.LIB_PATH))
-    lib.mz_debug_tile_list.restype = ctypes.c_int
+    lib = _ffi.lib()
     total = B * ty * tx * ntiles
     buf = (ctypes.c_uint * (2 * total))()
     n = lib.mz_debug_tile_list(B, ty, tx, ntiles, gm, gn, blk4, th, tw, buf, total)

@@ -3,8 +3,6 @@ packings a layer has, how many bytes each takes, and that each one holds every r
 mz_pack.h).  The table was recorded from the planned sizes of ConvW's packings when they were four pointer / size pairs (packed,
 packed16, packed16r, packed16t); a row that changes is a change of what the kernels read, and belongs in a pull request that says so."""
 
-import ctypes
-
 import numpy as np
 import pytest
 
@@ -284,11 +282,7 @@ TABLE = [
 
 
 def _lib():
-    lib = ctypes.CDLL(str(_ffi.LIB_PATH))
-    lib.mz_debug_pack.restype = ctypes.c_longlong
-    lib.mz_debug_pack.argtypes = [ctypes.c_int] * 5 + [ctypes.c_void_p, ctypes.c_longlong]
-    lib.mz_last_error.restype = ctypes.c_char_p
-    return lib
+    return _ffi.lib()
 
 
 def _weights(op, cin, cout):

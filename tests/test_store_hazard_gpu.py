@@ -32,10 +32,7 @@ FORMS = ["buffer_store soffset=0", "buffer_store soffset=sgpr", "global_store va
 
 def probe(follower, form, waits, dword, iters=64, blocks=1024):
     counts = (ctypes.c_uint * 5)()
-    lib = _ffi.lib()
-    lib.mz_debug_store_hazard.argtypes = [ctypes.c_int] * 6 + [ctypes.POINTER(ctypes.c_uint)]
-    lib.mz_debug_store_hazard.restype = ctypes.c_int
-    rc = lib.mz_debug_store_hazard(follower, form, waits, dword, iters, blocks, counts)
+    rc = _ffi.lib().mz_debug_store_hazard(follower, form, waits, dword, iters, blocks, counts)
     assert rc == 0, f"mz_debug_store_hazard returned {rc}"
     return list(counts)
 

@@ -9,7 +9,10 @@ from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import POINTER, Structure, byref, c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_size_t, c_uint8, c_uint32, c_uint64, c_void_p
+import re
+from contextlib import contextmanager
+from ctypes import (POINTER, Structure, byref, c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_longlong, c_size_t, c_uint, c_uint8,
+                    c_uint32, c_uint64, c_ulonglong, c_void_p)
 from pathlib import Path
 
 LIB_NAME = "libmewzoom_hip.so"
@@ -22,7 +25,9 @@ MZ_ERR_WORKSPACE_TOO_SMALL = -5
 
 MZ_METRIC_SLOTS = 16  # doubles per image of mz_metrics' output (include/mewzoom_hip.h documents the slots)
 MZ_METRIC_PSNR, MZ_METRIC_SSIM, MZ_METRIC_VIF = 1, 2, 4
+MZ_METRIC_MIN_SIZE = {"ssim": 11, "vif": 41}  # pixels an image needs in both directions: the 11-tap window; four scales of 17, 9, 5, 3 taps
 MZ_RESIZE_BICUBIC, MZ_RESIZE_BILINEAR = 0, 1
+MZ_RESIZE_FILTERS = {"bicubic": MZ_RESIZE_BICUBIC, "bilinear": MZ_RESIZE_BILINEAR}
 MZ_RESIZE_MAX_TAPS = 66  # taps of one output at the largest accepted ratio (n_in / n_out = 16, bicubic)
 MZ_INTERP_NEAREST, MZ_INTERP_BILINEAR, MZ_INTERP_BICUBIC = 0, 1, 2
 MZ_LUMA_STANDARDS = {"bt601": 0, "full": 1}  # studio range (MATLAB rgb2ycbcr, basicsr) / full range (JFIF, Pillow's "L")
@@ -63,98 +68,127 @@ class MewZoomHipError(RuntimeError):
         self.code = code
 
 
-_lib = None
+# Every function of include/mewzoom_hip.h, in the header's own spelling and order (tests/test_ffi_cpu.py holds the two to each other).
+PROTOTYPES = """
+int mz_create(const mz_config* cfg, int dtype, mz_handle** out);
+int mz_destroy(mz_handle* h);
+int mz_num_weights(const mz_handle* h);
+int mz_weight_info(const mz_handle* h, int index, const char** name, int64_t shape[4]);
+int mz_set_weight(mz_handle* h, const char* name, const float* dev_f32, const int64_t* shape, int ndim, void* hip_stream);
+int mz_weights_complete(const mz_handle* h);
+int mz_workspace_bytes(const mz_handle* h, int B, int H, int W, int max_images_in_flight, size_t* bytes);
+int mz_forward(mz_handle* h, const void* x, void* out_sr, float* out_qa, int B, int H, int W, int clamp, void* workspace,
+    size_t workspace_bytes, int max_images_in_flight, void* hip_stream);
+int mz_forward_u8(mz_handle* h, const uint8_t* x, uint8_t* out_sr, float* out_qa, int B, int H, int W, void* workspace,
+    size_t workspace_bytes, int max_images_in_flight, void* hip_stream);
+int mz_forward_view(mz_handle* h, const mz_image_view* x, const mz_image_view* out, float* out_qa, int B, int H, int W, int clamp,
+    int elem, const int32_t window[4], void* workspace, size_t workspace_bytes, int max_images_in_flight, void* hip_stream);
+int mz_padded_channels(int c);
+int mz_op_conv(int dtype, int kind, const void* in0, const void* in1, const float* w_dev_f32, float alpha, void* out, int B, int H, int W,
+    int cin, int cout, int Hout, int Wout, int silu, void* hip_stream);
+int mz_op_stem(int dtype, const void* x, const float* w_dev_f32, const float* b_dev_f32, void* out, int B, int H, int W, int cout,
+    void* hip_stream);
+int mz_op_final(int dtype, const void* feat, const void* img, const float* w_dev_f32, void* out, int B, int H, int W, int cin, int R,
+    int clamp, void* hip_stream);
+int mz_op_conv_mix(int dtype, const void* hid, const void* x, const float* w2_dev_f32, const float* wmix_dev_f32, float alpha, void* out,
+    int B, int H, int W, int cin, int cout, void* hip_stream);
+int mz_op_conv_film(int dtype, const void* in0, const float* w_dev_f32, const float* gamma_dev_f32, const float* beta_dev_f32, void* out,
+    int B, int H, int W, int cin, int cout, int silu, void* hip_stream);
+int mz_metrics_workspace_bytes(int B, int H, int W, int which, size_t* bytes);
+int mz_metrics(const mz_image_view* pred, const mz_image_view* target, int elem, int B, int H, int W, int which, double data_range,
+    double sigma_n_sq, double* out_dev, void* workspace, size_t workspace_bytes, void* hip_stream);
+int mz_luma(const mz_image_view* x, const mz_image_view* out, int elem, int B, int H, int W, int standard, int clamp, void* hip_stream);
+int mz_metrics_luma_workspace_bytes(int B, int H, int W, int which, size_t* bytes);
+int mz_metrics_luma(const mz_image_view* pred, const mz_image_view* target, int elem, int B, int H, int W, int which, int standard,
+    double data_range, double sigma_n_sq, double* out_dev, void* workspace, size_t workspace_bytes, void* hip_stream);
+int mz_debug_luma_coeffs(int standard, double out[4]);
+int mz_resize_workspace_bytes(int Hin, int Win, int Hout, int Wout, int filter, size_t* bytes);
+int mz_resize(const mz_image_view* x, const mz_image_view* out, int elem, int B, int Hin, int Win, int Hout, int Wout, int filter,
+    int clamp, const int32_t window[4], void* workspace, size_t workspace_bytes, void* hip_stream);
+int mz_debug_resize_taps(int n_in, int n_out, int filter, int i, int* first, double* w, int cap);
+int mz_interpolate(const mz_image_view* x, const mz_image_view* out, int elem, int B, int Hin, int Win, int Hout, int Wout, int mode,
+    int clamp, const int32_t window[4], void* hip_stream);
+int mz_debug_interp_taps(int n_in, int n_out, int mode, int i, int idx[4], double w[4]);
+int mz_blur(const mz_image_view* x, const mz_image_view* out, int elem, int B, int H, int W, double sigma, void* hip_stream);
+int mz_noise(const mz_image_view* x, const mz_image_view* out, int elem, int B, int H, int W, double sigma, uint64_t seed,
+    uint64_t offset, void* hip_stream);
+int mz_jpeg_workspace_bytes(int B, int H, int W, size_t* bytes);
+int mz_jpeg(const mz_image_view* x, const mz_image_view* out, int elem, int B, int H, int W, int quality, void* workspace,
+    size_t workspace_bytes, void* hip_stream);
+int mz_debug_blur_weights(double sigma, double* w, int cap);
+int mz_debug_jpeg_qtable(int quality, uint8_t* luma, uint8_t* chroma);
+int mz_debug_philox(const uint32_t counter[4], const uint32_t key[2], uint32_t out[4]);
+int mz_dihedral_inverse(int k);
+int mz_dihedral(const mz_image_view* x, const mz_image_view* out, int elem, int B, int H, int W, int k, void* hip_stream);
+int mz_ensemble_workspace_bytes(int B, int H, int W, size_t* bytes);
+int mz_ensemble_add(const mz_image_view* y, int elem, int B, int H, int W, int k, int first, void* workspace, size_t workspace_bytes,
+    void* hip_stream);
+int mz_ensemble_finish(const mz_image_view* out, int elem, int B, int H, int W, int n, int clamp, const int32_t window[4],
+    void* workspace, size_t workspace_bytes, void* hip_stream);
+const char* mz_last_error(void);
+const char* mz_version(void);
+double mz_flops_per_image(const mz_handle* h, int H, int W);
+int mz_profile_enable(mz_handle* h, int on);
+int mz_profile_dump(mz_handle* h, const char* path);
+int mz_profile_read(mz_handle* h, double* conv_ms, double* conv_flops, double* conv_launches, double* other_ms, double* conv_bytes);
+int mz_debug_read(unsigned long long* host_dst);
+const char* mz_debug_last_kernel(void);
+int mz_debug_tile_list(int B, int tiles_y, int tiles_x, int ntiles, int gm, int gn, int blk4, int th, int tw, unsigned int* out, int cap);
+const char* mz_debug_select(int dtype, int op, int cin, int cout, int B, int H, int W, int cus);
+int mz_debug_schedule(const mz_handle* h, int B, int H, int W, int want_qa, int cus, mz_debug_step* out, int cap);
+long long mz_debug_pack(int dtype, int op, int cin, int cout, int layout, long long* out, long long cap);
+int mz_debug_store_hazard(int follower, int form, int wait_states, int dword, int iters, int blocks, unsigned int* counts_out);
+"""
+
+_SCALARS = {
+    "int": c_int, "unsigned int": c_uint, "long long": c_longlong, "unsigned long long": c_ulonglong, "int32_t": c_int32,
+    "int64_t": c_int64, "uint8_t": c_uint8, "uint32_t": c_uint32, "uint64_t": c_uint64, "size_t": c_size_t, "float": c_float,
+    "double": c_double,
+}
+_POINTERS = {
+    "char*": c_char_p, "char**": POINTER(c_char_p), "mz_handle*": c_void_p, "mz_handle**": POINTER(c_void_p),
+    "mz_config*": POINTER(MzConfig), "mz_image_view*": POINTER(MzImageView), "mz_debug_step*": POINTER(MzDebugStep),
+    "size_t*": POINTER(c_size_t),  # the result of every *_workspace_bytes entry: always byref(c_size_t()) or None
+}
+
+
+def _ctype(spelling: str):
+    """The ctypes type of a C type as the header spells it (`T name[N]` arrives as `T*`).  Any other pointer to a scalar or to void than
+    those of _POINTERS is c_void_p: a device address as an int, a ctypes array, byref(...) and None all pass.  A spelling not listed here
+    is an error, never a default."""
+    key = re.sub(r"\bconst ", "", spelling)
+    if key in _SCALARS:
+        return _SCALARS[key]
+    if key in _POINTERS:
+        return _POINTERS[key]
+    if key.endswith("*") and (key[:-1] in _SCALARS or key[:-1] == "void"):
+        return c_void_p
+    raise TypeError(f"no ctypes type is stated for the C type {spelling!r}")
+
+
+def _parse(prototypes: str) -> dict:
+    """{name: (restype, argtypes)} of C prototypes, one `;` after each."""
+    table = {}
+    for text in prototypes.split(";")[:-1]:
+        result, name, params = re.fullmatch(r"(.+?)\s*\b(mz_\w+)\((.*)\)", " ".join(text.split())).groups()
+        argtypes = []
+        for param in ([] if params == "void" else params.split(", ")):
+            spelling, _, array = re.fullmatch(r"(.+?[ *])(\w+)(\[\d+\])?", param).groups()
+            argtypes.append(_ctype(spelling.strip() + ("*" if array else "")))
+        table[name] = (_ctype(result), argtypes)
+    return table
+
+
+SIGNATURES = _parse(PROTOTYPES)
 
 
 def _declare(lib) -> None:
-    H = c_void_p
-    lib.mz_create.argtypes = [POINTER(MzConfig), c_int, POINTER(H)]
-    lib.mz_destroy.argtypes = [H]
-    lib.mz_num_weights.argtypes = [H]
-    lib.mz_weight_info.argtypes = [H, c_int, POINTER(c_char_p), POINTER(c_int64)]
-    lib.mz_set_weight.argtypes = [H, c_char_p, c_void_p, POINTER(c_int64), c_int, c_void_p]
-    lib.mz_weights_complete.argtypes = [H]
-    lib.mz_workspace_bytes.argtypes = [H, c_int, c_int, c_int, c_int, POINTER(c_size_t)]
-    lib.mz_forward.argtypes = [H, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_int, c_void_p]
-    lib.mz_forward_u8.argtypes = [H, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_size_t, c_int, c_void_p]
-    lib.mz_forward_u8.restype = c_int
-    lib.mz_forward_view.argtypes = [H, POINTER(MzImageView), POINTER(MzImageView), c_void_p, c_int, c_int, c_int, c_int, c_int,
-                                    POINTER(c_int32), c_void_p, c_size_t, c_int, c_void_p]
-    lib.mz_forward_view.restype = c_int
-    lib.mz_metrics_workspace_bytes.argtypes = [c_int, c_int, c_int, c_int, POINTER(c_size_t)]
-    lib.mz_metrics_workspace_bytes.restype = c_int
-    lib.mz_metrics.argtypes = [POINTER(MzImageView), POINTER(MzImageView), c_int, c_int, c_int, c_int, c_int, c_double, c_double,
-                               c_void_p, c_void_p, c_size_t, c_void_p]
-    lib.mz_metrics.restype = c_int
-    lib.mz_luma.argtypes = [POINTER(MzImageView), POINTER(MzImageView), c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]
-    lib.mz_luma.restype = c_int
-    lib.mz_metrics_luma_workspace_bytes.argtypes = [c_int, c_int, c_int, c_int, POINTER(c_size_t)]
-    lib.mz_metrics_luma_workspace_bytes.restype = c_int
-    lib.mz_metrics_luma.argtypes = [POINTER(MzImageView), POINTER(MzImageView), c_int, c_int, c_int, c_int, c_int, c_int, c_double, c_double,
-                                    c_void_p, c_void_p, c_size_t, c_void_p]
-    lib.mz_metrics_luma.restype = c_int
-    lib.mz_debug_luma_coeffs.argtypes = [c_int, POINTER(c_double)]
-    lib.mz_debug_luma_coeffs.restype = c_int
-    lib.mz_resize_workspace_bytes.argtypes = [c_int, c_int, c_int, c_int, c_int, POINTER(c_size_t)]
-    lib.mz_resize_workspace_bytes.restype = c_int
-    lib.mz_resize.argtypes = [POINTER(MzImageView), POINTER(MzImageView), c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
-                              POINTER(c_int32), c_void_p, c_size_t, c_void_p]
-    lib.mz_resize.restype = c_int
-    lib.mz_debug_resize_taps.argtypes = [c_int, c_int, c_int, c_int, POINTER(c_int), POINTER(c_double), c_int]
-    lib.mz_debug_resize_taps.restype = c_int
-    lib.mz_interpolate.argtypes = [POINTER(MzImageView), POINTER(MzImageView), c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
-                                   POINTER(c_int32), c_void_p]
-    lib.mz_interpolate.restype = c_int
-    lib.mz_debug_interp_taps.argtypes = [c_int, c_int, c_int, c_int, POINTER(c_int), POINTER(c_double)]
-    lib.mz_debug_interp_taps.restype = c_int
-    lib.mz_blur.argtypes = [POINTER(MzImageView), POINTER(MzImageView), c_int, c_int, c_int, c_int, c_double, c_void_p]
-    lib.mz_blur.restype = c_int
-    lib.mz_noise.argtypes = [POINTER(MzImageView), POINTER(MzImageView), c_int, c_int, c_int, c_int, c_double, c_uint64, c_uint64, c_void_p]
-    lib.mz_noise.restype = c_int
-    lib.mz_jpeg_workspace_bytes.argtypes = [c_int, c_int, c_int, POINTER(c_size_t)]
-    lib.mz_jpeg_workspace_bytes.restype = c_int
-    lib.mz_jpeg.argtypes = [POINTER(MzImageView), POINTER(MzImageView), c_int, c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p]
-    lib.mz_jpeg.restype = c_int
-    lib.mz_debug_blur_weights.argtypes = [c_double, POINTER(c_double), c_int]
-    lib.mz_debug_blur_weights.restype = c_int
-    lib.mz_debug_jpeg_qtable.argtypes = [c_int, POINTER(c_uint8), POINTER(c_uint8)]
-    lib.mz_debug_jpeg_qtable.restype = c_int
-    lib.mz_debug_philox.argtypes = [POINTER(c_uint32), POINTER(c_uint32), POINTER(c_uint32)]
-    lib.mz_debug_philox.restype = c_int
-    lib.mz_dihedral_inverse.argtypes = [c_int]
-    lib.mz_dihedral_inverse.restype = c_int
-    lib.mz_dihedral.argtypes = [POINTER(MzImageView), POINTER(MzImageView), c_int, c_int, c_int, c_int, c_int, c_void_p]
-    lib.mz_dihedral.restype = c_int
-    lib.mz_ensemble_workspace_bytes.argtypes = [c_int, c_int, c_int, POINTER(c_size_t)]
-    lib.mz_ensemble_workspace_bytes.restype = c_int
-    lib.mz_ensemble_add.argtypes = [POINTER(MzImageView), c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p]
-    lib.mz_ensemble_add.restype = c_int
-    lib.mz_ensemble_finish.argtypes = [POINTER(MzImageView), c_int, c_int, c_int, c_int, c_int, c_int, POINTER(c_int32), c_void_p, c_size_t,
-                                       c_void_p]
-    lib.mz_ensemble_finish.restype = c_int
-    lib.mz_padded_channels.argtypes = [c_int]
-    lib.mz_op_conv.argtypes = [c_int, c_int, c_void_p, c_void_p, c_void_p, c_float, c_void_p] + [c_int] * 8 + [c_void_p]
-    lib.mz_op_conv_film.argtypes = [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p] + [c_int] * 6 + [c_void_p]
-    lib.mz_op_conv_film.restype = c_int
-    lib.mz_op_conv_mix.argtypes = [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p] + [c_int] * 5 + [c_void_p]
-    lib.mz_op_conv_mix.restype = c_int
-    lib.mz_op_stem.argtypes = [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]
-    lib.mz_op_final.argtypes = [c_int, c_void_p, c_void_p, c_void_p, c_void_p] + [c_int] * 6 + [c_void_p]
-    lib.mz_last_error.restype = c_char_p
-    lib.mz_version.restype = c_char_p
-    lib.mz_flops_per_image.argtypes = [H, c_int, c_int]
-    lib.mz_flops_per_image.restype = c_double
-    lib.mz_debug_schedule.argtypes = [H, c_int, c_int, c_int, c_int, c_int, POINTER(MzDebugStep), c_int]
-    lib.mz_debug_schedule.restype = c_int
-    lib.mz_profile_enable.argtypes = [H, c_int]
-    lib.mz_profile_read.argtypes = [H] + [POINTER(c_double)] * 5
-    lib.mz_profile_dump.argtypes = [H, c_char_p]
-    lib.mz_profile_dump.restype = c_int
-    for name in (
-        "mz_create mz_destroy mz_num_weights mz_weight_info mz_set_weight mz_weights_complete mz_workspace_bytes "
-        "mz_forward mz_padded_channels mz_op_conv mz_op_stem mz_op_final mz_profile_enable mz_profile_read"
-    ).split():
-        getattr(lib, name).restype = c_int
+    for name, (restype, argtypes) in SIGNATURES.items():
+        fn = getattr(lib, name)  # a function the library does not export is an error here
+        fn.restype, fn.argtypes = restype, argtypes
+
+
+_lib = None
 
 
 def lib():
@@ -242,6 +276,33 @@ def output_shape(B: int, size, window, size_check=None):
     return Hout, Wout, window, (B, 3, h, w)
 
 
+def pair(t):
+    """(address of element (0, 0, 0, 0), element strides) of a tensor: the two arguments that name a view in the functions below."""
+    return t.data_ptr(), t.stride()
+
+
+@contextmanager
+def image_frame(x, out=None, want=None, need=None):
+    """The frame of a tensor-level image entry around its call of the library: inside, x's device is the current one, and the frame hands
+    over (out, (workspace address, workspace bytes) or (), the current stream as an int).  `out` is held to the shape `want` by
+    check_same_batch before anything touches the device; without one it is a new dense tensor of that shape and of x's dtype (want =
+    None: the entry has no image output).  `need`, a function that returns a number of bytes, asks for a uint8 workspace of that size."""
+    import torch
+
+    if out is not None:
+        check_same_batch(x, out, want)
+    with torch.cuda.device(x.device):
+        stream = torch.cuda.current_stream(x.device).cuda_stream
+        ws = ()
+        if need is not None:
+            nbytes = need()
+            scratch = torch.empty(nbytes, dtype=torch.uint8, device=x.device)  # lives until the call inside the frame is enqueued
+            ws = (scratch.data_ptr(), nbytes)
+        if out is None and want is not None:
+            out = torch.empty(want, dtype=x.dtype, device=x.device)
+        yield out, ws, stream
+
+
 def view(ptr, strides) -> MzImageView:
     """An mz_image_view: the address of element (0, 0, 0, 0) and the element strides (image, channel, row, column; signed)."""
     return MzImageView(c_void_p(ptr), (c_int64 * 4)(*[int(v) for v in strides]))
@@ -256,22 +317,35 @@ def make_config(cfg: dict) -> MzConfig:
     return MzConfig(**{k: int(cfg[k]) for k, _ in MzConfig._fields_})
 
 
-def metrics_workspace_bytes(B: int, H: int, W: int, which: int) -> int:
+def _call(entry: str, *args) -> None:
+    """One call of a status-returning entry.  A view or a config is passed as it is (ctypes takes its address for a POINTER parameter), a
+    device address or a stream as an int; a status other than 0 raises."""
+    check(getattr(lib(), entry)(*args))
+
+
+def _bytes(entry: str, *args) -> int:
+    """What a *_workspace_bytes entry writes to its `size_t* bytes`."""
     out = c_size_t()
-    check(lib().mz_metrics_workspace_bytes(B, H, W, which, byref(out)))
+    _call(entry, *args, byref(out))
     return int(out.value)
+
+
+def _count(n: int) -> int:
+    """The count a host-only mz_debug_* entry returns; negative: its status."""
+    if n < 0:
+        check(n)
+    return n
+
+
+def metrics_workspace_bytes(B: int, H: int, W: int, which: int) -> int:
+    return _bytes("mz_metrics_workspace_bytes", B, H, W, which)
 
 
 def metrics(pred_ptr, pred_strides, target_ptr, target_strides, elem, B, H, W, which, data_range, sigma_n_sq, out_ptr, ws_ptr, ws_bytes,
             stream) -> None:
     """mz_metrics: the two views as for Handle.forward_view; `elem` 0..2 = MZ_F32 / MZ_BF16 / MZ_F16, 3 = uint8."""
-    pv, tv = view(pred_ptr, pred_strides), view(target_ptr, target_strides)
-    check(
-        lib().mz_metrics(
-            byref(pv), byref(tv), int(elem), B, H, W, int(which), float(data_range), float(sigma_n_sq), c_void_p(out_ptr),
-            c_void_p(ws_ptr), ws_bytes, c_void_p(stream),
-        )
-    )
+    _call("mz_metrics", view(pred_ptr, pred_strides), view(target_ptr, target_strides), int(elem), B, H, W, int(which), float(data_range),
+          float(sigma_n_sq), out_ptr, ws_ptr, ws_bytes, stream)
 
 
 def luma_standard(standard) -> int:
@@ -281,127 +355,106 @@ def luma_standard(standard) -> int:
     return MZ_LUMA_STANDARDS[standard]
 
 
+def resize_filter(filter_) -> int:
+    """The `filter` code of mz_resize: "bicubic" -> 0, "bilinear" -> 1."""
+    if filter_ not in tuple(MZ_RESIZE_FILTERS):
+        raise ValueError(f"filter is 'bicubic' or 'bilinear', got {filter_!r}")
+    return MZ_RESIZE_FILTERS[filter_]
+
+
 def luma(x_ptr, x_strides, out_ptr, out_strides, elem, B, H, W, standard, clamp, stream) -> None:
     """mz_luma: x a view of [B,3,H,W], out a view of [B,1,H,W], as for `resize`; `standard` 0 bt601, 1 full; no workspace."""
-    xv, ov = view(x_ptr, x_strides), view(out_ptr, out_strides)
-    check(lib().mz_luma(byref(xv), byref(ov), int(elem), B, H, W, int(standard), int(bool(clamp)), c_void_p(stream)))
+    _call("mz_luma", view(x_ptr, x_strides), view(out_ptr, out_strides), int(elem), B, H, W, int(standard), bool(clamp), stream)
 
 
 def luma_coeffs(standard: int):
     """mz_debug_luma_coeffs (host only): [off, kr, kg, kb], the constants the kernels compile."""
     out = (c_double * 4)()
-    check(lib().mz_debug_luma_coeffs(int(standard), out))
+    _call("mz_debug_luma_coeffs", int(standard), out)
     return [float(v) for v in out]
 
 
 def metrics_luma_workspace_bytes(B: int, H: int, W: int, which: int) -> int:
-    out = c_size_t()
-    check(lib().mz_metrics_luma_workspace_bytes(B, H, W, which, byref(out)))
-    return int(out.value)
+    return _bytes("mz_metrics_luma_workspace_bytes", B, H, W, which)
 
 
 def metrics_luma(pred_ptr, pred_strides, target_ptr, target_strides, elem, B, H, W, which, standard, data_range, sigma_n_sq, out_ptr, ws_ptr,
                  ws_bytes, stream) -> None:
     """mz_metrics_luma: `metrics` on the float64 Y planes of the two [B,3,H,W] views."""
-    pv, tv = view(pred_ptr, pred_strides), view(target_ptr, target_strides)
-    check(
-        lib().mz_metrics_luma(
-            byref(pv), byref(tv), int(elem), B, H, W, int(which), int(standard), float(data_range), float(sigma_n_sq), c_void_p(out_ptr),
-            c_void_p(ws_ptr), ws_bytes, c_void_p(stream),
-        )
-    )
+    _call("mz_metrics_luma", view(pred_ptr, pred_strides), view(target_ptr, target_strides), int(elem), B, H, W, int(which), int(standard),
+          float(data_range), float(sigma_n_sq), out_ptr, ws_ptr, ws_bytes, stream)
 
 
 def resize_workspace_bytes(Hin: int, Win: int, Hout: int, Wout: int, filter_: int) -> int:
-    out = c_size_t()
-    check(lib().mz_resize_workspace_bytes(Hin, Win, Hout, Wout, int(filter_), byref(out)))
-    return int(out.value)
+    return _bytes("mz_resize_workspace_bytes", Hin, Win, Hout, Wout, int(filter_))
 
 
 def resize(x_ptr, x_strides, out_ptr, out_strides, elem, B, Hin, Win, Hout, Wout, filter_, clamp, window, ws_ptr, ws_bytes, stream) -> None:
     """mz_resize: the two views as for Handle.forward_view (out: of the window); `elem` 0..2 = MZ_F32 / MZ_BF16 / MZ_F16, 3 = uint8;
     `window` = (y0, x0, h, w) in pixels of the Hout x Wout result, or None."""
-    xv, ov = view(x_ptr, x_strides), view(out_ptr, out_strides)
-    win = _window_arg(window)
-    check(
-        lib().mz_resize(
-            byref(xv), byref(ov), int(elem), B, Hin, Win, Hout, Wout, int(filter_), int(bool(clamp)), win, c_void_p(ws_ptr), ws_bytes,
-            c_void_p(stream),
-        )
-    )
+    _call("mz_resize", view(x_ptr, x_strides), view(out_ptr, out_strides), int(elem), B, Hin, Win, Hout, Wout, int(filter_), bool(clamp),
+          _window_arg(window), ws_ptr, ws_bytes, stream)
 
 
 def resize_taps(n_in: int, n_out: int, filter_: int, i: int):
     """mz_debug_resize_taps (host only): (first, [w_0 .. w_{count-1}]) of output index i of one axis."""
     first = c_int()
     w = (c_double * MZ_RESIZE_MAX_TAPS)()
-    count = lib().mz_debug_resize_taps(n_in, n_out, int(filter_), i, byref(first), w, MZ_RESIZE_MAX_TAPS)
-    if count < 0:
-        check(count)
+    count = _count(lib().mz_debug_resize_taps(n_in, n_out, int(filter_), i, byref(first), w, MZ_RESIZE_MAX_TAPS))
     return int(first.value), [float(w[j]) for j in range(count)]
 
 
 def interpolate(x_ptr, x_strides, out_ptr, out_strides, elem, B, Hin, Win, Hout, Wout, mode, clamp, window, stream) -> None:
     """mz_interpolate: the two views and the window as for `resize`; `mode` 0 nearest, 1 bilinear, 2 bicubic (A = -0.75); no workspace."""
-    xv, ov = view(x_ptr, x_strides), view(out_ptr, out_strides)
-    win = _window_arg(window)
-    check(lib().mz_interpolate(byref(xv), byref(ov), int(elem), B, Hin, Win, Hout, Wout, int(mode), int(bool(clamp)), win, c_void_p(stream)))
+    _call("mz_interpolate", view(x_ptr, x_strides), view(out_ptr, out_strides), int(elem), B, Hin, Win, Hout, Wout, int(mode), bool(clamp),
+          _window_arg(window), stream)
 
 
 def interp_taps(n_in: int, n_out: int, mode: int, i: int):
     """mz_debug_interp_taps (host only): ([idx_0 ..], [w_0 ..]) of output index i of one axis, 1, 2 or 4 taps."""
     idx, w = (c_int * 4)(), (c_double * 4)()
-    count = lib().mz_debug_interp_taps(n_in, n_out, int(mode), i, idx, w)
-    if count < 0:
-        check(count)
+    count = _count(lib().mz_debug_interp_taps(n_in, n_out, int(mode), i, idx, w))
     return [int(idx[j]) for j in range(count)], [float(w[j]) for j in range(count)]
 
 
 def blur(x_ptr, x_strides, out_ptr, out_strides, elem, B, H, W, sigma, stream) -> None:
     """mz_blur: the two views as for `resize`; `elem` 0..2 = MZ_F32 / MZ_BF16 / MZ_F16, 3 = uint8."""
-    xv, ov = view(x_ptr, x_strides), view(out_ptr, out_strides)
-    check(lib().mz_blur(byref(xv), byref(ov), int(elem), B, H, W, float(sigma), c_void_p(stream)))
+    _call("mz_blur", view(x_ptr, x_strides), view(out_ptr, out_strides), int(elem), B, H, W, float(sigma), stream)
 
 
 def noise(x_ptr, x_strides, out_ptr, out_strides, elem, B, H, W, sigma, seed, offset, stream) -> None:
     """mz_noise: `seed` and `offset` are taken modulo 2^64; out may be the same view as x."""
-    xv, ov = view(x_ptr, x_strides), view(out_ptr, out_strides)
-    check(lib().mz_noise(byref(xv), byref(ov), int(elem), B, H, W, float(sigma), int(seed) & (2**64 - 1), int(offset) & (2**64 - 1),
-                         c_void_p(stream)))
+    _call("mz_noise", view(x_ptr, x_strides), view(out_ptr, out_strides), int(elem), B, H, W, float(sigma), int(seed) & (2**64 - 1),
+          int(offset) & (2**64 - 1), stream)
 
 
 def jpeg_workspace_bytes(B: int, H: int, W: int) -> int:
-    out = c_size_t()
-    check(lib().mz_jpeg_workspace_bytes(B, H, W, byref(out)))
-    return int(out.value)
+    return _bytes("mz_jpeg_workspace_bytes", B, H, W)
 
 
 def jpeg(x_ptr, x_strides, out_ptr, out_strides, elem, B, H, W, quality, ws_ptr, ws_bytes, stream) -> None:
     """mz_jpeg: the round trip at `quality` 1..100 on a workspace of `jpeg_workspace_bytes(B, H, W)` bytes."""
-    xv, ov = view(x_ptr, x_strides), view(out_ptr, out_strides)
-    check(lib().mz_jpeg(byref(xv), byref(ov), int(elem), B, H, W, int(quality), c_void_p(ws_ptr), ws_bytes, c_void_p(stream)))
+    _call("mz_jpeg", view(x_ptr, x_strides), view(out_ptr, out_strides), int(elem), B, H, W, int(quality), ws_ptr, ws_bytes, stream)
 
 
 def blur_weights(sigma: float):
     """mz_debug_blur_weights (host only): the k = 2 * int(3 sigma) + 1 normalised weights the kernel is handed."""
     w = (c_double * 31)()
-    k = lib().mz_debug_blur_weights(float(sigma), w, 31)
-    if k < 0:
-        check(k)
+    k = _count(lib().mz_debug_blur_weights(float(sigma), w, 31))
     return [float(w[j]) for j in range(k)]
 
 
 def jpeg_qtable(quality: int):
     """mz_debug_jpeg_qtable (host only): (luminance, chrominance), 64 integers each, row-major."""
     a, b = (c_uint8 * 64)(), (c_uint8 * 64)()
-    check(lib().mz_debug_jpeg_qtable(int(quality), a, b))
+    _call("mz_debug_jpeg_qtable", int(quality), a, b)
     return list(a), list(b)
 
 
 def philox(counter, key):
     """mz_debug_philox (host only): the four words of one Philox4x32-10 block, from the function the noise kernel compiles."""
     out = (c_uint32 * 4)()
-    check(lib().mz_debug_philox((c_uint32 * 4)(*counter), (c_uint32 * 2)(*key), out))
+    _call("mz_debug_philox", (c_uint32 * 4)(*counter), (c_uint32 * 2)(*key), out)
     return [int(v) for v in out]
 
 
@@ -412,28 +465,23 @@ def dihedral_inverse(k: int) -> int:
 
 def dihedral(x_ptr, x_strides, out_ptr, out_strides, elem, B, H, W, k, stream) -> None:
     """mz_dihedral: out, a view of [B,3,H',W'], receives T(x, k) of the [B,3,H,W] view x; the views as for `resize`."""
-    xv, ov = view(x_ptr, x_strides), view(out_ptr, out_strides)
-    check(lib().mz_dihedral(byref(xv), byref(ov), int(elem), B, H, W, int(k), c_void_p(stream)))
+    _call("mz_dihedral", view(x_ptr, x_strides), view(out_ptr, out_strides), int(elem), B, H, W, int(k), stream)
 
 
 def ensemble_workspace_bytes(B: int, H: int, W: int) -> int:
-    out = c_size_t()
-    check(lib().mz_ensemble_workspace_bytes(B, H, W, byref(out)))
-    return int(out.value)
+    return _bytes("mz_ensemble_workspace_bytes", B, H, W)
 
 
 def ensemble_add(y_ptr, y_strides, elem, B, H, W, k, first, ws_ptr, ws_bytes, stream) -> None:
     """mz_ensemble_add: the pass result y, a view in ITS orientation ([B,3,W,H] when k & 4), turned back and stored in (`first`) or added
     to the float32 accumulator of the [B,3,H,W] result."""
-    yv = view(y_ptr, y_strides)
-    check(lib().mz_ensemble_add(byref(yv), int(elem), B, H, W, int(k), int(bool(first)), c_void_p(ws_ptr), ws_bytes, c_void_p(stream)))
+    _call("mz_ensemble_add", view(y_ptr, y_strides), int(elem), B, H, W, int(k), bool(first), ws_ptr, ws_bytes, stream)
 
 
 def ensemble_finish(out_ptr, out_strides, elem, B, H, W, n, clamp, window, ws_ptr, ws_bytes, stream) -> None:
     """mz_ensemble_finish: the mean of the n results added, into out (a view of the window, as for `resize`)."""
-    ov = view(out_ptr, out_strides)
-    win = _window_arg(window)
-    check(lib().mz_ensemble_finish(byref(ov), int(elem), B, H, W, int(n), int(bool(clamp)), win, c_void_p(ws_ptr), ws_bytes, c_void_p(stream)))
+    _call("mz_ensemble_finish", view(out_ptr, out_strides), int(elem), B, H, W, int(n), bool(clamp), _window_arg(window), ws_ptr, ws_bytes,
+          stream)
 
 
 class Handle:
@@ -441,7 +489,7 @@ class Handle:
 
     def __init__(self, cfg: dict, dtype_code_: int):
         self._h = c_void_p()
-        check(lib().mz_create(byref(make_config(cfg)), dtype_code_, byref(self._h)))
+        _call("mz_create", make_config(cfg), dtype_code_, byref(self._h))
         self.dtype_code = dtype_code_
 
     def close(self) -> None:
@@ -466,57 +514,36 @@ class Handle:
         return self._h
 
     def weight_infos(self):
-        n = lib().mz_num_weights(self._h)
         out = []
-        for i in range(n):
+        for i in range(lib().mz_num_weights(self._h)):
             name = c_char_p()
             shape = (c_int64 * 4)()
-            ndim = lib().mz_weight_info(self._h, i, byref(name), shape)
-            if ndim < 0:
-                check(ndim)
+            ndim = _count(lib().mz_weight_info(self._h, i, byref(name), shape))
             out.append((name.value.decode(), tuple(int(shape[k]) for k in range(ndim))))
         return out
 
     def set_weight(self, name: str, dev_ptr: int, shape, stream: int) -> None:
         arr = (c_int64 * 4)(*list(shape) + [0] * (4 - len(shape)))
-        check(lib().mz_set_weight(self._h, name.encode(), c_void_p(dev_ptr), arr, len(shape), c_void_p(stream)))
+        _call("mz_set_weight", self._h, name.encode(), dev_ptr, arr, len(shape), stream)
 
     def weights_complete(self) -> None:
-        check(lib().mz_weights_complete(self._h))
+        _call("mz_weights_complete", self._h)
 
     def workspace_bytes(self, B: int, H: int, W: int, max_in_flight: int = 0) -> int:
-        out = c_size_t()
-        check(lib().mz_workspace_bytes(self._h, B, H, W, max_in_flight, byref(out)))
-        return int(out.value)
+        return _bytes("mz_workspace_bytes", self._h, B, H, W, max_in_flight)
 
     def forward(self, x_ptr, sr_ptr, qa_ptr, B, H, W, clamp, ws_ptr, ws_bytes, max_in_flight, stream) -> None:
-        check(
-            lib().mz_forward(
-                self._h, c_void_p(x_ptr), c_void_p(sr_ptr), c_void_p(qa_ptr) if qa_ptr else None, B, H, W, int(clamp),
-                c_void_p(ws_ptr), ws_bytes, max_in_flight, c_void_p(stream),
-            )
-        )
+        _call("mz_forward", self._h, x_ptr, sr_ptr, qa_ptr or None, B, H, W, int(clamp), ws_ptr, ws_bytes, max_in_flight, stream)
 
     def forward_u8(self, x_ptr, sr_ptr, qa_ptr, B, H, W, ws_ptr, ws_bytes, max_in_flight, stream) -> None:
-        check(
-            lib().mz_forward_u8(
-                self._h, c_void_p(x_ptr), c_void_p(sr_ptr), c_void_p(qa_ptr) if qa_ptr else None, B, H, W,
-                c_void_p(ws_ptr), ws_bytes, max_in_flight, c_void_p(stream),
-            )
-        )
+        _call("mz_forward_u8", self._h, x_ptr, sr_ptr, qa_ptr or None, B, H, W, ws_ptr, ws_bytes, max_in_flight, stream)
 
     def forward_view(self, x_ptr, x_strides, out_ptr, out_strides, qa_ptr, B, H, W, clamp, elem, window, ws_ptr, ws_bytes,
                      max_in_flight, stream) -> None:
         """mz_forward_view: `x_ptr` / `out_ptr` address element (0, 0, 0, 0) of each view (out: of the window), the strides count
         elements (image, channel, row, column; signed); `window` = (y0, x0, h, w) in output pixels or None; `elem` 1 = uint8."""
-        xv, ov = view(x_ptr, x_strides), view(out_ptr, out_strides)
-        win = _window_arg(window)
-        check(
-            lib().mz_forward_view(
-                self._h, byref(xv), byref(ov), c_void_p(qa_ptr) if qa_ptr else None, B, H, W, int(clamp), int(elem), win,
-                c_void_p(ws_ptr), ws_bytes, max_in_flight, c_void_p(stream),
-            )
-        )
+        _call("mz_forward_view", self._h, view(x_ptr, x_strides), view(out_ptr, out_strides), qa_ptr or None, B, H, W, int(clamp), int(elem),
+              _window_arg(window), ws_ptr, ws_bytes, max_in_flight, stream)
 
     def flops_per_image(self, H: int, W: int) -> float:
         return float(lib().mz_flops_per_image(self._h, H, W))
@@ -524,23 +551,22 @@ class Handle:
     def schedule(self, B: int, H: int, W: int, want_qa: bool, cus: int = 256):
         """mz_debug_schedule (host only): the steps of one micro-batch of B images, in launch order, as a list of dicts with
         mz_debug_step's fields (off, bytes: tuples of in, second in, out; kernel: a str or None)."""
-        n = lib().mz_debug_schedule(self._h, B, H, W, int(bool(want_qa)), cus, None, 0)  # how many
-        if n < 0:
-            check(n)
+        n = _count(lib().mz_debug_schedule(self._h, B, H, W, bool(want_qa), cus, None, 0))  # how many
         steps = (MzDebugStep * n)()
-        lib().mz_debug_schedule(self._h, B, H, W, int(bool(want_qa)), cus, steps, n)
+        lib().mz_debug_schedule(self._h, B, H, W, bool(want_qa), cus, steps, n)
         ints = [name for name, _ in MzDebugStep._fields_[:10]]
         return [dict({k: int(getattr(s, k)) for k in ints}, off=tuple(s.off), bytes=tuple(s.bytes),
                      kernel=s.kernel.decode() if s.kernel else None) for s in steps]
 
     def profile_enable(self, on: bool) -> None:
-        check(lib().mz_profile_enable(self._h, int(on)))
+        _call("mz_profile_enable", self._h, int(on))
 
     def profile_dump(self, path: str) -> None:
-        check(lib().mz_profile_dump(self._h, str(path).encode()))
+        _call("mz_profile_dump", self._h, str(path).encode())
 
     def profile_read(self) -> dict:
         vals = [c_double() for _ in range(5)]
-        check(lib().mz_profile_read(self._h, *[byref(v) for v in vals]))
+        _call("mz_profile_read", self._h, *[byref(v) for v in vals])
         keys = ("conv_ms", "conv_flops", "conv_launches", "other_ms", "conv_bytes")
         return {k: v.value for k, v in zip(keys, vals)}
+

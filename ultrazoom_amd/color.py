@@ -19,7 +19,6 @@ from __future__ import annotations
 
 from typing import Optional
 
-import torch
 from torch import Tensor
 
 from . import _ffi
@@ -30,11 +29,6 @@ def rgb_to_y(x: Tensor, standard: str = "bt601", *, clamp: bool = False, out: Op
     `out` (any strides).  `clamp` clamps floating-point results to [0, 1] (uint8 results are always clamped).  x and out must not overlap."""
     code = _ffi.luma_standard(standard)
     elem, B, H, W = _ffi.check_image_batch(x, "rgb_to_y")
-    if out is not None:
-        _ffi.check_same_batch(x, out, (B, 1, H, W))
-    with torch.cuda.device(x.device):
-        stream = torch.cuda.current_stream(x.device)
-        if out is None:
-            out = torch.empty((B, 1, H, W), dtype=x.dtype, device=x.device)
-        _ffi.luma(x.data_ptr(), x.stride(), out.data_ptr(), out.stride(), elem, B, H, W, code, clamp, stream.cuda_stream)
+    with _ffi.image_frame(x, out, (B, 1, H, W)) as (out, _, stream):
+        _ffi.luma(*_ffi.pair(x), *_ffi.pair(out), elem, B, H, W, code, clamp, stream)
     return out

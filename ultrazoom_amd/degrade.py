@@ -56,12 +56,9 @@ def gaussian_blur(x: Tensor, sigma: Union[float, Sequence[float]], out: Optional
             raise ValueError(f"sigma {s}: need 0 <= sigma and int(3 sigma) <= {BLUR_MAX_HALF}")
         if int(3 * s) >= min(H, W):
             raise ValueError(f"sigma {s} needs {int(3 * s)} pixels of reflect padding: a {H} x {W} image is too small")
-    with torch.cuda.device(x.device):
-        stream = torch.cuda.current_stream(x.device).cuda_stream
-        if out is None:
-            out = torch.empty(x.shape, dtype=x.dtype, device=x.device)
-        _run(x, out, sigmas, lambda xv, ov, n, s, b: _ffi.blur(xv.data_ptr(), xv.stride(), ov.data_ptr(), ov.stride(), elem, n, H, W,
-                                                              float(sigma if s is None else s), stream))
+    with _ffi.image_frame(x, out, x.shape) as (out, _, stream):
+        _run(x, out, sigmas, lambda xv, ov, n, s, b: _ffi.blur(*_ffi.pair(xv), *_ffi.pair(ov), elem, n, H, W, float(sigma if s is None else s),
+                                                              stream))
     return out
 
 
@@ -74,12 +71,9 @@ def gaussian_noise(x: Tensor, sigma: Union[float, Sequence[float]], *, seed: int
     for s in ([sigma] if sigmas is None else sigmas):
         if not 0.0 <= float(s) <= 1e6:
             raise ValueError(f"sigma {s}: need 0 <= sigma <= 1e6")
-    with torch.cuda.device(x.device):
-        stream = torch.cuda.current_stream(x.device).cuda_stream
-        if out is None:
-            out = torch.empty(x.shape, dtype=x.dtype, device=x.device)
-        _run(x, out, sigmas, lambda xv, ov, n, s, b: _ffi.noise(xv.data_ptr(), xv.stride(), ov.data_ptr(), ov.stride(), elem, n, H, W,
-                                                               float(sigma if s is None else s), seed, int(offset) + b, stream))
+    with _ffi.image_frame(x, out, x.shape) as (out, _, stream):
+        _run(x, out, sigmas, lambda xv, ov, n, s, b: _ffi.noise(*_ffi.pair(xv), *_ffi.pair(ov), elem, n, H, W, float(sigma if s is None else s),
+                                                               seed, int(offset) + b, stream))
     return out
 
 
@@ -92,14 +86,10 @@ def jpeg(x: Tensor, quality: Union[int, Sequence[int]], out: Optional[Tensor] = 
     for q in ([quality] if qualities is None else qualities):
         if int(q) != q or not 1 <= int(q) <= 100:
             raise ValueError(f"quality is an integer in 1..100, got {q!r}")
-    with torch.cuda.device(x.device):
-        stream = torch.cuda.current_stream(x.device).cuda_stream
-        need = _ffi.jpeg_workspace_bytes(B if qualities is None else 1, H, W)
-        ws = torch.empty(need, dtype=torch.uint8, device=x.device)  # calls on one stream run one after the other: one workspace serves all
-        if out is None:
-            out = torch.empty(x.shape, dtype=x.dtype, device=x.device)
-        _run(x, out, qualities, lambda xv, ov, n, q, b: _ffi.jpeg(xv.data_ptr(), xv.stride(), ov.data_ptr(), ov.stride(), elem, n, H, W,
-                                                                 int(quality if q is None else q), ws.data_ptr(), need, stream))
+    # calls on one stream run one after the other: one workspace serves all
+    with _ffi.image_frame(x, out, x.shape, lambda: _ffi.jpeg_workspace_bytes(B if qualities is None else 1, H, W)) as (out, ws, stream):
+        _run(x, out, qualities, lambda xv, ov, n, q, b: _ffi.jpeg(*_ffi.pair(xv), *_ffi.pair(ov), elem, n, H, W,
+                                                                 int(quality if q is None else q), *ws, stream))
     return out
 
 
@@ -129,8 +119,7 @@ class Degradation:
     seed: int = 0
 
     def __post_init__(self):
-        if self.filter not in ("bicubic", "bilinear"):
-            raise ValueError(f"filter is 'bicubic' or 'bilinear', got {self.filter!r}")
+        _ffi.resize_filter(self.filter)
         for name in ("blur", "noise", "compression"):
             lo, hi = getattr(self, name)
             if not 0.0 <= lo < hi:

@@ -40,14 +40,8 @@ def dihedral(x: Tensor, k: int, out: Optional[Tensor] = None) -> Tensor:
     k = int(k)
     if not 0 <= k <= 7:
         raise ValueError(f"an orientation is 0..7, got {k}")
-    want = (B, 3, W, H) if k & 4 else (B, 3, H, W)
-    if out is not None:
-        _ffi.check_same_batch(x, out, want)
-    with torch.cuda.device(x.device):
-        stream = torch.cuda.current_stream(x.device)
-        if out is None:
-            out = torch.empty(want, dtype=x.dtype, device=x.device)
-        _ffi.dihedral(x.data_ptr(), x.stride(), out.data_ptr(), out.stride(), elem, B, H, W, k, stream.cuda_stream)
+    with _ffi.image_frame(x, out, (B, 3, W, H) if k & 4 else (B, 3, H, W)) as (out, _, stream):
+        _ffi.dihedral(*_ffi.pair(x), *_ffi.pair(out), elem, B, H, W, k, stream)
     return out
 
 
@@ -89,8 +83,6 @@ def upscale_ensemble(model, x: Tensor, n: int = 8, out: Optional[Tensor] = None,
         raise ValueError(f"n is 1, 2, 4 or 8 orientations, got {n}")
     r = model.upscale_ratio
     Ho, Wo = r * H, r * W
-    if out is not None:
-        _ffi.check_same_batch(x, out, (B, 3, Ho, Wo))
 
     def run(xk: Tensor, dst: Tensor) -> None:  # one pass: dst = U(xk)
         if tile is None:
@@ -100,13 +92,10 @@ def upscale_ensemble(model, x: Tensor, n: int = 8, out: Optional[Tensor] = None,
 
             upscale_tiled(model, xk, tile, out=dst)
 
-    with torch.cuda.device(x.device):
-        if out is None:
-            out = torch.empty((B, 3, Ho, Wo), dtype=x.dtype, device=x.device)
+    with _ffi.image_frame(x, out, (B, 3, Ho, Wo)) as (out, _, stream):
         if n == 1:
             run(x, out)
             return out
-        stream = torch.cuda.current_stream(x.device).cuda_stream
         chunks = plan_chunks(B, Ho, Wo, x.element_size(), workspace_bytes)
         b_max = chunks[0][1]
         acc = torch.empty(b_max * 3 * Ho * Wo, dtype=torch.float32, device=x.device)
@@ -120,6 +109,6 @@ def upscale_ensemble(model, x: Tensor, n: int = 8, out: Optional[Tensor] = None,
                 xk = xc if k == 0 else dihedral(xc, k, out=turned[: nb * 3 * hk * wk].view(nb, 3, hk, wk))
                 yk = scratch[: nb * 3 * Ho * Wo].view(nb, 3, r * hk, r * wk)
                 run(xk, yk)
-                _ffi.ensemble_add(yk.data_ptr(), yk.stride(), elem, nb, Ho, Wo, k, k == 0, acc.data_ptr(), acc_bytes, stream)
-            _ffi.ensemble_finish(oc.data_ptr(), oc.stride(), elem, nb, Ho, Wo, n, True, None, acc.data_ptr(), acc_bytes, stream)
+                _ffi.ensemble_add(*_ffi.pair(yk), elem, nb, Ho, Wo, k, k == 0, acc.data_ptr(), acc_bytes, stream)
+            _ffi.ensemble_finish(*_ffi.pair(oc), elem, nb, Ho, Wo, n, True, None, acc.data_ptr(), acc_bytes, stream)
     return out

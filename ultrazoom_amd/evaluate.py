@@ -34,6 +34,10 @@ import torch
 import torch.nn.functional as F
 from torch import Tensor
 
+from ._ffi import MZ_LUMA_STANDARDS, MZ_METRIC_MIN_SIZE, luma_standard, resize_filter  # names and sizes only: nothing here calls the library
+
+VIF_MIN_SIZE = MZ_METRIC_MIN_SIZE["vif"]
+
 
 class PSNR:
     def __init__(self, data_range: float = 1.0):
@@ -117,8 +121,8 @@ def vif_per_image(pred: Tensor, target: Tensor, sigma_n_sq: float = 2.0) -> Tens
     """Pixel-domain visual information fidelity of each image of a [B, C, H, W] batch (mean over channels)."""
     if pred.shape != target.shape or pred.dim() != 4:
         raise ValueError("expected two [B, C, H, W] tensors of one shape")
-    if pred.shape[-1] < 41 or pred.shape[-2] < 41:
-        raise ValueError(f"VIF needs images of at least 41 x 41 pixels, got {tuple(pred.shape[-2:])}")
+    if min(pred.shape[-2:]) < VIF_MIN_SIZE:
+        raise ValueError(f"VIF needs images of at least {VIF_MIN_SIZE} x {VIF_MIN_SIZE} pixels, got {tuple(pred.shape[-2:])}")
     eps = 1e-10
     B, C = pred.shape[:2]
     p = pred.double().reshape(B * C, 1, *pred.shape[2:])
@@ -176,7 +180,7 @@ LUMA_COEFFS = {"bt601": (16.0 / 255.0, 65.481 / 255.0, 128.553 / 255.0, 24.966 /
 
 
 def _check_luma(luma) -> None:
-    if luma is not None and luma not in LUMA_COEFFS:
+    if luma is not None and luma not in MZ_LUMA_STANDARDS:
         raise ValueError(f"luma is None, 'bt601' (studio range) or 'full' (full range), got {luma!r}")
 
 
@@ -184,8 +188,7 @@ def luma_plane(x: Tensor, standard: str = "bt601") -> Tensor:
     """The float64 Y plane [B, 1, H, W] of a [B, 3, H, W] tensor (R, G, B): off + kr R + kg G + kb B, added in this order, in plain torch
     arithmetic wherever the tensor lives (a product is rounded before it is added: the kernels fuse the two, which moves Y by at most
     three roundings of 2^-54).  A uint8 value v means v / 255."""
-    if standard not in LUMA_COEFFS:
-        raise ValueError(f"luma standard is 'bt601' (studio range) or 'full' (full range), got {standard!r}")
+    luma_standard(standard)
     if x.dim() != 4 or x.shape[1] != 3:
         raise ValueError(f"expected a [B, 3, H, W] tensor, got {tuple(x.shape)}")
     off, kr, kg, kb = LUMA_COEFFS[standard]
@@ -203,8 +206,57 @@ def _measured(img: Tensor, luma, shave: int) -> Tensor:
     return img if luma is None else luma_plane(img, luma)
 
 
-def _bicubic_keys(res: dict) -> dict:
-    return {"bicubic_" + k: res[k] for k in ("psnr", "ssim", "vif")}
+class TorchMeters:
+    """The three meters above behind the `update(pred, target)` / `compute()` of `metrics.MetricsAccumulator`, with its `luma` and
+    `shave`; VIF takes the updates whose measured images still have 41 x 41 pixels."""
+
+    def __init__(self, luma: Optional[str] = None, shave: int = 0):
+        self.luma, self.shave = luma, shave
+        self.psnr, self.ssim, self.vif = PSNR(1.0), SSIM(), VIF()
+
+    def update(self, pred: Tensor, target: Tensor) -> None:
+        target, pred = _measured(target, self.luma, self.shave), _measured(pred, self.luma, self.shave)
+        self.psnr.update(pred, target)
+        self.ssim.update(pred, target)
+        if min(target.shape[-2:]) >= VIF_MIN_SIZE:
+            self.vif.update(pred, target)
+
+    def compute(self) -> dict:
+        return {"psnr": self.psnr.compute(), "ssim": self.ssim.compute(), "vif": self.vif.compute() if self.vif.n else None}
+
+
+def _meters(backend: str, luma, shave: int):
+    if backend == "hip":
+        from .metrics import MetricsAccumulator
+
+        return MetricsAccumulator(1.0, luma=luma, shave=shave)
+    return TorchMeters(luma, shave)
+
+
+def _evaluate(batches, step, backend: str, baseline: bool, luma, shave: int, extra_key: Optional[str] = None) -> dict:
+    """The one loop.  step(batch, images so far) -> (input, prediction, target, per-batch differences or None).  The meters of `backend`
+    take prediction and target; with `baseline` a second set takes the bicubic enlargement of the input.  With `extra_key` the mean square
+    of all the differences becomes that key of the result: summed on the device and read in the meters' one read, after the loop."""
+    meters, base = _meters(backend, luma, shave), _meters(backend, luma, shave) if baseline else None
+    sq, count, n = None, 0, 0
+    for batch in batches:
+        x, pred, target, d = step(batch, n)
+        meters.update(pred, target)
+        if baseline:
+            base.update(bicubic_baseline(x, target.shape[-2:], backend), target)
+        if d is not None:
+            sq = (d * d).sum() if sq is None else sq + (d * d).sum()
+            count += d.numel()
+        n += x.shape[0]
+    if extra_key is None:
+        res = meters.compute()
+    elif sq is None:
+        res = {**meters.compute(), extra_key: float("nan")}
+    else:
+        res, (total,) = meters.compute(extra=sq.reshape(1))
+        res[extra_key] = total / count
+    res["images"] = n
+    return {**res, **{"bicubic_" + k: v for k, v in base.compute().items()}} if baseline else res  # (a second read, still after the loop)
 
 
 def bicubic_baseline(x: Tensor, size, backend: str = "torch") -> Tensor:
@@ -241,42 +293,19 @@ def evaluate(model, pairs: Iterable[Tuple[Tensor, Tensor]], backend: str = "torc
     _check_luma(luma)
     predict = model.upscale
     if ensemble != 1:
-        if ensemble not in (2, 4, 8):
+        from .ensemble import ORIENTATIONS, upscale_ensemble
+
+        if ensemble not in ORIENTATIONS:
             raise ValueError(f"ensemble is 1, 2, 4 or 8 orientations, got {ensemble!r}")
-        from .ensemble import upscale_ensemble
 
         def predict(x):
             return upscale_ensemble(model, x, n=ensemble)
-    if backend == "hip":
-        from .metrics import MetricsAccumulator
 
-        acc, base = MetricsAccumulator(1.0, luma=luma, shave=shave), MetricsAccumulator(1.0, luma=luma, shave=shave)
-        n = 0
-        for x, y in pairs:
-            acc.update(predict(x), y)
-            if baseline:
-                base.update(bicubic_baseline(x, y.shape[-2:], "hip"), y)
-            n += x.shape[0]
-        res = {**acc.compute(), "images": n}
-        return {**res, **_bicubic_keys(base.compute())} if baseline else res
-    meters = [(PSNR(1.0), SSIM(), VIF())] + ([(PSNR(1.0), SSIM(), VIF())] if baseline else [])
-    n = 0
-    for x, y in pairs:
-        images = [predict(x)] + ([bicubic_baseline(x, y.shape[-2:])] if baseline else [])
-        y = _measured(y, luma, shave)
-        for (psnr, ssim, vif), img in zip(meters, images):
-            img = _measured(img, luma, shave)
-            psnr.update(img, y)
-            ssim.update(img, y)
-            if min(y.shape[-2:]) >= 41:
-                vif.update(img, y)
-        n += x.shape[0]
-    out = [{"psnr": psnr.compute(), "ssim": ssim.compute(), "vif": vif.compute() if vif.n else None} for psnr, ssim, vif in meters]
-    res = {**out[0], "images": n}
-    return {**res, **_bicubic_keys(out[1])} if baseline else res
+    def step(pair, n):
+        x, y = pair
+        return x, predict(x), y, None
 
-
-_INTERP_MODES = ("bicubic", "bilinear")
+    return _evaluate(pairs, step, backend, baseline, luma, shave)
 
 
 @torch.inference_mode()
@@ -289,8 +318,7 @@ def lr_from_hr(hr: Tensor, ratio: int, filter: str = "bicubic", backend: str = "
     (blur, noise, JPEG: transforms.py) is `ultrazoom_amd.degrade`: `Degradation.apply` runs this resize between them."""
     if backend not in ("torch", "hip"):
         raise ValueError(f"backend is 'torch' or 'hip', got {backend!r}")
-    if filter not in _INTERP_MODES:
-        raise ValueError(f"filter is 'bicubic' or 'bilinear', got {filter!r}")
+    resize_filter(filter)
     ratio = int(ratio)
     if hr.dim() != 4 or ratio < 1 or hr.shape[-2] < ratio or hr.shape[-1] < ratio:
         raise ValueError(f"expected a [B, C, H, W] tensor of at least {ratio} x {ratio} pixels, got {tuple(hr.shape)}")
@@ -328,7 +356,9 @@ def evaluate_hr(model, hr_batches: Iterable[Tensor], *, filter: str = "bicubic",
                         luma, shave)
     if backend != "hip":
         raise ValueError("degrade runs on the device only: use backend='hip'. There is no CPU path.")
-    if ensemble not in (1, 2, 4, 8):
+    from .ensemble import ORIENTATIONS
+
+    if ensemble not in ORIENTATIONS:
         raise ValueError(f"ensemble is 1, 2, 4 or 8 orientations, got {ensemble}")
     return _evaluate_degraded(model, hr_batches, degrade, int(ensemble), bool(baseline), luma, shave)
 
@@ -336,28 +366,16 @@ def evaluate_hr(model, hr_batches: Iterable[Tensor], *, filter: str = "bicubic",
 @torch.inference_mode()
 def _evaluate_degraded(model, hr_batches: Iterable[Tensor], degrade, ensemble: int = 1, baseline: bool = False, luma: Optional[str] = None,
                        shave: int = 0) -> dict:
-    from .metrics import MetricsAccumulator
-
-    acc, base = MetricsAccumulator(1.0, luma=luma, shave=shave), MetricsAccumulator(1.0, luma=luma, shave=shave)
-    sq, count, n = None, 0, 0
-    for hr in hr_batches:
+    def step(hr, n):
         lr, target, want = degrade.apply(hr, model.upscale_ratio, index=n)
         if ensemble == 1:
             sr, qa = model.forward(lr)
-            acc.update(sr.clamp(0, 1), target)
+            sr = sr.clamp(0, 1)
         else:
             from .ensemble import upscale_ensemble
 
             qa = model.predict_degredation(lr)
-            acc.update(upscale_ensemble(model, lr, n=ensemble), target)
-        if baseline:
-            base.update(bicubic_baseline(lr, target.shape[-2:], "hip"), target)
-        d = qa.double() - want.double()
-        sq = (d * d).sum() if sq is None else sq + (d * d).sum()
-        count += d.numel()
-        n += hr.shape[0]
-    extra = _bicubic_keys(base.compute()) if baseline else {}  # (a second read, still after the loop)
-    if sq is None:
-        return {**acc.compute(), "deg_l2": float("nan"), "images": 0, **extra}
-    res, (total,) = acc.compute(extra=sq.reshape(1))  # the one read of the run
-    return {**res, "deg_l2": total / count, "images": n, **extra}
+            sr = upscale_ensemble(model, lr, n=ensemble)
+        return lr, sr, target, qa.double() - want.double()
+
+    return _evaluate(hr_batches, step, "hip", baseline, luma, shave, extra_key="deg_l2")

@@ -12,7 +12,6 @@ from __future__ import annotations
 
 from typing import Optional, Tuple
 
-import torch
 from torch import Tensor
 
 from . import _ffi
@@ -43,12 +42,6 @@ def interpolate(x: Tensor, size: Optional[Tuple[int, int]] = None, scale_factor:
     if scale_factor is not None:
         size = (H * scale_factor, W * scale_factor)
     Hout, Wout, window, want = _ffi.output_shape(B, size, window)
-    if out is not None:
-        _ffi.check_same_batch(x, out, want)
-    with torch.cuda.device(x.device):
-        stream = torch.cuda.current_stream(x.device)
-        if out is None:
-            out = torch.empty(want, dtype=x.dtype, device=x.device)
-        _ffi.interpolate(x.data_ptr(), x.stride(), out.data_ptr(), out.stride(), elem, B, H, W, Hout, Wout, _MODES[mode], clamp, window,
-                         stream.cuda_stream)
+    with _ffi.image_frame(x, out, want) as (out, _, stream):
+        _ffi.interpolate(*_ffi.pair(x), *_ffi.pair(out), elem, B, H, W, Hout, Wout, _MODES[mode], clamp, window, stream)
     return out

@@ -35,10 +35,9 @@ def shaved(x: Tensor, shave: int) -> Tensor:
 
 
 def _check_sizes(which, H: int, W: int) -> None:
-    if "ssim" in which and min(H, W) < 11:
-        raise ValueError(f"SSIM needs images of at least 11 x 11 pixels, got {(H, W)}")
-    if "vif" in which and min(H, W) < 41:
-        raise ValueError(f"VIF needs images of at least 41 x 41 pixels, got {(H, W)}")
+    for name, least in _ffi.MZ_METRIC_MIN_SIZE.items():
+        if name in which and min(H, W) < least:
+            raise ValueError(f"{name.upper()} needs images of at least {least} x {least} pixels, got {(H, W)}")
 
 
 def image_metrics(pred: Tensor, target: Tensor, *, which: Iterable[str] = ("psnr", "ssim", "vif"), data_range: Optional[float] = None,
@@ -63,18 +62,15 @@ def image_metrics(pred: Tensor, target: Tensor, *, which: Iterable[str] = ("psnr
     H, W = pred.shape[-2:]
     _check_sizes(which, H, W)
     bits = sum(_BITS[w] for w in set(which))
-    with torch.cuda.device(pred.device):
-        stream = torch.cuda.current_stream(pred.device)
-        need = _ffi.metrics_workspace_bytes(B, H, W, bits) if luma is None else _ffi.metrics_luma_workspace_bytes(B, H, W, bits)
-        ws = torch.empty(need, dtype=torch.uint8, device=pred.device)
+    need = _ffi.metrics_workspace_bytes if luma is None else _ffi.metrics_luma_workspace_bytes
+    with _ffi.image_frame(pred, need=lambda: need(B, H, W, bits)) as (_, ws, stream):
         out = torch.zeros((B, _ffi.MZ_METRIC_SLOTS), dtype=torch.float64, device=pred.device)
         rng = -1.0 if data_range is None else float(data_range)
+        views = (*_ffi.pair(pred), *_ffi.pair(target))
         if luma is None:
-            _ffi.metrics(pred.data_ptr(), pred.stride(), target.data_ptr(), target.stride(), elem, B, H, W, bits, rng, float(sigma_n_sq),
-                         out.data_ptr(), ws.data_ptr(), need, stream.cuda_stream)
+            _ffi.metrics(*views, elem, B, H, W, bits, rng, float(sigma_n_sq), out.data_ptr(), *ws, stream)
         else:
-            _ffi.metrics_luma(pred.data_ptr(), pred.stride(), target.data_ptr(), target.stride(), elem, B, H, W, bits, standard, rng,
-                              float(sigma_n_sq), out.data_ptr(), ws.data_ptr(), need, stream.cuda_stream)
+            _ffi.metrics_luma(*views, elem, B, H, W, bits, standard, rng, float(sigma_n_sq), out.data_ptr(), *ws, stream)
     res = {}
     if "psnr" in which:
         res["sq_err"], res["numel"] = out[:, 0], out[:, 1]
@@ -105,7 +101,7 @@ class MetricsAccumulator:
         self.vif_n = 0
 
     def update(self, pred: Tensor, target: Tensor) -> None:
-        with_vif = min(shaved(pred, self.shave).shape[-2:]) >= 41
+        with_vif = min(shaved(pred, self.shave).shape[-2:]) >= _ffi.MZ_METRIC_MIN_SIZE["vif"]
         r = image_metrics(pred, target, which=("psnr", "ssim", "vif") if with_vif else ("psnr", "ssim"), data_range=self.data_range,
                           sigma_n_sq=self.sigma_n_sq, luma=self.luma, shave=self.shave)
         vif = r["vif"].sum() if with_vif else torch.zeros((), dtype=torch.float64, device=pred.device)

@@ -531,24 +531,10 @@ class _Engine:
         self._last_done.record(stream)
         self._last_stream = stream
 
-    def run(self, x: Tensor, clamp: bool, want_qa: bool, max_in_flight: int):
-        B, _, H, W = x.shape
-        r = self.config["upscale_ratio"]
-        with torch.cuda.device(self.device):
-            stream = torch.cuda.current_stream(self.device)
-            ws = self._workspace_for(self.handle.workspace_bytes(B, H, W, max_in_flight), stream)
-            sr = torch.empty((B, 3, H * r, W * r), dtype=self.dtype, device=self.device)
-            qa = torch.empty((B, self.config["num_deg_features"]), dtype=torch.float32, device=self.device) if want_qa else None
-            self.handle.forward(
-                x.data_ptr(), sr.data_ptr(), qa.data_ptr() if want_qa else 0, B, H, W, clamp,
-                ws.data_ptr(), ws.numel(), max_in_flight, stream.cuda_stream,
-            )
-            self._mark_done(stream)
-        return sr, qa
-
-    def run_view(self, x: Tensor, out: Optional[Tensor], window, clamp: bool, want_qa: bool, max_in_flight: int):
-        """The same through mz_forward_view: x (and out, when given) with any strides, read and written in place.  uint8 tensors
-        take the fused uint8 ends.  Without `out` the result is a new dense NCHW tensor."""
+    def _forward(self, x: Tensor, out: Optional[Tensor], want_qa: bool, max_in_flight: int, call):
+        """The one body of run, run_u8 and run_view: on the engine's device and the current stream, with the shared workspace,
+        call(out, address of the quality output or 0, (B, H, W), (workspace address, its bytes, max_in_flight, stream)) is the entry's
+        Handle call.  Without `out` the result is a new dense NCHW tensor of x's dtype.  Returns (out, the quality output or None)."""
         B, _, H, W = x.shape
         r = self.config["upscale_ratio"]
         with torch.cuda.device(self.device):
@@ -557,21 +543,24 @@ class _Engine:
             if out is None:
                 out = torch.empty((B, 3, H * r, W * r), dtype=x.dtype, device=self.device)
             qa = torch.empty((B, self.config["num_deg_features"]), dtype=torch.float32, device=self.device) if want_qa else None
-            self.handle.forward_view(
-                x.data_ptr(), x.stride(), out.data_ptr(), out.stride(), qa.data_ptr() if want_qa else 0, B, H, W, clamp,
-                1 if x.dtype == torch.uint8 else 0, window, ws.data_ptr(), ws.numel(), max_in_flight, stream.cuda_stream,
-            )
+            call(out, qa.data_ptr() if want_qa else 0, (B, H, W), (ws.data_ptr(), ws.numel(), max_in_flight, stream.cuda_stream))
             self._mark_done(stream)
         return out, qa
 
+    def run(self, x: Tensor, clamp: bool, want_qa: bool, max_in_flight: int):
+        """mz_forward: x dense NCHW of the engine's dtype."""
+        return self._forward(x, None, want_qa, max_in_flight, lambda sr, qa, shape, tail:
+                             self.handle.forward(x.data_ptr(), sr.data_ptr(), qa, *shape, clamp, *tail))
+
+    def run_view(self, x: Tensor, out: Optional[Tensor], window, clamp: bool, want_qa: bool, max_in_flight: int):
+        """The same through mz_forward_view: x (and out, when given) with any strides, read and written in place.  uint8 tensors
+        take the fused uint8 ends."""
+        return self._forward(x, out, want_qa, max_in_flight, lambda out, qa, shape, tail:
+                             self.handle.forward_view(*_ffi.pair(x), *_ffi.pair(out), qa, *shape, clamp, 1 if x.dtype == torch.uint8 else 0,
+                                                      window, *tail))
+
     def run_u8(self, x: Tensor, max_in_flight: int) -> Tensor:
-        B, _, H, W = x.shape
-        r = self.config["upscale_ratio"]
-        with torch.cuda.device(self.device):
-            stream = torch.cuda.current_stream(self.device)
-            ws = self._workspace_for(self.handle.workspace_bytes(B, H, W, max_in_flight), stream)
-            sr = torch.empty((B, 3, H * r, W * r), dtype=torch.uint8, device=self.device)
-            self.handle.forward_u8(x.data_ptr(), sr.data_ptr(), 0, B, H, W, ws.data_ptr(), ws.numel(), max_in_flight,
-                                   stream.cuda_stream)
-            self._mark_done(stream)
-        return sr
+        """mz_forward_u8: x dense NCHW uint8."""
+        return self._forward(x, None, False, max_in_flight, lambda sr, qa, shape, tail:
+                             self.handle.forward_u8(x.data_ptr(), sr.data_ptr(), qa, *shape, *tail))[0]
+

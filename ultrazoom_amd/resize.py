@@ -10,12 +10,10 @@ from __future__ import annotations
 
 from typing import Optional, Tuple
 
-import torch
 from torch import Tensor
 
 from . import _ffi
 
-_FILTERS = {"bicubic": _ffi.MZ_RESIZE_BICUBIC, "bilinear": _ffi.MZ_RESIZE_BILINEAR}
 MAX_RATIO = 16  # an axis shrinks at most this much in one call (include/mewzoom_hip.h)
 
 
@@ -27,22 +25,14 @@ def resize(x: Tensor, size: Tuple[int, int], *, filter: str = "bicubic", clamp: 
     pixels of the Hout x Wout result selects the part that is computed and stored, `out` ([B, 3, h, w], or [B, 3, Hout, Wout] without a
     window; any strides, x's dtype) receives it in place: a window of a result equals that part of the whole result bit for bit.  An
     axis may shrink by at most 16; enlarging is not bounded.  x and out must not overlap."""
-    if filter not in _FILTERS:
-        raise ValueError(f"filter is 'bicubic' or 'bilinear', got {filter!r}")
+    code = _ffi.resize_filter(filter)
     elem, B, H, W = _ffi.check_image_batch(x, "resize")
+
     def ratio_check(Hout, Wout):
         if H > MAX_RATIO * Hout or W > MAX_RATIO * Wout:
             raise ValueError(f"{(H, W)} -> {(Hout, Wout)} shrinks an axis by more than {MAX_RATIO}: resize in two steps")
 
     Hout, Wout, window, want = _ffi.output_shape(B, size, window, ratio_check)
-    if out is not None:
-        _ffi.check_same_batch(x, out, want)
-    with torch.cuda.device(x.device):
-        stream = torch.cuda.current_stream(x.device)
-        need = _ffi.resize_workspace_bytes(H, W, Hout, Wout, _FILTERS[filter])
-        ws = torch.empty(need, dtype=torch.uint8, device=x.device)
-        if out is None:
-            out = torch.empty(want, dtype=x.dtype, device=x.device)
-        _ffi.resize(x.data_ptr(), x.stride(), out.data_ptr(), out.stride(), elem, B, H, W, Hout, Wout, _FILTERS[filter], clamp,
-                    window, ws.data_ptr(), need, stream.cuda_stream)
+    with _ffi.image_frame(x, out, want, lambda: _ffi.resize_workspace_bytes(H, W, Hout, Wout, code)) as (out, ws, stream):
+        _ffi.resize(*_ffi.pair(x), *_ffi.pair(out), elem, B, H, W, Hout, Wout, code, clamp, window, *ws, stream)
     return out
