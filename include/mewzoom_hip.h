@@ -94,14 +94,15 @@ int mz_weights_complete(const mz_handle* h);
  * micro-batches of at most `max_images_in_flight` images (0 = library default), so memory does
  * not grow beyond that.
  *
- * What a call touches (mz_forward, mz_forward_u8, mz_forward_view, mz_metrics, mz_metrics_luma, mz_luma, mz_resize, mz_interpolate, mz_blur, mz_noise,
+ * What a call touches (mz_forward, mz_forward_u8, mz_forward_view, mz_metrics, mz_metrics_luma, mz_luma, mz_yuv420_to_rgb, mz_rgb_to_yuv420,
+ * mz_resize, mz_interpolate, mz_blur, mz_noise,
  * mz_jpeg and the mz_op_* entries alike): it READS only its
  * input tensors -- the elements its shape and strides name, never a byte next to them -- and the workspace bytes it has itself
  * written during that call; it WRITES only its outputs (of a view: the elements of the window) and its workspace, never an input.
  * The workspace needs no initialisation and carries nothing from one call to the next: whatever it holds, NaN patterns included,
  * the results have the same bits.  mz_metrics and mz_metrics_luma write the `out` slots of the metrics `which` selects and leave the
  * others alone.  tests/test_poison_ops_gpu.py, tests/test_poison_forward_gpu.py, tests/test_metrics_gpu.py and
- * tests/test_poison_color_gpu.py hold every entry to this.
+ * tests/test_poison_color_gpu.py, tests/test_poison_yuv_gpu.py hold every entry to this.
  *
  * Number range (the convolution, mix, stem and head kernels, in every storage type): subnormals of the storage type are operands and
  * results like any other value -- nothing is flushed on the way in, in the matrix unit's operands, or at the store.  Accumulation is
@@ -139,7 +140,8 @@ int mz_forward_u8(mz_handle* h, const uint8_t* x, uint8_t* out_sr, float* out_qa
  * and out, or between elements of out, is the caller's responsibility and is not checked (beyond refusing an output stride of 0;
  * mz_blur, mz_noise and mz_jpeg also compare the two byte ranges).
  *
- * THE VIEW REFUSALS.  Every entry that takes views (mz_forward_view, mz_metrics, mz_metrics_luma, mz_luma, mz_resize, mz_interpolate, mz_blur,
+ * THE VIEW REFUSALS.  Every entry that takes views (mz_forward_view, mz_metrics, mz_metrics_luma, mz_luma, mz_yuv420_to_rgb, mz_rgb_to_yuv420,
+ * mz_resize, mz_interpolate, mz_blur,
  * mz_noise, mz_jpeg, mz_dihedral, mz_ensemble_add, mz_ensemble_finish) returns
  * MZ_ERR_INVALID_ARGUMENT, before anything touches the GPU, for: a null view or null data; an `elem` outside the entry's codes; a view
  * that is WRITTEN whose channel, row or column stride is 0, or whose image stride is 0 when B > 1 (mz_luma's one-channel output: its
@@ -263,6 +265,37 @@ int mz_metrics_luma(const mz_image_view* pred, const mz_image_view* target, int 
                     double data_range, double sigma_n_sq, double* out_dev, void* workspace, size_t workspace_bytes, void* hip_stream);
 /* Host only: {off, kr, kg, kb} of a standard, the constants the kernels compile. */
 int mz_debug_luma_coeffs(int standard, double out[4]);
+
+/* ---- 8-bit 4:2:0 YCbCr frames: no reference counterpart; what video decoders and encoders exchange (NV12, NV21, I420, YV12).
+ *      ultrazoom_amd/csrc/mz_yuv.h is the one statement of the arithmetic -------------------------------------------------------------
+ * The planes are three views of uint8 CODE VALUES 0..255: y of [B,1,H,W], cb and cr of [B,1,Hc,Wc] with Hc = ceil(H/2), Wc = ceil(W/2)
+ * (their channel strides are never used).  A layout is a choice of views, not of kernels: I420 / YV12 are two planar chroma views
+ * (column stride 1), NV12 / NV21 two views with column stride 2 one byte apart.  Odd H and W are legal; indices clamp at the edges.
+ * matrix   0 "bt601" (Kr = 0.299, Kb = 0.114), 1 "bt709" (Kr = 0.2126, Kb = 0.0722); Kg = (1 - Kr) - Kb
+ * range    0 "limited" (Y 16..235, chroma 16..240: Yoff = 16, Sy = 219, Sc = 224), 1 "full" (Yoff = 0, Sy = Sc = 255)
+ * siting   0 "left" (a chroma sample sits on luma column 2i, between luma rows 2j and 2j + 1: MPEG-2, H.264, HEVC),
+ *          1 "center" (in the middle of its 2 x 2 luma block: JPEG, MPEG-1)
+ * Float64 throughout, sums in a fixed order, one rounding on store.
+ *
+ * mz_yuv420_to_rgb: chroma is upsampled by the 3/4, 1/4 taps of the siting (vertically; horizontally the same for "center", the sample
+ * itself and the mean of two for "left"), then R = yn + a_r crn, B = yn + a_b cbn, G = yn + g_r crn + g_b cbn on yn = (Y - Yoff) / Sy,
+ * cbn = (cb - 128) / Sc; out, a view of [B,3,H,W] of element type elem_out (0..3), is stored as mz_luma stores: float types clamped to
+ * [0, 1] when clamp != 0, then one rounding; uint8 always clamps, then * 255 + 0.5, then truncates.  Reads exactly the plane elements
+ * named, writes exactly B 3 H W elements.
+ * mz_rgb_to_yuv420: y = Kr r + Kg g + Kb b of the [B,3,H,W] view x (elem 0..3), pb = (b - y) / (2 (1 - Kb)), pr likewise; the Y code is
+ * Sy y + Yoff clamped to [0, 255] (no 16..235 clamp), + 0.5, truncated; a chroma sample is the siting's filter over the UNROUNDED pb, pr
+ * of its 2 rows x 2 (center) or 3 (left) columns, Sc f + 128 clamped to [0, 255], + 0.5, truncated.  Writes every plane element once.
+ * Both are stateless, need no workspace and enqueue on the given stream.
+ * Refuse the view refusals above (the written views: out; y, cb and cr), and: B < 1 or > 65535; H or W < 1 or > 2^28; a matrix, range or
+ * siting outside 0..1; ANY overlap of the byte range of the RGB view with that of a plane.  mz_rgb_to_yuv420 also refuses two planes of
+ * which an image of one shares bytes with an image of the other -- except that Cb and Cr may INTERLEAVE: identical strides, a column
+ * stride of at least 2 and base addresses at least one byte but less than the column stride apart.  The three codes are checked last. */
+int mz_yuv420_to_rgb(const mz_image_view* y, const mz_image_view* cb, const mz_image_view* cr, const mz_image_view* out, int elem_out,
+                     int B, int H, int W, int matrix, int range, int siting, int clamp, void* hip_stream);
+int mz_rgb_to_yuv420(const mz_image_view* x, int elem, const mz_image_view* y, const mz_image_view* cb, const mz_image_view* cr,
+                     int B, int H, int W, int matrix, int range, int siting, void* hip_stream);
+/* Host only: {Yoff, 1/Sy, 1/Sc, a_r, a_b, g_r, g_b, Sy, Sc} of a matrix and a range, the constants the kernels compile. */
+int mz_debug_yuv_coeffs(int matrix, int range, double out[9]);
 
 /* ---- antialiased resampling to any size: no reference counterpart in `model.py`; stands in for torchvision's antialiased `Resize`
  *      as the reference's `data.py:91-108` uses it (HR -> LR for validation), and serves "a 3X or a true-4K result from a 4X model"

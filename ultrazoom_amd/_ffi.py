@@ -31,6 +31,9 @@ MZ_RESIZE_FILTERS = {"bicubic": MZ_RESIZE_BICUBIC, "bilinear": MZ_RESIZE_BILINEA
 MZ_RESIZE_MAX_TAPS = 66  # taps of one output at the largest accepted ratio (n_in / n_out = 16, bicubic)
 MZ_INTERP_NEAREST, MZ_INTERP_BILINEAR, MZ_INTERP_BICUBIC = 0, 1, 2
 MZ_LUMA_STANDARDS = {"bt601": 0, "full": 1}  # studio range (MATLAB rgb2ycbcr, basicsr) / full range (JFIF, Pillow's "L")
+MZ_YUV_MATRICES = {"bt601": 0, "bt709": 1}
+MZ_YUV_RANGES = {"limited": 0, "full": 1}
+MZ_YUV_SITINGS = {"left": 0, "center": 1}  # MPEG-2 / H.264 / HEVC; JPEG / MPEG-1
 
 
 class MzConfig(Structure):
@@ -102,6 +105,11 @@ int mz_metrics_luma_workspace_bytes(int B, int H, int W, int which, size_t* byte
 int mz_metrics_luma(const mz_image_view* pred, const mz_image_view* target, int elem, int B, int H, int W, int which, int standard,
     double data_range, double sigma_n_sq, double* out_dev, void* workspace, size_t workspace_bytes, void* hip_stream);
 int mz_debug_luma_coeffs(int standard, double out[4]);
+int mz_yuv420_to_rgb(const mz_image_view* y, const mz_image_view* cb, const mz_image_view* cr, const mz_image_view* out, int elem_out,
+    int B, int H, int W, int matrix, int range, int siting, int clamp, void* hip_stream);
+int mz_rgb_to_yuv420(const mz_image_view* x, int elem, const mz_image_view* y, const mz_image_view* cb, const mz_image_view* cr,
+    int B, int H, int W, int matrix, int range, int siting, void* hip_stream);
+int mz_debug_yuv_coeffs(int matrix, int range, double out[9]);
 int mz_resize_workspace_bytes(int Hin, int Win, int Hout, int Wout, int filter, size_t* bytes);
 int mz_resize(const mz_image_view* x, const mz_image_view* out, int elem, int B, int Hin, int Win, int Hout, int Wout, int filter,
     int clamp, const int32_t window[4], void* workspace, size_t workspace_bytes, void* hip_stream);
@@ -371,6 +379,33 @@ def luma_coeffs(standard: int):
     """mz_debug_luma_coeffs (host only): [off, kr, kg, kb], the constants the kernels compile."""
     out = (c_double * 4)()
     _call("mz_debug_luma_coeffs", int(standard), out)
+    return [float(v) for v in out]
+
+
+def yuv_codes(matrix, range_, siting):
+    """The (matrix, range, siting) codes of the YCbCr entries, from their names."""
+    for what, value, table in (("matrix", matrix, MZ_YUV_MATRICES), ("range", range_, MZ_YUV_RANGES), ("siting", siting, MZ_YUV_SITINGS)):
+        if value not in tuple(table):
+            raise ValueError(f"{what} is {' or '.join(repr(k) for k in table)}, got {value!r}")
+    return MZ_YUV_MATRICES[matrix], MZ_YUV_RANGES[range_], MZ_YUV_SITINGS[siting]
+
+
+def yuv420_to_rgb(y, cb, cr, out, elem_out, B, H, W, matrix, range_, siting, clamp, stream) -> None:
+    """mz_yuv420_to_rgb: y, cb, cr and out are (address, strides) pairs of the uint8 planes [B,1,H,W], [B,1,Hc,Wc] twice and of the
+    [B,3,H,W] result of element type `elem_out`; no workspace."""
+    _call("mz_yuv420_to_rgb", view(*y), view(*cb), view(*cr), view(*out), int(elem_out), B, H, W, int(matrix), int(range_), int(siting),
+          bool(clamp), stream)
+
+
+def rgb_to_yuv420(x, elem, y, cb, cr, B, H, W, matrix, range_, siting, stream) -> None:
+    """mz_rgb_to_yuv420: x the (address, strides) pair of a [B,3,H,W] view of element type `elem`; y, cb, cr those of the planes written."""
+    _call("mz_rgb_to_yuv420", view(*x), int(elem), view(*y), view(*cb), view(*cr), B, H, W, int(matrix), int(range_), int(siting), stream)
+
+
+def yuv_coeffs(matrix: int, range_: int):
+    """mz_debug_yuv_coeffs (host only): [Yoff, 1/Sy, 1/Sc, a_r, a_b, g_r, g_b, Sy, Sc], the constants the kernels compile."""
+    out = (c_double * 9)()
+    _call("mz_debug_yuv_coeffs", int(matrix), int(range_), out)
     return [float(v) for v in out]
 
 

@@ -1,4 +1,4 @@
-// Stateless image entry points of libmewzoom_hip.so: image-quality metrics (RGB and luma), the luma plane, antialiased resizing, plain
+// Stateless image entry points of libmewzoom_hip.so: image-quality metrics (RGB and luma), the luma plane, 4:2:0 YCbCr frames, antialiased resizing, plain
 // interpolation, the degradation chain, the dihedral transforms with the self-ensemble accumulator, and the
 // host-only mz_debug_* views of what their kernels are handed.  Every check comes before anything touches the GPU.
 #include <cstring>
@@ -10,6 +10,7 @@
 #include "mz_interp.h"
 #include "mz_metrics.h"
 #include "mz_resize.h"
+#include "mz_yuv.h"
 
 using namespace mz;
 
@@ -153,6 +154,112 @@ extern "C" int mz_metrics_luma(const mz_image_view* pred, const mz_image_view* t
     a.out = out_dev;
     a.ws = (char*)workspace;
     return launched("luma metrics launch", [&] { return launch_metrics_luma(a, (hipStream_t)hip_stream); });
+}
+
+// ------------------------------------------------------------------------------------------------
+// 8-bit 4:2:0 YCbCr frames (mz_yuv.h): Y, Cb and Cr planes to an RGB view and back.  No reference counterpart.  Stateless like mz_luma,
+// no workspace.  Every check comes before anything touches the GPU.
+// ------------------------------------------------------------------------------------------------
+struct YuvPlanes { mz_image_view y, cb, cr; };  // the three views with a channel stride of 1: one channel, its stride names nothing
+
+// the three codes: the LAST check of both entries (a call that arrives here with a bad code has passed every check of its views --
+// how tests/test_yuv_cpu.py shows on a machine with a GPU that a layout is accepted, without a launch)
+static int check_yuv_codes(int matrix, int range, int siting) {
+    if (!yuv_code_valid(matrix)) return fail(MZ_ERR_INVALID_ARGUMENT, "matrix must be 0 (bt601) or 1 (bt709), got %d", matrix);
+    if (!yuv_code_valid(range)) return fail(MZ_ERR_INVALID_ARGUMENT, "range must be 0 (limited) or 1 (full), got %d", range);
+    if (!yuv_code_valid(siting)) return fail(MZ_ERR_INVALID_ARGUMENT, "siting must be 0 (left) or 1 (center), got %d", siting);
+    return MZ_OK;
+}
+
+// the views and shapes of both entries; `planes_written`: the planes are the outputs (no stride of 0), else the RGB view is
+static int check_yuv_call(const mz_image_view* y, const mz_image_view* cb, const mz_image_view* cr, const mz_image_view* rgb, int elem, int B, int H,
+                          int W, int matrix, int range, int siting, bool planes_written, YuvPlanes* p, YuvArgs* a) {
+    static const ViewRules written = {3, MZ_ELEM_NAMES_0_3, /*second_is_output*/ true, /*batch_bound*/ true, /*side_bound*/ true};
+    static const ViewRules read = {3, MZ_ELEM_NAMES_0_3, /*second_is_output*/ false, /*batch_bound*/ true, /*side_bound*/ true};
+    if (!y || !cb || !cr || !rgb) return fail(MZ_ERR_INVALID_ARGUMENT, "null image view");
+    p->y = *y; p->cb = *cb; p->cr = *cr;
+    p->y.stride[1] = p->cb.stride[1] = p->cr.stride[1] = 1;
+    StridedView unused;
+    if (const Refusal r = check_views(planes_written ? rgb : &p->y, planes_written ? &p->y : rgb, written, elem, B, H, W,
+                                      planes_written ? &a->rgb : &a->y, planes_written ? &a->y : &a->rgb)) return fail(r);
+    const ViewRules& chroma = planes_written ? written : read;
+    if (const Refusal r = check_views(&p->cb, &p->cb, chroma, elem, B, H, W, &unused, &a->cb)) return fail(r);
+    if (const Refusal r = check_views(&p->cr, &p->cr, chroma, elem, B, H, W, &unused, &a->cr)) return fail(r);
+    // the RGB view against each plane: inputs and outputs lie apart
+    const int Hc = (H + 1) / 2, Wc = (W + 1) / 2;
+    const mz_image_view* plane[3] = {&p->y, &p->cb, &p->cr};
+    for (int i = 0; i < 3; ++i) {
+        long long rl, rh, pl, ph;
+        if (!view_extent(rgb, elem, B, H, W, &rl, &rh) || !view_extent(plane[i], EL_U8, B, i ? Hc : H, i ? Wc : W, &pl, &ph, 1))
+            return fail(MZ_ERR_INVALID_ARGUMENT, "a view's byte range does not fit in 63 bits");
+        if (rl < ph && pl < rh) return fail(MZ_ERR_INVALID_ARGUMENT, "the RGB view and the %s plane overlap: this entry does not work in place", i == 0 ? "Y" : i == 1 ? "Cb" : "Cr");
+    }
+    a->elem = elem; a->B = B; a->H = H; a->W = W;
+    a->matrix = matrix; a->range = range; a->siting = siting;
+    return MZ_OK;
+}
+
+// Two planes that are WRITTEN share no byte: the byte range of every image of one against every image of the other.  (The ranges of whole
+// batches would not do: the planes of an NV12 or I420 batch alternate in memory.)  With equal image strides image b of one meets image
+// b' of the other exactly when the ranges of their images 0, (b - b') image strides apart, do; with different ones the batches' ranges decide.
+static bool planes_apart(const mz_image_view* p, int Hp, int Wp, const mz_image_view* q, int Hq, int Wq, int B, bool* fits) {
+    long long pl, ph, ql, qh;
+    *fits = true;
+    if (B > 1 && p->stride[0] != q->stride[0]) {
+        *fits = view_extent(p, EL_U8, B, Hp, Wp, &pl, &ph, 1) && view_extent(q, EL_U8, B, Hq, Wq, &ql, &qh, 1);
+        return *fits && !(pl < qh && ql < ph);
+    }
+    *fits = view_extent(p, EL_U8, 1, Hp, Wp, &pl, &ph, 1) && view_extent(q, EL_U8, 1, Hq, Wq, &ql, &qh, 1);
+    if (!*fits) return false;
+    for (long long d = -(long long)(B - 1); d <= B - 1; ++d) {  // (B <= 65535)
+        const __int128 shift = (__int128)d * p->stride[0];
+        if (pl + shift < qh && ql < ph + shift) return false;
+    }
+    return true;
+}
+
+// Cb and Cr interleave, as in NV12: identical strides, a column stride of at least 2, bases 1 .. column stride - 1 bytes apart
+static bool chroma_interleaved(const mz_image_view* cb, const mz_image_view* cr) {
+    for (int i = 0; i < 4; ++i)
+        if (cb->stride[i] != cr->stride[i]) return false;
+    const long long s = cb->stride[3], d = (long long)((intptr_t)cr->data - (intptr_t)cb->data);
+    return s >= 2 && d != 0 && d > -s && d < s;
+}
+
+extern "C" int mz_yuv420_to_rgb(const mz_image_view* y, const mz_image_view* cb, const mz_image_view* cr, const mz_image_view* out, int elem_out,
+                                int B, int H, int W, int matrix, int range, int siting, int clamp, void* hip_stream) {
+    YuvPlanes p;
+    YuvArgs a = {};
+    if (int rc = check_yuv_call(y, cb, cr, out, elem_out, B, H, W, matrix, range, siting, false, &p, &a)) return rc;
+    if (int rc = check_yuv_codes(matrix, range, siting)) return rc;
+    a.clamp = clamp != 0;
+    return launched("yuv420_to_rgb launch", [&] { return (hipError_t)launch_yuv420_to_rgb(a, hip_stream); });
+}
+
+extern "C" int mz_rgb_to_yuv420(const mz_image_view* x, int elem, const mz_image_view* y, const mz_image_view* cb, const mz_image_view* cr,
+                                int B, int H, int W, int matrix, int range, int siting, void* hip_stream) {
+    YuvPlanes p;
+    YuvArgs a = {};
+    if (int rc = check_yuv_call(y, cb, cr, x, elem, B, H, W, matrix, range, siting, true, &p, &a)) return rc;
+    const int Hc = (H + 1) / 2, Wc = (W + 1) / 2;
+    bool fits;
+    if (!planes_apart(&p.y, H, W, &p.cb, Hc, Wc, B, &fits) || !planes_apart(&p.y, H, W, &p.cr, Hc, Wc, B, &fits))
+        return fits ? fail(MZ_ERR_INVALID_ARGUMENT, "the Y plane and a chroma plane overlap") : fail(MZ_ERR_INVALID_ARGUMENT, "a view's byte range does not fit in 63 bits");
+    if (!chroma_interleaved(&p.cb, &p.cr) && !planes_apart(&p.cb, Hc, Wc, &p.cr, Hc, Wc, B, &fits))
+        return fits ? fail(MZ_ERR_INVALID_ARGUMENT, "the Cb and Cr planes overlap without interleaving (identical strides, a column stride of "
+                                                     "at least 2, bases less than that apart)")
+                    : fail(MZ_ERR_INVALID_ARGUMENT, "a view's byte range does not fit in 63 bits");
+    if (int rc = check_yuv_codes(matrix, range, siting)) return rc;
+    return launched("rgb_to_yuv420 launch", [&] { return (hipError_t)launch_rgb_to_yuv420(a, hip_stream); });
+}
+
+// Host only: {Yoff, 1/Sy, 1/Sc, a_r, a_b, g_r, g_b, Sy, Sc} of a matrix and a range, the constants the kernels compile
+extern "C" int mz_debug_yuv_coeffs(int matrix, int range, double out[9]) {
+    if (!out) return fail(MZ_ERR_INVALID_ARGUMENT, "null argument");
+    if (!yuv_code_valid(matrix) || !yuv_code_valid(range)) return fail(MZ_ERR_INVALID_ARGUMENT, "matrix and range must be 0 or 1, got %d and %d", matrix, range);
+    const YuvCoeffs k = yuv_coeffs(matrix, range);
+    out[0] = k.yoff; out[1] = k.inv_sy; out[2] = k.inv_sc; out[3] = k.a_r; out[4] = k.a_b; out[5] = k.g_r; out[6] = k.g_b; out[7] = k.sy; out[8] = k.sc;
+    return MZ_OK;
 }
 
 // ------------------------------------------------------------------------------------------------

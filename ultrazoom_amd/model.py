@@ -424,6 +424,18 @@ class MewZoom(nn.Module, PyTorchModelHubMixin):
         sr = self.upscale_uint8(x) if x.dtype == torch.uint8 else self.upscale(x)
         return sr, interpolate(x, scale_factor=self.upscale_ratio, mode="bicubic", clamp=True)
 
+    @torch.inference_mode()
+    def upscale_yuv420(self, y: Tensor, cb: Tensor, cr: Tensor, *, matrix: str = "bt709", range: str = "limited", siting: str = "left",
+                       out: Optional[Tuple[Tensor, Tensor, Tensor]] = None) -> Tuple[Tensor, Tensor, Tensor]:
+        """``upscale`` on 8-bit 4:2:0 YCbCr frames: the uint8 planes ``(Y, Cb, Cr)`` of the upscaled frames, r times the size, from the
+        planes y [B, 1, H, W], cb and cr [B, 1, ceil(H / 2), ceil(W / 2)] (any strides: ``ultrazoom_amd.nv12_planes`` /
+        ``i420_planes`` cut them out of a frame buffer) -- ``ultrazoom_amd.video.upscale_yuv420(self, ...)``: ``yuv420_to_rgb`` into the
+        dtype of the model's parameters, clamped, then ``upscale``, then ``rgb_to_yuv420`` into ``out`` (a triple of uint8 tensors or
+        views).  No host synchronisation beyond ``upscale``'s.  No reference counterpart."""
+        from .video import upscale_yuv420
+
+        return upscale_yuv420(self, y, cb, cr, matrix=matrix, range=range, siting=siting, out=out)
+
     # ---- checkpoint ingestion (test_compare.py:32-45 of the reference) -------------------------
     def load_training_checkpoint(self, state_dict: Dict[str, Tensor], lora_alpha: Optional[float] = None) -> None:
         """Loads a raw training checkpoint: strips ``_orig_mod.`` prefixes left by torch.compile, bakes weight-norm
