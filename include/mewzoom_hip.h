@@ -95,14 +95,14 @@ int mz_weights_complete(const mz_handle* h);
  * not grow beyond that.
  *
  * What a call touches (mz_forward, mz_forward_u8, mz_forward_view, mz_metrics, mz_metrics_luma, mz_luma, mz_yuv420_to_rgb, mz_rgb_to_yuv420,
- * mz_resize, mz_interpolate, mz_blur, mz_noise,
+ * mz_ycbcr_to_rgb, mz_rgb_to_ycbcr, mz_resize, mz_interpolate, mz_blur, mz_noise,
  * mz_jpeg and the mz_op_* entries alike): it READS only its
  * input tensors -- the elements its shape and strides name, never a byte next to them -- and the workspace bytes it has itself
  * written during that call; it WRITES only its outputs (of a view: the elements of the window) and its workspace, never an input.
  * The workspace needs no initialisation and carries nothing from one call to the next: whatever it holds, NaN patterns included,
  * the results have the same bits.  mz_metrics and mz_metrics_luma write the `out` slots of the metrics `which` selects and leave the
  * others alone.  tests/test_poison_ops_gpu.py, tests/test_poison_forward_gpu.py, tests/test_metrics_gpu.py and
- * tests/test_poison_color_gpu.py, tests/test_poison_yuv_gpu.py hold every entry to this.
+ * tests/test_poison_color_gpu.py, tests/test_poison_yuv_gpu.py, tests/test_poison_ycbcr_gpu.py hold every entry to this.
  *
  * Number range (the convolution, mix, stem and head kernels, in every storage type): subnormals of the storage type are operands and
  * results like any other value -- nothing is flushed on the way in, in the matrix unit's operands, or at the store.  Accumulation is
@@ -141,7 +141,7 @@ int mz_forward_u8(mz_handle* h, const uint8_t* x, uint8_t* out_sr, float* out_qa
  * mz_blur, mz_noise and mz_jpeg also compare the two byte ranges).
  *
  * THE VIEW REFUSALS.  Every entry that takes views (mz_forward_view, mz_metrics, mz_metrics_luma, mz_luma, mz_yuv420_to_rgb, mz_rgb_to_yuv420,
- * mz_resize, mz_interpolate, mz_blur,
+ * mz_ycbcr_to_rgb, mz_rgb_to_ycbcr, mz_resize, mz_interpolate, mz_blur,
  * mz_noise, mz_jpeg, mz_dihedral, mz_ensemble_add, mz_ensemble_finish) returns
  * MZ_ERR_INVALID_ARGUMENT, before anything touches the GPU, for: a null view or null data; an `elem` outside the entry's codes; a view
  * that is WRITTEN whose channel, row or column stride is 0, or whose image stride is 0 when B > 1 (mz_luma's one-channel output: its
@@ -296,6 +296,29 @@ int mz_rgb_to_yuv420(const mz_image_view* x, int elem, const mz_image_view* y, c
                      int B, int H, int W, int matrix, int range, int siting, void* hip_stream);
 /* Host only: {Yoff, 1/Sy, 1/Sc, a_r, a_b, g_r, g_b, Sy, Sc} of a matrix and a range, the constants the kernels compile. */
 int mz_debug_yuv_coeffs(int matrix, int range, double out[9]);
+
+/* ---- YCbCr frames of 8, 10, 12 or 16 bits in 4:2:0, 4:2:2 or 4:4:4: the two entries above generalised (P010 / P012 / P016, yuv420p10le
+ *      and its kin, NV16 / NV24, I422 / I444, BT.2020).  ultrazoom_amd/csrc/mz_ycbcr.h is the one statement of the arithmetic ------------
+ * Where a parameter takes the value of the 4:2:0 entries, every operation and its order are theirs: depth 8, subsampling 0 and matrix 0
+ * or 1 give the bits of mz_yuv420_to_rgb / mz_rgb_to_yuv420.
+ * depth        8: planes of uint8; 10, 12, 16: planes of host-endian uint16 (strides count ELEMENTS; data aligned to 2 bytes).  With
+ *              s = 2^(depth - 8): "limited" Yoff = 16 s, Sy = 219 s, Sc = 224 s; "full" Yoff = 0, Sy = Sc = 2^depth - 1; the chroma
+ *              midpoint is 2^(depth - 1); codes clamp to [0, 2^depth - 1]
+ * align        of a 16-bit container: 0 "low" -- a code is word & (2^depth - 1), written as it is (yuv420p10le, ..); 1 "high" -- a code
+ *              is word >> (16 - depth), written as code << (16 - depth), the low bits zero (P010, P012, P016).  Depth 8 and 16: no difference
+ * subsampling  cb and cr are views of [B,1,Hc,Wc]: 0 "420" Hc = ceil(H/2), Wc = ceil(W/2); 1 "422" Hc = H, Wc = ceil(W/2), no vertical
+ *              filter; 2 "444" Hc = H, Wc = W, no filter (the siting must still be a valid code)
+ * matrix       0, 1 as above; 2 "bt2020" (Kr = 0.2627, Kb = 0.0593, non-constant luminance)
+ * Refuse what mz_yuv420_to_rgb and mz_rgb_to_yuv420 refuse (a matrix outside 0..2), and: a depth outside {8, 10, 12, 16}; an align
+ * outside 0..1; a subsampling outside 0..2; plane data not aligned to 2 bytes when depth > 8.  Byte ranges are those of the planes'
+ * element size, and the interleaving exception counts ELEMENTS: identical strides, a column stride of at least 2, bases a whole number
+ * of elements -- at least one, fewer than the column stride -- apart.  Matrix, range and siting are checked last. */
+int mz_ycbcr_to_rgb(const mz_image_view* y, const mz_image_view* cb, const mz_image_view* cr, int depth, int align, int subsampling,
+                    const mz_image_view* out, int elem_out, int B, int H, int W, int matrix, int range, int siting, int clamp, void* hip_stream);
+int mz_rgb_to_ycbcr(const mz_image_view* x, int elem, const mz_image_view* y, const mz_image_view* cb, const mz_image_view* cr,
+                    int depth, int align, int subsampling, int B, int H, int W, int matrix, int range, int siting, void* hip_stream);
+/* Host only: the nine values of mz_debug_yuv_coeffs at a depth, then the chroma midpoint and the largest code. */
+int mz_debug_ycbcr_coeffs(int matrix, int range, int depth, double out[11]);
 
 /* ---- antialiased resampling to any size: no reference counterpart in `model.py`; stands in for torchvision's antialiased `Resize`
  *      as the reference's `data.py:91-108` uses it (HR -> LR for validation), and serves "a 3X or a true-4K result from a 4X model"

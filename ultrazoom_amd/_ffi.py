@@ -34,6 +34,10 @@ MZ_LUMA_STANDARDS = {"bt601": 0, "full": 1}  # studio range (MATLAB rgb2ycbcr, b
 MZ_YUV_MATRICES = {"bt601": 0, "bt709": 1}
 MZ_YUV_RANGES = {"limited": 0, "full": 1}
 MZ_YUV_SITINGS = {"left": 0, "center": 1}  # MPEG-2 / H.264 / HEVC; JPEG / MPEG-1
+MZ_YCBCR_MATRICES = {"bt601": 0, "bt709": 1, "bt2020": 2}  # the matrices of mz_ycbcr_to_rgb / mz_rgb_to_ycbcr
+MZ_YCBCR_DEPTHS = (8, 10, 12, 16)
+MZ_YCBCR_ALIGNS = {"low": 0, "high": 1}  # yuv420p10le and its kin; P010 / P012 / P016
+MZ_YCBCR_SUBSAMPLINGS = {"420": 0, "422": 1, "444": 2}
 
 
 class MzConfig(Structure):
@@ -110,6 +114,11 @@ int mz_yuv420_to_rgb(const mz_image_view* y, const mz_image_view* cb, const mz_i
 int mz_rgb_to_yuv420(const mz_image_view* x, int elem, const mz_image_view* y, const mz_image_view* cb, const mz_image_view* cr,
     int B, int H, int W, int matrix, int range, int siting, void* hip_stream);
 int mz_debug_yuv_coeffs(int matrix, int range, double out[9]);
+int mz_ycbcr_to_rgb(const mz_image_view* y, const mz_image_view* cb, const mz_image_view* cr, int depth, int align, int subsampling,
+    const mz_image_view* out, int elem_out, int B, int H, int W, int matrix, int range, int siting, int clamp, void* hip_stream);
+int mz_rgb_to_ycbcr(const mz_image_view* x, int elem, const mz_image_view* y, const mz_image_view* cb, const mz_image_view* cr,
+    int depth, int align, int subsampling, int B, int H, int W, int matrix, int range, int siting, void* hip_stream);
+int mz_debug_ycbcr_coeffs(int matrix, int range, int depth, double out[11]);
 int mz_resize_workspace_bytes(int Hin, int Win, int Hout, int Wout, int filter, size_t* bytes);
 int mz_resize(const mz_image_view* x, const mz_image_view* out, int elem, int B, int Hin, int Win, int Hout, int Wout, int filter,
     int clamp, const int32_t window[4], void* workspace, size_t workspace_bytes, void* hip_stream);
@@ -406,6 +415,38 @@ def yuv_coeffs(matrix: int, range_: int):
     """mz_debug_yuv_coeffs (host only): [Yoff, 1/Sy, 1/Sc, a_r, a_b, g_r, g_b, Sy, Sc], the constants the kernels compile."""
     out = (c_double * 9)()
     _call("mz_debug_yuv_coeffs", int(matrix), int(range_), out)
+    return [float(v) for v in out]
+
+
+def ycbcr_codes(depth, align, subsampling, matrix, range_, siting):
+    """((depth, align, subsampling), (matrix, range, siting)) codes of the mz_ycbcr entries, from their names."""
+    if depth not in MZ_YCBCR_DEPTHS:
+        raise ValueError(f"depth is 8, 10, 12 or 16, got {depth!r}")
+    for what, value, table in (("align", align, MZ_YCBCR_ALIGNS), ("subsampling", subsampling, MZ_YCBCR_SUBSAMPLINGS),
+                               ("matrix", matrix, MZ_YCBCR_MATRICES), ("range", range_, MZ_YUV_RANGES), ("siting", siting, MZ_YUV_SITINGS)):
+        if value not in tuple(table):
+            raise ValueError(f"{what} is {' or '.join(repr(k) for k in table)}, got {value!r}")
+    return ((int(depth), MZ_YCBCR_ALIGNS[align], MZ_YCBCR_SUBSAMPLINGS[subsampling]),
+            (MZ_YCBCR_MATRICES[matrix], MZ_YUV_RANGES[range_], MZ_YUV_SITINGS[siting]))
+
+
+def ycbcr_to_rgb(y, cb, cr, depth, align, subsampling, out, elem_out, B, H, W, matrix, range_, siting, clamp, stream) -> None:
+    """mz_ycbcr_to_rgb: y, cb, cr and out are (address, strides) pairs of the uint8 (depth 8) or uint16 planes and of the [B,3,H,W] result of
+    element type `elem_out`; no workspace."""
+    _call("mz_ycbcr_to_rgb", view(*y), view(*cb), view(*cr), int(depth), int(align), int(subsampling), view(*out), int(elem_out), B, H, W,
+          int(matrix), int(range_), int(siting), bool(clamp), stream)
+
+
+def rgb_to_ycbcr(x, elem, y, cb, cr, depth, align, subsampling, B, H, W, matrix, range_, siting, stream) -> None:
+    """mz_rgb_to_ycbcr: x the (address, strides) pair of a [B,3,H,W] view of element type `elem`; y, cb, cr those of the planes written."""
+    _call("mz_rgb_to_ycbcr", view(*x), int(elem), view(*y), view(*cb), view(*cr), int(depth), int(align), int(subsampling), B, H, W,
+          int(matrix), int(range_), int(siting), stream)
+
+
+def ycbcr_coeffs(matrix: int, range_: int, depth: int):
+    """mz_debug_ycbcr_coeffs (host only): the nine values of yuv_coeffs at `depth`, then the chroma midpoint and the largest code."""
+    out = (c_double * 11)()
+    _call("mz_debug_ycbcr_coeffs", int(matrix), int(range_), int(depth), out)
     return [float(v) for v in out]
 
 

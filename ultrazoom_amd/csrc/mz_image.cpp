@@ -1,4 +1,4 @@
-// Stateless image entry points of libmewzoom_hip.so: image-quality metrics (RGB and luma), the luma plane, 4:2:0 YCbCr frames, antialiased resizing, plain
+// Stateless image entry points of libmewzoom_hip.so: image-quality metrics (RGB and luma), the luma plane, YCbCr frames (8-bit 4:2:0; any depth and subsampling), antialiased resizing, plain
 // interpolation, the degradation chain, the dihedral transforms with the self-ensemble accumulator, and the
 // host-only mz_debug_* views of what their kernels are handed.  Every check comes before anything touches the GPU.
 #include <cstring>
@@ -10,6 +10,7 @@
 #include "mz_interp.h"
 #include "mz_metrics.h"
 #include "mz_resize.h"
+#include "mz_ycbcr.h"
 #include "mz_yuv.h"
 
 using namespace mz;
@@ -202,28 +203,30 @@ static int check_yuv_call(const mz_image_view* y, const mz_image_view* cb, const
 // Two planes that are WRITTEN share no byte: the byte range of every image of one against every image of the other.  (The ranges of whole
 // batches would not do: the planes of an NV12 or I420 batch alternate in memory.)  With equal image strides image b of one meets image
 // b' of the other exactly when the ranges of their images 0, (b - b') image strides apart, do; with different ones the batches' ranges decide.
-static bool planes_apart(const mz_image_view* p, int Hp, int Wp, const mz_image_view* q, int Hq, int Wq, int B, bool* fits) {
+// (`elem`: a code whose element has the planes' size -- EL_U8, or EL_F16 for 16-bit samples)
+static bool planes_apart(const mz_image_view* p, int Hp, int Wp, const mz_image_view* q, int Hq, int Wq, int B, bool* fits, int elem = EL_U8) {
     long long pl, ph, ql, qh;
     *fits = true;
     if (B > 1 && p->stride[0] != q->stride[0]) {
-        *fits = view_extent(p, EL_U8, B, Hp, Wp, &pl, &ph, 1) && view_extent(q, EL_U8, B, Hq, Wq, &ql, &qh, 1);
+        *fits = view_extent(p, elem, B, Hp, Wp, &pl, &ph, 1) && view_extent(q, elem, B, Hq, Wq, &ql, &qh, 1);
         return *fits && !(pl < qh && ql < ph);
     }
-    *fits = view_extent(p, EL_U8, 1, Hp, Wp, &pl, &ph, 1) && view_extent(q, EL_U8, 1, Hq, Wq, &ql, &qh, 1);
+    *fits = view_extent(p, elem, 1, Hp, Wp, &pl, &ph, 1) && view_extent(q, elem, 1, Hq, Wq, &ql, &qh, 1);
     if (!*fits) return false;
     for (long long d = -(long long)(B - 1); d <= B - 1; ++d) {  // (B <= 65535)
-        const __int128 shift = (__int128)d * p->stride[0];
+        const __int128 shift = (__int128)d * p->stride[0] * (elem == EL_U8 ? 1 : 2);
         if (pl + shift < qh && ql < ph + shift) return false;
     }
     return true;
 }
 
-// Cb and Cr interleave, as in NV12: identical strides, a column stride of at least 2, bases 1 .. column stride - 1 bytes apart
-static bool chroma_interleaved(const mz_image_view* cb, const mz_image_view* cr) {
+// Cb and Cr interleave, as in NV12: identical strides, a column stride of at least 2, bases a whole number of elements (of `bytes`
+// bytes), 1 .. column stride - 1, apart
+static bool chroma_interleaved(const mz_image_view* cb, const mz_image_view* cr, int bytes = 1) {
     for (int i = 0; i < 4; ++i)
         if (cb->stride[i] != cr->stride[i]) return false;
-    const long long s = cb->stride[3], d = (long long)((intptr_t)cr->data - (intptr_t)cb->data);
-    return s >= 2 && d != 0 && d > -s && d < s;
+    const long long s = cb->stride[3], db = (long long)((intptr_t)cr->data - (intptr_t)cb->data), d = db / bytes;
+    return s >= 2 && db % bytes == 0 && d != 0 && d > -s && d < s;
 }
 
 extern "C" int mz_yuv420_to_rgb(const mz_image_view* y, const mz_image_view* cb, const mz_image_view* cr, const mz_image_view* out, int elem_out,
@@ -259,6 +262,102 @@ extern "C" int mz_debug_yuv_coeffs(int matrix, int range, double out[9]) {
     if (!yuv_code_valid(matrix) || !yuv_code_valid(range)) return fail(MZ_ERR_INVALID_ARGUMENT, "matrix and range must be 0 or 1, got %d and %d", matrix, range);
     const YuvCoeffs k = yuv_coeffs(matrix, range);
     out[0] = k.yoff; out[1] = k.inv_sy; out[2] = k.inv_sc; out[3] = k.a_r; out[4] = k.a_b; out[5] = k.g_r; out[6] = k.g_b; out[7] = k.sy; out[8] = k.sc;
+    return MZ_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// YCbCr frames of 8, 10, 12 or 16 bits in 4:2:0, 4:2:2 or 4:4:4 (mz_ycbcr.h): the entries above generalised over depth, alignment,
+// subsampling and a third matrix.  The same checks in the same order, byte ranges with the planes' element size.
+// ------------------------------------------------------------------------------------------------
+// what decides the planes' shapes and element size: checked once the views are known not to be null, before their ranges are formed
+static int check_ycbcr_format(int depth, int align, int subsampling) {
+    if (!ycbcr_depth_valid(depth)) return fail(MZ_ERR_INVALID_ARGUMENT, "depth must be 8, 10, 12 or 16, got %d", depth);
+    if (align != YCBCR_LOW && align != YCBCR_HIGH) return fail(MZ_ERR_INVALID_ARGUMENT, "align must be 0 (low) or 1 (high), got %d", align);
+    if (!ycbcr_code3_valid(subsampling)) return fail(MZ_ERR_INVALID_ARGUMENT, "subsampling must be 0 (420), 1 (422) or 2 (444), got %d", subsampling);
+    return MZ_OK;
+}
+// the LAST check of both entries, as check_yuv_codes
+static int check_ycbcr_codes(int matrix, int range, int siting) {
+    if (!ycbcr_code3_valid(matrix)) return fail(MZ_ERR_INVALID_ARGUMENT, "matrix must be 0 (bt601), 1 (bt709) or 2 (bt2020), got %d", matrix);
+    if (!yuv_code_valid(range)) return fail(MZ_ERR_INVALID_ARGUMENT, "range must be 0 (limited) or 1 (full), got %d", range);
+    if (!yuv_code_valid(siting)) return fail(MZ_ERR_INVALID_ARGUMENT, "siting must be 0 (left) or 1 (center), got %d", siting);
+    return MZ_OK;
+}
+
+// check_yuv_call with the format: `plane_elem` is a code whose element has the planes' size
+static int check_ycbcr_call(const mz_image_view* y, const mz_image_view* cb, const mz_image_view* cr, const mz_image_view* rgb, int elem, int B, int H,
+                            int W, int depth, int align, int subsampling, bool planes_written, YuvPlanes* p, YcbcrArgs* a, int* plane_elem) {
+    static const ViewRules written = {3, MZ_ELEM_NAMES_0_3, /*second_is_output*/ true, /*batch_bound*/ true, /*side_bound*/ true};
+    static const ViewRules read = {3, MZ_ELEM_NAMES_0_3, /*second_is_output*/ false, /*batch_bound*/ true, /*side_bound*/ true};
+    if (!y || !cb || !cr || !rgb) return fail(MZ_ERR_INVALID_ARGUMENT, "null image view");
+    if (int rc = check_ycbcr_format(depth, align, subsampling)) return rc;
+    *plane_elem = depth > 8 ? EL_F16 : EL_U8;  // (view_extent takes an element code: a 16-bit sample has the size of a 16-bit element)
+    p->y = *y; p->cb = *cb; p->cr = *cr;
+    p->y.stride[1] = p->cb.stride[1] = p->cr.stride[1] = 1;
+    StridedView unused;
+    if (const Refusal r = check_views(planes_written ? rgb : &p->y, planes_written ? &p->y : rgb, written, elem, B, H, W,
+                                      planes_written ? &a->rgb : &a->y, planes_written ? &a->y : &a->rgb)) return fail(r);
+    const ViewRules& chroma = planes_written ? written : read;
+    if (const Refusal r = check_views(&p->cb, &p->cb, chroma, elem, B, H, W, &unused, &a->cb)) return fail(r);
+    if (const Refusal r = check_views(&p->cr, &p->cr, chroma, elem, B, H, W, &unused, &a->cr)) return fail(r);
+    const int Hc = ycbcr_hc(H, subsampling), Wc = ycbcr_wc(W, subsampling);
+    const mz_image_view* plane[3] = {&p->y, &p->cb, &p->cr};
+    static const char* const names[3] = {"Y", "Cb", "Cr"};
+    if (depth > 8)
+        for (int i = 0; i < 3; ++i)
+            if ((uintptr_t)plane[i]->data % 2) return fail(MZ_ERR_INVALID_ARGUMENT, "the %s plane's data is not aligned to 2 bytes (depth %d: uint16 samples)", names[i], depth);
+    for (int i = 0; i < 3; ++i) {  // the RGB view against each plane: inputs and outputs lie apart
+        long long rl, rh, pl, ph;
+        if (!view_extent(rgb, elem, B, H, W, &rl, &rh) || !view_extent(plane[i], *plane_elem, B, i ? Hc : H, i ? Wc : W, &pl, &ph, 1))
+            return fail(MZ_ERR_INVALID_ARGUMENT, "a view's byte range does not fit in 63 bits");
+        if (rl < ph && pl < rh) return fail(MZ_ERR_INVALID_ARGUMENT, "the RGB view and the %s plane overlap: this entry does not work in place", names[i]);
+    }
+    a->elem = elem; a->B = B; a->H = H; a->W = W;
+    a->depth = depth; a->align = align; a->subsampling = subsampling;
+    return MZ_OK;
+}
+
+extern "C" int mz_ycbcr_to_rgb(const mz_image_view* y, const mz_image_view* cb, const mz_image_view* cr, int depth, int align, int subsampling,
+                               const mz_image_view* out, int elem_out, int B, int H, int W, int matrix, int range, int siting, int clamp,
+                               void* hip_stream) {
+    YuvPlanes p;
+    YcbcrArgs a = {};
+    int plane_elem;
+    if (int rc = check_ycbcr_call(y, cb, cr, out, elem_out, B, H, W, depth, align, subsampling, false, &p, &a, &plane_elem)) return rc;
+    if (int rc = check_ycbcr_codes(matrix, range, siting)) return rc;
+    a.matrix = matrix; a.range = range; a.siting = siting;
+    a.clamp = clamp != 0;
+    return launched("ycbcr_to_rgb launch", [&] { return (hipError_t)launch_ycbcr_to_rgb(a, hip_stream); });
+}
+
+extern "C" int mz_rgb_to_ycbcr(const mz_image_view* x, int elem, const mz_image_view* y, const mz_image_view* cb, const mz_image_view* cr,
+                               int depth, int align, int subsampling, int B, int H, int W, int matrix, int range, int siting, void* hip_stream) {
+    YuvPlanes p;
+    YcbcrArgs a = {};
+    int pe;
+    if (int rc = check_ycbcr_call(y, cb, cr, x, elem, B, H, W, depth, align, subsampling, true, &p, &a, &pe)) return rc;
+    const int Hc = ycbcr_hc(H, subsampling), Wc = ycbcr_wc(W, subsampling);
+    bool fits;
+    if (!planes_apart(&p.y, H, W, &p.cb, Hc, Wc, B, &fits, pe) || !planes_apart(&p.y, H, W, &p.cr, Hc, Wc, B, &fits, pe))
+        return fits ? fail(MZ_ERR_INVALID_ARGUMENT, "the Y plane and a chroma plane overlap") : fail(MZ_ERR_INVALID_ARGUMENT, "a view's byte range does not fit in 63 bits");
+    if (!chroma_interleaved(&p.cb, &p.cr, depth > 8 ? 2 : 1) && !planes_apart(&p.cb, Hc, Wc, &p.cr, Hc, Wc, B, &fits, pe))
+        return fits ? fail(MZ_ERR_INVALID_ARGUMENT, "the Cb and Cr planes overlap without interleaving (identical strides, a column stride of "
+                                                     "at least 2 elements, bases at least one element and less than that apart)")
+                    : fail(MZ_ERR_INVALID_ARGUMENT, "a view's byte range does not fit in 63 bits");
+    if (int rc = check_ycbcr_codes(matrix, range, siting)) return rc;
+    a.matrix = matrix; a.range = range; a.siting = siting;
+    return launched("rgb_to_ycbcr launch", [&] { return (hipError_t)launch_rgb_to_ycbcr(a, hip_stream); });
+}
+
+// Host only: the nine values of mz_debug_yuv_coeffs at a depth, then the chroma midpoint and the largest code
+extern "C" int mz_debug_ycbcr_coeffs(int matrix, int range, int depth, double out[11]) {
+    if (!out) return fail(MZ_ERR_INVALID_ARGUMENT, "null argument");
+    if (!ycbcr_code3_valid(matrix) || !yuv_code_valid(range) || !ycbcr_depth_valid(depth))
+        return fail(MZ_ERR_INVALID_ARGUMENT, "matrix must be 0..2, range 0 or 1, depth 8, 10, 12 or 16, got %d, %d and %d", matrix, range, depth);
+    const YcbcrCoeffs c = ycbcr_coeffs(matrix, range, depth);
+    const YuvCoeffs& k = c.k;
+    out[0] = k.yoff; out[1] = k.inv_sy; out[2] = k.inv_sc; out[3] = k.a_r; out[4] = k.a_b; out[5] = k.g_r; out[6] = k.g_b; out[7] = k.sy; out[8] = k.sc;
+    out[9] = c.mid; out[10] = c.maxc;
     return MZ_OK;
 }
 

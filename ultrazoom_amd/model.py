@@ -436,6 +436,22 @@ class MewZoom(nn.Module, PyTorchModelHubMixin):
 
         return upscale_yuv420(self, y, cb, cr, matrix=matrix, range=range, siting=siting, out=out)
 
+    @torch.inference_mode()
+    def upscale_ycbcr(self, y: Tensor, cb: Tensor, cr: Tensor, *, depth: Optional[int] = None, align: str = "low", subsampling: str = "420",
+                      matrix: str = "bt709", range: str = "limited", siting: str = "left",
+                      out: Optional[Tuple[Tensor, Tensor, Tensor]] = None) -> Tuple[Tensor, Tensor, Tensor]:
+        """``upscale`` on YCbCr frames of 8, 10, 12 or 16 bits in 4:2:0, 4:2:2 or 4:4:4 (P010, yuv420p10le, NV16, I444, ..; matrix
+        "bt601", "bt709" or "bt2020"): the planes of the upscaled frames, r times the size, in the depth, alignment and subsampling of
+        those that went in (``ultrazoom_amd.frame_planes`` cuts them out of a frame buffer) --
+        ``ultrazoom_amd.video.upscale_ycbcr(self, ...)``: ``ycbcr_to_rgb`` into the dtype of the model's parameters, clamped, then
+        ``upscale``, then ``rgb_to_ycbcr`` into ``out``.  The intermediate RGB has the MODEL's dtype: a bfloat16 model carries about 8
+        significant bits through; a 10-bit result needs a float16 or float32 model for its low bits to mean anything.  No reference
+        counterpart."""
+        from .video import upscale_ycbcr
+
+        return upscale_ycbcr(self, y, cb, cr, depth=depth, align=align, subsampling=subsampling, matrix=matrix, range=range, siting=siting,
+                             out=out)
+
     # ---- checkpoint ingestion (test_compare.py:32-45 of the reference) -------------------------
     def load_training_checkpoint(self, state_dict: Dict[str, Tensor], lora_alpha: Optional[float] = None) -> None:
         """Loads a raw training checkpoint: strips ``_orig_mod.`` prefixes left by torch.compile, bakes weight-norm
