@@ -148,7 +148,13 @@ int mz_forward_u8(mz_handle* h, const uint8_t* x, uint8_t* out_sr, float* out_qa
  * channel stride is never used and may be anything; strides of a view that is only read
  * may be 0, and any stride may be negative); where the entry takes a window: one that is empty or not inside the result.  Each entry
  * below lists only what it refuses beyond these.  A workspace that is null or smaller than the entry's *_workspace_bytes is
- * MZ_ERR_WORKSPACE_TOO_SMALL.  (ultrazoom_amd/csrc/mz_view_check.h is the one statement of these checks.) */
+ * MZ_ERR_WORKSPACE_TOO_SMALL.  (ultrazoom_amd/csrc/mz_view_check.h is the one statement of these checks.)
+ *
+ * A call within these bounds whose kernel would need more workgroups than one grid holds -- 2^24 - 1 workgroups of 256 threads: a grid
+ * dimension counts its work-items in 32 bits, and a larger grid would be launched cut short, without an error -- is refused with
+ * MZ_ERR_HIP (hipErrorInvalidValue) and writes nothing.  The streaming entries take one work item per run of a row (mz_luma: 16 bytes of
+ * elements; the four YCbCr entries: 16 columns), so this is B * rows * runs < 2^32; mz_noise, one thread an element, splits such a call into
+ * several launches and serves 2^42 elements. */
 typedef struct mz_image_view {
     void*   data;        /* element (image 0, channel 0, row 0, column 0) */
     int64_t stride[4];   /* in ELEMENTS, signed: image, channel, row, column */

@@ -122,22 +122,26 @@ int main() {
         EXPECT(check_workspace((void*)0x10000, SIZE_MAX, SIZE_MAX).code == MZ_OK);
     }
 
-    // the launchers' helpers of mz_view.h.  2^31 - 1 is prime and a plane-tile grid is a multiple of 3: its largest is 2^31 - 2
+    // the launchers' helpers of mz_view.h.  A grid dimension holds 2^32 - 1 work-items, 2^24 - 1 workgroups of 256 threads (kGridRowMax);
+    // 2^24 - 1 = 3^2 5 7 13 17 241 is a multiple of 3, so a plane-tile grid can have exactly that many
     {
-        EXPECT(grid_ok(1) && grid_ok(INT32_MAX) && !grid_ok(0) && !grid_ok(-1) && !grid_ok((long long)INT32_MAX + 1) && !grid_ok(LLONG_MIN));
-        EXPECT(grid_ok(INT32_MAX, 1) && grid_ok(1, INT32_MAX) && grid_ok(715827882, 3) && !grid_ok(715827883, 3) && !grid_ok(65536, 32768));
+        const long long top = 16777215;
+        EXPECT(kImageThreads == 256 && kGridRowMax == top && (top + 1) * kImageThreads == 1LL << 32);
+        EXPECT(grid_ok(1) && grid_ok(top) && !grid_ok(0) && !grid_ok(-1) && !grid_ok(top + 1) && !grid_ok(INT32_MAX) && !grid_ok(LLONG_MIN));
+        EXPECT(grid_ok(top, 1) && grid_ok(1, top) && grid_ok(5592405, 3) && !grid_ok(5592406, 3) && !grid_ok(4096, 4096) && !grid_ok(65536, 32768));
         EXPECT(!grid_ok(LLONG_MAX, LLONG_MAX) && !grid_ok(LLONG_MAX, 2) && !grid_ok(5, 0) && !grid_ok(5, -3));
         TileGrid g;
-        const int h = 151 * 331, w = 2 * 3 * 7 * 11 * 31;  // h w = (2^31 - 2) / 3
-        EXPECT(plane_tile_grid(h, w, 1, 1, 1, &g) && g.tiles_x == w && g.tiles_y == h && g.tiles == 715827882LL && g.wgs == (long long)INT32_MAX - 1);
-        EXPECT(plane_tile_grid(16 * h - 15, 32 * w, 16, 32, 1, &g) && g.tiles_x == w && g.tiles_y == h && g.wgs == (long long)INT32_MAX - 1);
-        EXPECT(plane_tile_grid(151, w, 1, 1, 331, &g) && g.tiles == 151LL * w && g.wgs == (long long)INT32_MAX - 1);
+        const int h = 17 * 241, w = 3 * 5 * 7 * 13;  // h w = (2^24 - 1) / 3
+        EXPECT(plane_tile_grid(h, w, 1, 1, 1, &g) && g.tiles_x == w && g.tiles_y == h && g.tiles == 5592405LL && g.wgs == top);
+        EXPECT(plane_tile_grid(16 * h - 15, 32 * w, 16, 32, 1, &g) && g.tiles_x == w && g.tiles_y == h && g.wgs == top);
+        EXPECT(plane_tile_grid(17, w, 1, 1, 241, &g) && g.tiles == 17LL * w && g.wgs == top);
         EXPECT(!plane_tile_grid(h + 1, w, 1, 1, 1, &g));           // one more row of tiles
         EXPECT(!plane_tile_grid(16 * h + 1, 32 * w, 16, 32, 1, &g));
-        EXPECT(!plane_tile_grid(151, w, 1, 1, 332, &g));           // one more image
+        EXPECT(!plane_tile_grid(17, w, 1, 1, 242, &g));            // one more image
         EXPECT(!plane_tile_grid(side, side, 1, 1, 65535, &g));     // 2^56 tiles: refused before anything is multiplied by 3 B
         EXPECT(!plane_tile_grid(side, side, 1, 1, 1, &g));
-        EXPECT(plane_tile_grid(side, side, 1 << 14, 1 << 14, 2, &g) && g.tiles == 1LL << 28 && g.wgs == 3LL << 29);
+        EXPECT(!plane_tile_grid(side, side, 1 << 14, 1 << 14, 2, &g));  // 3 * 2^29 workgroups: they fit an int, not a grid dimension
+        EXPECT(plane_tile_grid(side, side, 1 << 17, 1 << 17, 1, &g) && g.tiles == 1LL << 22 && g.wgs == 3LL << 22);
         EXPECT(plane_tile_grid(1, 1, 64, 64, 65535, &g) && g.tiles_x == 1 && g.tiles_y == 1 && g.wgs == 3 * 65535);
         EXPECT(plane_tile_grid(33, 129, 32, 128, 1, &g) && g.tiles_x == 2 && g.tiles_y == 2 && g.wgs == 12);  // ragged last tiles
         for (int bad : {INT_MIN, -1, 0}) {

@@ -53,7 +53,7 @@ struct LumaArgs {
     int standard;        // LumaStandard
     int clamp;
 };
-// hipError_t values (kept as int: this header stays free of HIP types); hipErrorInvalidValue for a grid beyond 2^31 - 1 workgroups
+// hipError_t values (kept as int: this header stays free of HIP types); hipErrorInvalidValue for a grid beyond what grid_ok() (mz_view.h) can launch
 int launch_luma(const LumaArgs& a, void* hip_stream);
 
 #ifdef __HIPCC__

@@ -9,6 +9,7 @@
 namespace mz {
 
 constexpr int kLumaThreads = 256;
+static_assert(kLumaThreads == kImageThreads, "grid_ok() (mz_view.h) bounds a grid of workgroups of kImageThreads threads");
 
 // Work item i of B * H * chunks: one run of kVec<E> output elements (16 bytes) along a row, run fastest, then the row, then the image.
 // vec: both views have a column stride of 1 and 16-byte aligned rows (the launcher's finding): three 16-byte loads, one store16; a row's
@@ -54,7 +55,7 @@ int launch_luma(const LumaArgs& a, void* hip_stream) {
         constexpr int E = decltype(e)::value;
         const int chunks = (int)(((long long)a.W + kVec<E> - 1) / kVec<E>);
         const __int128 items = (__int128)a.B * a.H * chunks, blocks = (items + kLumaThreads - 1) / kLumaThreads;
-        if (items < 1 || blocks > 0x7fffffffLL) return hipErrorInvalidValue;
+        if (items < 1 || blocks > kGridRowMax) return hipErrorInvalidValue;
         StridedView o = a.out;
         o.s[1] = 0;  // one channel: its stride names nothing
         const bool vec = a.x.s[3] == 1 && o.s[3] == 1 && rows_aligned(a.x, a.B, a.H, kElemBytes<E>, 16) && rows_aligned(o, a.B, a.H, kElemBytes<E>, 16);

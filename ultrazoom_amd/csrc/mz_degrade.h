@@ -58,6 +58,7 @@ namespace mz {
 constexpr int kBlurMaxHalf = 15;  // sigma < 16 / 3
 constexpr int kBlurTile = 32;     // output pixels a side of one blur_kernel workgroup
 constexpr int kDegradeThreads = 256;
+static_assert(kDegradeThreads == kImageThreads, "grid_ok() (mz_view.h) bounds a grid of workgroups of kImageThreads threads");
 constexpr int kJpegMcus = 2;      // 16 x 16 MCUs of one jpeg_code_kernel workgroup, side by side
 
 struct BlurWeights {
@@ -117,7 +118,7 @@ struct DegradeArgs {
     int elem;  // Elem 0..3
     int B, H, W;
 };
-// Each enqueues one call; hipErrorInvalidValue for a grid beyond 2^31 - 1 workgroups
+// Each enqueues one call; hipErrorInvalidValue for a grid beyond what grid_ok() (mz_view.h) can launch
 hipError_t launch_blur(const DegradeArgs& a, const BlurWeights& bw, hipStream_t s);
 hipError_t launch_noise(const DegradeArgs& a, double sigma, unsigned long long seed, unsigned long long offset, hipStream_t s);
 hipError_t launch_jpeg(const DegradeArgs& a, const JpegTables& t, const JpegPlan& plan, char* ws, hipStream_t s);
@@ -179,11 +180,12 @@ __global__ __launch_bounds__(kDegradeThreads) void blur_kernel(const StridedView
         }
 }
 
-// grid: ceil(3 H W / 256) * B workgroups, chunk fastest.  x and out may be the same view: a thread reads and writes its own element only
+// grid: ceil(3 H W / 256) * B workgroups, chunk fastest; a call of more workgroups than one grid holds (grid_ok(), mz_view.h) is
+// several launches, each of the workgroups from wg0 on.  x and out may be the same view: a thread reads and writes its own element only
 template <int E>
-__global__ __launch_bounds__(kDegradeThreads) void noise_kernel(const StridedView x, const StridedView out, int H, int W, long long chunks, double sigma,
-                                                                  unsigned long long seed, unsigned long long offset) {
-    const long long wg = blockIdx.x;
+__global__ __launch_bounds__(kDegradeThreads) void noise_kernel(const StridedView x, const StridedView out, int H, int W, long long chunks, long long wg0,
+                                                                  double sigma, unsigned long long seed, unsigned long long offset) {
+    const long long wg = wg0 + blockIdx.x;
     const long long b = wg / chunks;
     const long long i = (wg - b * chunks) * kDegradeThreads + threadIdx.x;
     const long long hw = (long long)H * W;

@@ -12,10 +12,18 @@ template <int E> static hipError_t launch_blur_e(const DegradeArgs& a, const Blu
 }
 
 template <int E> static hipError_t launch_noise_e(const DegradeArgs& a, double sigma, unsigned long long seed, unsigned long long offset, hipStream_t s) {
-    const long long chunks = (3LL * a.H * a.W + kDegradeThreads - 1) / kDegradeThreads;
-    if (!grid_ok(chunks, a.B)) return hipErrorInvalidValue;
-    hipLaunchKernelGGL((noise_kernel<E>), dim3((unsigned)(chunks * a.B)), dim3(kDegradeThreads), 0, s, a.x, a.out, a.H, a.W, chunks, sigma, seed, offset);
-    return hipGetLastError();
+    // One workgroup a chunk of 256 elements: from 2^32 elements a call on, more than one grid holds (grid_ok), so the call is up to
+    // kNoiseLaunches launches of at most kGridRowMax workgroups each -- 2^42 elements a call; the usual call is one launch
+    constexpr long long kNoiseLaunches = 1024;
+    const long long chunks = (3LL * a.H * a.W + kDegradeThreads - 1) / kDegradeThreads;  // (H, W <= 2^28: below 2^50)
+    if (a.B < 1 || chunks < 1 || chunks > kNoiseLaunches * kGridRowMax / a.B) return hipErrorInvalidValue;
+    const long long wgs = chunks * a.B;
+    for (long long wg0 = 0; wg0 < wgs; wg0 += kGridRowMax) {
+        const long long n = wgs - wg0 < kGridRowMax ? wgs - wg0 : kGridRowMax;
+        hipLaunchKernelGGL((noise_kernel<E>), dim3((unsigned)n), dim3(kDegradeThreads), 0, s, a.x, a.out, a.H, a.W, chunks, wg0, sigma, seed, offset);
+        if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+    }
+    return hipSuccess;
 }
 
 template <int E> static hipError_t launch_jpeg_e(const DegradeArgs& a, const JpegTables& t, const JpegPlan& pl, char* ws, hipStream_t s) {

@@ -63,6 +63,7 @@ MZ_HD inline void dihedral_source(int k, int H, int W, int i, int j, int* si, in
 constexpr int kDihedralTile = 64;
 constexpr int kDihedralPitch = kDihedralTile + 1;  // odd: a column of the tile walks all 32 banks
 constexpr int kDihedralThreads = 256;
+static_assert(kDihedralThreads == kImageThreads, "grid_ok() (mz_view.h) bounds a grid of workgroups of kImageThreads threads");
 
 enum DihedralMode : int { DM_COPY = 0, DM_ACC = 1 };  // raw elements to a view of the same type; float32 values stored to / added into the accumulator
 
@@ -81,7 +82,7 @@ struct EnsembleFinishArgs {
     int n, clamp;
     int y0, x0, h, w;
 };
-// hipError_t values (kept as int: this header stays free of HIP types); hipErrorInvalidValue for a grid beyond 2^31 - 1 workgroups
+// hipError_t values (kept as int: this header stays free of HIP types); hipErrorInvalidValue for a grid beyond what grid_ok() (mz_view.h) can launch
 int launch_dihedral(const DihedralArgs& a, void* hip_stream);
 int launch_ensemble_finish(const EnsembleFinishArgs& a, void* hip_stream);
 

@@ -54,6 +54,7 @@ namespace mz {
 constexpr int kInterpTileH = 32;  // output pixels of one interp_kernel workgroup
 constexpr int kInterpTileW = 128;
 constexpr int kInterpThreads = 256;
+static_assert(kInterpThreads == kImageThreads, "grid_ok() (mz_view.h) bounds a grid of workgroups of kImageThreads threads");
 constexpr int kInterpStageRows = 20;  // source rows whose horizontal sums a workgroup keeps in LDS: 32 / 2 + 3, and one to spare
 
 enum InterpMode : int { IM_NEAREST = 0, IM_BILINEAR = 1, IM_BICUBIC = 2 };
@@ -121,7 +122,7 @@ struct InterpArgs {
     int mode, clamp;
     int y0, x0, h, w;    // the window of the Hout x Wout result that is computed and stored
 };
-// hipError_t values (kept as int: this header stays free of HIP types); hipErrorInvalidValue for a grid beyond 2^31 - 1 workgroups.
+// hipError_t values (kept as int: this header stays free of HIP types); hipErrorInvalidValue for a grid beyond what grid_ok() (mz_view.h) can launch.
 // MZ_INTERP_GATHER in the environment (read at every call; a debug knob of the tests) sends every tile down the gather path.
 int launch_interp(const InterpArgs& a, void* hip_stream);
 

@@ -38,6 +38,7 @@ namespace mz {
 constexpr int kMetricsTileH = 16;   // output pixels of one moments_kernel workgroup
 constexpr int kMetricsTileW = 32;
 constexpr int kMetricsThreads = 256;
+static_assert(kMetricsThreads == kImageThreads, "grid_ok() (mz_view.h) bounds a grid of workgroups of kImageThreads threads");
 constexpr int kMetricsRun = 4;      // adjacent outputs of one horizontal-pass work item
 constexpr int kMetricsMaxTaps = 17;
 constexpr int kMetricSlots = 16;    // == MZ_METRIC_SLOTS
@@ -121,7 +122,7 @@ struct MetricsArgs {
     char* ws;
     MetricsPlan plan;
 };
-// Enqueues the whole call; hipErrorInvalidValue for a grid beyond 2^31 - 1 workgroups.  launch_metrics: mz_metrics (plan.C = 3,
+// Enqueues the whole call; hipErrorInvalidValue for a grid beyond what grid_ok() (mz_view.h) can launch.  launch_metrics: mz_metrics (plan.C = 3,
 // mz_metrics.hip); launch_metrics_luma: mz_metrics_luma (plan.C = 1; mz_color.hip, which compiles the C = 1 kernels)
 hipError_t launch_metrics(const MetricsArgs& a, hipStream_t s);
 hipError_t launch_metrics_luma(const MetricsArgs& a, hipStream_t s);

@@ -39,6 +39,7 @@ namespace mz {
 constexpr int kResizeTileH = 8;    // output pixels of one resize_kernel workgroup
 constexpr int kResizeTileW = 32;
 constexpr int kResizeThreads = 256;
+static_assert(kResizeThreads == kImageThreads, "grid_ok() (mz_view.h) bounds a grid of workgroups of kImageThreads threads");
 constexpr int kResizeMaxRatio = 16;  // n_in / n_out beyond this is refused: bounds count at 66 and the LDS of a workgroup at 43 KiB
 constexpr int kResizeMaxTaps = 66;
 
@@ -123,7 +124,7 @@ struct ResizeArgs {
     char* ws;
     ResizePlan plan;
 };
-// Enqueues the whole call (the table kernel, then resize_kernel); hipErrorInvalidValue for a grid beyond 2^31 - 1 workgroups
+// Enqueues the whole call (the table kernel, then resize_kernel); hipErrorInvalidValue for a grid beyond what grid_ok() (mz_view.h) can launch
 hipError_t launch_resize(const ResizeArgs& a, hipStream_t s);
 
 #ifdef MZ_RESIZE_KERNELS  // mz_resize.hip only: the host runtime includes the plan above without the device code

@@ -22,14 +22,20 @@ struct StridedView {
 enum Elem : int { EL_F32 = 0, EL_BF16 = 1, EL_F16 = 2, EL_U8 = 3, EL_F64 = 4 };
 
 // ---- the launchers' side --------------------------------------------------------------------------------------------------------
-// a grid of wgs * per workgroups can be launched: 1 .. 2^31 - 1 (no product is formed here: the caller's fits once this says so)
-inline bool grid_ok(long long wgs, long long per = 1) { return wgs > 0 && per > 0 && wgs <= 0x7fffffffLL / per; }
+// A grid dimension holds at most 2^32 - 1 WORK-ITEMS: the dispatch packet counts a dimension's work-items in 32 bits, and HIP launches
+// a larger grid cut to the count modulo 2^32 WITHOUT an error -- the workgroups past it never run (measured: EXPERIMENTS.md, "Large-index
+// tests").  Every image kernel runs workgroups of kImageThreads threads, so one grid dimension holds 2^24 - 1 of them.
+constexpr int kImageThreads = 256;
+constexpr long long kGridRowMax = 0xffffffffLL / kImageThreads;
+// a one-dimensional grid of wgs * per workgroups can be launched: 1 .. 2^24 - 1 (no product is formed here: the caller's fits once this
+// says so)
+inline bool grid_ok(long long wgs, long long per = 1) { return wgs > 0 && per > 0 && wgs <= kGridRowMax / per; }
 
 // THE GRID CONVENTION of the plane-tile kernels (interp, dihedral, resize, blur, moments): tiles * C * B workgroups, tile fastest -- the
 // tile_h x tile_w tiles of an h x w rectangle row by row, then the channel, then the image; plane_tile() below takes an index apart.
 // C is 3 everywhere but in the metrics of a luma plane (mz_metrics_luma: C = 1).
 struct TileGrid { int tiles_x, tiles_y; long long tiles, wgs; };  // tiles = tiles_x * tiles_y; wgs = tiles * C * B
-// false where wgs is not in [1, 2^31 - 1] (nothing is multiplied before it is known to fit: sides of 2^28 in 1 x 1 tiles are refused)
+// false where wgs is not in [1, kGridRowMax] (nothing is multiplied before it is known to fit: sides of 2^28 in 1 x 1 tiles are refused)
 inline bool plane_tile_grid(int h, int w, int tile_h, int tile_w, int B, TileGrid* g, int C = 3) {
     if (h < 1 || w < 1 || tile_h < 1 || tile_w < 1 || B < 1 || C < 1) return false;
     g->tiles_x = (int)(((long long)w + tile_w - 1) / tile_w);

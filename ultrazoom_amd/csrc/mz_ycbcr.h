@@ -96,7 +96,7 @@ struct YcbcrArgs {
     int matrix, range, siting;
     int clamp;              // YCbCr -> RGB only
 };
-// hipError_t values (kept as int: this header stays free of HIP types); hipErrorInvalidValue for a grid beyond 2^31 - 1 workgroups
+// hipError_t values (kept as int: this header stays free of HIP types); hipErrorInvalidValue for a grid beyond what grid_ok() (mz_view.h) can launch
 int launch_ycbcr_to_rgb(const YcbcrArgs& a, void* hip_stream);
 int launch_rgb_to_ycbcr(const YcbcrArgs& a, void* hip_stream);
 

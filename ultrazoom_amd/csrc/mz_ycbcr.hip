@@ -9,6 +9,7 @@
 namespace mz {
 
 constexpr int kYcThreads = 256;
+static_assert(kYcThreads == kImageThreads, "grid_ok() (mz_view.h) bounds a grid of workgroups of kImageThreads threads");
 constexpr int kYcRun = 16;  // luma columns of a work item: 16 (uint8) or 2 x 16 (uint16) bytes of Y
 
 typedef uint32_t yc_u32x2 __attribute__((ext_vector_type(2)));
@@ -402,7 +403,7 @@ static bool yc_launch(const YcbcrArgs& a, int rows, YcLaunch* l) {
     const int bytes = a.depth > 8 ? 2 : 1;
     l->chunks = (int)(((long long)a.W + kYcRun - 1) / kYcRun);
     const __int128 items = (__int128)a.B * rows * l->chunks, blocks = (items + kYcThreads - 1) / kYcThreads;
-    if (items < 1 || blocks > 0x7fffffffLL || !grid_ok((long long)blocks)) return false;
+    if (items < 1 || blocks > kGridRowMax || !grid_ok((long long)blocks)) return false;
     l->items = (long long)items;
     l->blocks = (unsigned)blocks;
     l->y = a.y; l->cb = a.cb; l->cr = a.cr;

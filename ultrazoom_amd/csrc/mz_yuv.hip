@@ -7,6 +7,7 @@
 namespace mz {
 
 constexpr int kYuvThreads = 256;
+static_assert(kYuvThreads == kImageThreads, "grid_ok() (mz_view.h) bounds a grid of workgroups of kImageThreads threads");
 constexpr int kYuvRun = 16;  // luma columns of a work item: one 16-byte run of Y, 8 samples of each chroma plane
 
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
@@ -275,7 +276,7 @@ struct YuvLaunch { int chunks; long long items; unsigned blocks; StridedView y, 
 static bool yuv_launch(const YuvArgs& a, int rows, YuvLaunch* l) {
     l->chunks = (int)(((long long)a.W + kYuvRun - 1) / kYuvRun);
     const __int128 items = (__int128)a.B * rows * l->chunks, blocks = (items + kYuvThreads - 1) / kYuvThreads;
-    if (items < 1 || blocks > 0x7fffffffLL || !grid_ok((long long)blocks)) return false;
+    if (items < 1 || blocks > kGridRowMax || !grid_ok((long long)blocks)) return false;
     l->items = (long long)items;
     l->blocks = (unsigned)blocks;
     l->y = a.y; l->cb = a.cb; l->cr = a.cr;
