@@ -96,13 +96,14 @@ int mz_weights_complete(const mz_handle* h);
  *
  * What a call touches (mz_forward, mz_forward_u8, mz_forward_view, mz_metrics, mz_metrics_luma, mz_luma, mz_yuv420_to_rgb, mz_rgb_to_yuv420,
  * mz_ycbcr_to_rgb, mz_rgb_to_ycbcr, mz_resize, mz_interpolate, mz_blur, mz_noise,
- * mz_jpeg and the mz_op_* entries alike): it READS only its
+ * mz_jpeg, mz_alpha_fill, mz_alpha_merge and the mz_op_* entries alike): it READS only its
  * input tensors -- the elements its shape and strides name, never a byte next to them -- and the workspace bytes it has itself
  * written during that call; it WRITES only its outputs (of a view: the elements of the window) and its workspace, never an input.
  * The workspace needs no initialisation and carries nothing from one call to the next: whatever it holds, NaN patterns included,
  * the results have the same bits.  mz_metrics and mz_metrics_luma write the `out` slots of the metrics `which` selects and leave the
  * others alone.  tests/test_poison_ops_gpu.py, tests/test_poison_forward_gpu.py, tests/test_metrics_gpu.py and
- * tests/test_poison_color_gpu.py, tests/test_poison_yuv_gpu.py, tests/test_poison_ycbcr_gpu.py hold every entry to this.
+ * tests/test_poison_color_gpu.py, tests/test_poison_yuv_gpu.py, tests/test_poison_ycbcr_gpu.py, tests/test_poison_alpha_gpu.py hold every
+ * entry to this.
  *
  * Number range (the convolution, mix, stem and head kernels, in every storage type): subnormals of the storage type are operands and
  * results like any other value -- nothing is flushed on the way in, in the matrix unit's operands, or at the store.  Accumulation is
@@ -142,7 +143,7 @@ int mz_forward_u8(mz_handle* h, const uint8_t* x, uint8_t* out_sr, float* out_qa
  *
  * THE VIEW REFUSALS.  Every entry that takes views (mz_forward_view, mz_metrics, mz_metrics_luma, mz_luma, mz_yuv420_to_rgb, mz_rgb_to_yuv420,
  * mz_ycbcr_to_rgb, mz_rgb_to_ycbcr, mz_resize, mz_interpolate, mz_blur,
- * mz_noise, mz_jpeg, mz_dihedral, mz_ensemble_add, mz_ensemble_finish) returns
+ * mz_noise, mz_jpeg, mz_dihedral, mz_ensemble_add, mz_ensemble_finish, mz_alpha_fill, mz_alpha_merge) returns
  * MZ_ERR_INVALID_ARGUMENT, before anything touches the GPU, for: a null view or null data; an `elem` outside the entry's codes; a view
  * that is WRITTEN whose channel, row or column stride is 0, or whose image stride is 0 when B > 1 (mz_luma's one-channel output: its
  * channel stride is never used and may be anything; strides of a view that is only read
@@ -479,6 +480,41 @@ int mz_ensemble_add(const mz_image_view* y, int elem, int B, int H, int W, int k
                     void* hip_stream);
 int mz_ensemble_finish(const mz_image_view* out, int elem, int B, int H, int W, int n, int clamp, const int32_t window[4],
                        void* workspace, size_t workspace_bytes, void* hip_stream);
+
+/* ---- images with an alpha channel: no reference counterpart (the reference's `decode_image(mode="RGB")` drops alpha).  In a straight-alpha
+ *      image the colour under a == 0 is arbitrary, and the model's receptive field (hundreds of low-resolution pixels) pulls it into every
+ *      visible edge.  mz_alpha_fill extrapolates the visible colour over the WHOLE transparent region by a push-pull pyramid; mz_alpha_merge
+ *      enlarges the alpha plane with the bits of the model's own skip and premultiplies the result if asked
+ *      (ultrazoom_amd/alpha.py: alpha_fill, alpha_merge, upscale_rgba; MewZoom.upscale_rgba) --------------------------------------------
+ * Stateless like mz_resize: every call enqueues on the given stream, never synchronises, allocates nothing and uses no atomics.  All views
+ * of a call have one element type, elem 0..2 = mz_dtype, 3 = uint8.  `alpha` and `out_alpha` are ONE-channel views: their channel stride
+ * names nothing (as for mz_luma's output).  The rgb and alpha of an interleaved RGBA buffer are two views with the same strides and data
+ * pointers three elements apart: nothing is copied on either side.  The touch contract of the workspace paragraph above holds.
+ * ultrazoom_amd/csrc/mz_alpha.h is the one statement of the arithmetic (float64, fixed order, stored components rounded once); in short:
+ *
+ * mz_alpha_fill   a = the alpha element clamped to [0, 1] (NaN: 0); c = the colour (premultiplied != 0: clamp(p / a, 0, 1)).  Texels
+ *                 (w, r, g, b) = (a, a c) -- exactly zero where a == 0, by a select: the colour elements there are never used
+ *                 arithmetically, whatever they hold -- are summed 2 x 2 down to 1 x 1 (a sum with w > 1 is divided by w) and pulled back
+ *                 up: texel' = texel + (1 - w) U, U the bilinear 2x enlargement of the pulled coarser level.  out: pixels with a > 0 keep
+ *                 their elements bit for bit (premultiplied: c rounded once); pixels with a == 0 get rgb' / w' clamped to [0, 1], 0 where
+ *                 the image has no visible pixel.  The workspace holds the levels from 1 up, 16 bytes a texel.
+ * mz_alpha_merge  out_alpha [B,1,Hout,Wout] = the alpha plane [B,1,Hin,Win] interpolated as mz_interpolate does (mode 0..2), clamped to
+ *                 [0, 1] (nearest moves elements): the bits of mz_interpolate(clamp = 1) on that plane.  premultiply != 0: out_rgb = rgb *
+ *                 A, in float64, rounded once, A the out_alpha element AS STORED; out_rgb may be exactly the rgb view (in place), any
+ *                 other overlap of the two is the caller's responsibility.  premultiply == 0: rgb and out_rgb are not looked at (NULL).
+ *
+ * Both refuse the view refusals above (elem outside 0..3; rgb and alpha are only read), and: B < 1 or > 65535; a size < 1 or > 2^28.
+ * mz_alpha_fill: a pyramid beyond 2^62 bytes; out whose byte range overlaps that of rgb or alpha; a null or short workspace
+ * (MZ_ERR_WORKSPACE_TOO_SMALL).  mz_alpha_merge: a mode outside 0..2; alpha whose byte range overlaps that of out_alpha or out_rgb. */
+/* Host only. */
+int mz_alpha_fill_workspace_bytes(int B, int H, int W, size_t* bytes);
+int mz_alpha_fill(const mz_image_view* rgb, const mz_image_view* alpha, const mz_image_view* out, int elem, int B, int H, int W,
+                  int premultiplied, void* workspace, size_t workspace_bytes, void* hip_stream);
+int mz_alpha_merge(const mz_image_view* rgb, const mz_image_view* alpha, const mz_image_view* out_rgb, const mz_image_view* out_alpha,
+                   int elem, int B, int Hin, int Win, int Hout, int Wout, int mode, int premultiply, void* hip_stream);
+/* Host only: the level count of the pyramid of an H x W image (level 0 = H x W down to 1 x 1); the sizes of the first min(count, cap)
+ * levels as hw[2 l] = H_l, hw[2 l + 1] = W_l.  Negative on bad arguments. */
+int mz_debug_alpha_levels(int H, int W, int* hw, int cap);   /* the level count and the sizes of the pyramid */
 
 /* ---- introspection ------------------------------------------------------------------------ */
 const char* mz_last_error(void);

@@ -7,6 +7,7 @@
 All arithmetic runs in hand-written gfx950 kernels behind the C ABI in include/mewzoom_hip.h.
 """
 
+from .alpha import alpha_fill, alpha_merge, upscale_rgba  # noqa: F401
 from .color import rgb_to_y  # noqa: F401
 from .degrade import Degradation, gaussian_blur, gaussian_noise, jpeg  # noqa: F401
 from .ensemble import dihedral, dihedral_inverse, upscale_ensemble  # noqa: F401
@@ -16,4 +17,4 @@ from .video import frame_planes, i420_planes, nv12_planes, rgb_to_ycbcr, rgb_to_
 
 __all__ = ["MewZoom", "bake_state_dict", "Degradation", "gaussian_blur", "gaussian_noise", "jpeg", "dihedral", "dihedral_inverse",
            "upscale_ensemble", "interpolate", "rgb_to_y", "yuv420_to_rgb", "rgb_to_yuv420", "nv12_planes", "i420_planes",
-           "ycbcr_to_rgb", "rgb_to_ycbcr", "frame_planes"]
+           "ycbcr_to_rgb", "rgb_to_ycbcr", "frame_planes", "alpha_fill", "alpha_merge", "upscale_rgba"]

@@ -142,6 +142,12 @@ int mz_ensemble_add(const mz_image_view* y, int elem, int B, int H, int W, int k
     void* hip_stream);
 int mz_ensemble_finish(const mz_image_view* out, int elem, int B, int H, int W, int n, int clamp, const int32_t window[4],
     void* workspace, size_t workspace_bytes, void* hip_stream);
+int mz_alpha_fill_workspace_bytes(int B, int H, int W, size_t* bytes);
+int mz_alpha_fill(const mz_image_view* rgb, const mz_image_view* alpha, const mz_image_view* out, int elem, int B, int H, int W,
+    int premultiplied, void* workspace, size_t workspace_bytes, void* hip_stream);
+int mz_alpha_merge(const mz_image_view* rgb, const mz_image_view* alpha, const mz_image_view* out_rgb, const mz_image_view* out_alpha,
+    int elem, int B, int Hin, int Win, int Hout, int Wout, int mode, int premultiply, void* hip_stream);
+int mz_debug_alpha_levels(int H, int W, int* hw, int cap);
 const char* mz_last_error(void);
 const char* mz_version(void);
 double mz_flops_per_image(const mz_handle* h, int H, int W);
@@ -558,6 +564,31 @@ def ensemble_finish(out_ptr, out_strides, elem, B, H, W, n, clamp, window, ws_pt
     """mz_ensemble_finish: the mean of the n results added, into out (a view of the window, as for `resize`)."""
     _call("mz_ensemble_finish", view(out_ptr, out_strides), int(elem), B, H, W, int(n), bool(clamp), _window_arg(window), ws_ptr, ws_bytes,
           stream)
+
+
+def alpha_fill_workspace_bytes(B: int, H: int, W: int) -> int:
+    return _bytes("mz_alpha_fill_workspace_bytes", B, H, W)
+
+
+def alpha_fill(rgb, alpha, out, elem, B, H, W, premultiplied, ws_ptr, ws_bytes, stream) -> None:
+    """mz_alpha_fill: rgb, alpha and out are (address, strides) pairs of the [B,3,H,W] colour, the [B,1,H,W] alpha plane and the [B,3,H,W]
+    result, all of element type `elem`; the workspace holds `alpha_fill_workspace_bytes(B, H, W)` bytes."""
+    _call("mz_alpha_fill", view(*rgb), view(*alpha), view(*out), int(elem), B, H, W, bool(premultiplied), ws_ptr, ws_bytes, stream)
+
+
+def alpha_merge(rgb, alpha, out_rgb, out_alpha, elem, B, Hin, Win, Hout, Wout, mode, premultiply, stream) -> None:
+    """mz_alpha_merge: alpha [B,1,Hin,Win] and out_alpha [B,1,Hout,Wout] as (address, strides) pairs; rgb and out_rgb ([B,3,Hout,Wout]) are
+    pairs with `premultiply` and may be None without it; `mode` as for `interpolate`; no workspace."""
+    _call("mz_alpha_merge", view(*rgb) if rgb is not None else None, view(*alpha), view(*out_rgb) if out_rgb is not None else None,
+          view(*out_alpha), int(elem), B, Hin, Win, Hout, Wout, int(mode), bool(premultiply), stream)
+
+
+def alpha_levels(H: int, W: int):
+    """mz_debug_alpha_levels (host only): [(H_l, W_l)] of the pyramid of an H x W image, level 0 first, down to (1, 1)."""
+    n = _count(lib().mz_debug_alpha_levels(H, W, None, 0))
+    hw = (c_int * (2 * n))()
+    _count(lib().mz_debug_alpha_levels(H, W, hw, n))
+    return [(int(hw[2 * l]), int(hw[2 * l + 1])) for l in range(n)]
 
 
 class Handle:

@@ -1,8 +1,9 @@
 // Stateless image entry points of libmewzoom_hip.so: image-quality metrics (RGB and luma), the luma plane, YCbCr frames (8-bit 4:2:0; any depth and subsampling), antialiased resizing, plain
-// interpolation, the degradation chain, the dihedral transforms with the self-ensemble accumulator, and the
+// interpolation, the degradation chain, the dihedral transforms with the self-ensemble accumulator, images with alpha, and the
 // host-only mz_debug_* views of what their kernels are handed.  Every check comes before anything touches the GPU.
 #include <cstring>
 
+#include "mz_alpha.h"
 #include "mz_color.h"
 #include "mz_degrade.h"
 #include "mz_dihedral.h"
@@ -588,4 +589,92 @@ extern "C" int mz_ensemble_finish(const mz_image_view* out, int elem, int B, int
     a.acc = (const float*)workspace;
     a.elem = elem; a.B = B; a.H = H; a.W = W; a.n = n; a.clamp = clamp != 0;
     return launched("ensemble finish launch", [&] { return (hipError_t)launch_ensemble_finish(a, hip_stream); });
+}
+
+// ------------------------------------------------------------------------------------------------
+// images with an alpha channel (mz_alpha.h): the push-pull fill of the colour under a == 0, the merge of the enlarged alpha plane.  No
+// reference counterpart: the reference's decode_image(mode="RGB") drops alpha.  Stateless like mz_resize.  Every check comes before
+// anything touches the GPU.
+// ------------------------------------------------------------------------------------------------
+static const ViewRules kAlphaOut = {3, MZ_ELEM_NAMES_0_3, /*second_is_output*/ true, /*batch_bound*/ true, /*side_bound*/ true};
+static const ViewRules kAlphaIn = {3, MZ_ELEM_NAMES_0_3, /*second_is_output*/ false, /*batch_bound*/ true, /*side_bound*/ true};
+
+// two byte ranges of a call, each from its own channel count and shape
+static int alpha_ranges_apart(const mz_image_view* a, int Ca, int Ha, int Wa, const mz_image_view* b, int Cb, int Hb, int Wb, int elem, int B,
+                              const char* what) {
+    long long al, ah, bl, bh;
+    if (!view_extent(a, elem, B, Ha, Wa, &al, &ah, Ca) || !view_extent(b, elem, B, Hb, Wb, &bl, &bh, Cb))
+        return fail(MZ_ERR_INVALID_ARGUMENT, "a view's byte range does not fit in 63 bits");
+    if (al < bh && bl < ah) return fail(MZ_ERR_INVALID_ARGUMENT, "%s overlap: this entry does not work in place", what);
+    return MZ_OK;
+}
+
+static int alpha_fill_plan(int B, int H, int W, AlphaPlan* plan) {
+    if (int rc = check_batch_bounds(B, H, W)) return rc;
+    if (!alpha_plan(B, H, W, plan)) return fail(MZ_ERR_INVALID_ARGUMENT, "the pyramid of %d images of %d x %d is beyond 2^62 bytes", B, H, W);
+    return MZ_OK;
+}
+
+extern "C" int mz_alpha_fill_workspace_bytes(int B, int H, int W, size_t* bytes) {
+    if (!bytes) return fail(MZ_ERR_INVALID_ARGUMENT, "null argument");
+    AlphaPlan plan;
+    if (int rc = alpha_fill_plan(B, H, W, &plan)) return rc;
+    *bytes = plan.total;
+    return MZ_OK;
+}
+
+extern "C" int mz_alpha_fill(const mz_image_view* rgb, const mz_image_view* alpha, const mz_image_view* out, int elem, int B, int H, int W,
+                             int premultiplied, void* workspace, size_t workspace_bytes, void* hip_stream) {
+    if (!rgb || !alpha || !out) return fail(MZ_ERR_INVALID_ARGUMENT, "null image view");
+    mz_image_view al = *alpha;
+    al.stride[1] = 1;  // one channel: its stride is never used, any value is accepted
+    AlphaFillArgs a = {};
+    StridedView unused;
+    if (const Refusal r = check_views(rgb, out, kAlphaOut, elem, B, H, W, &a.rgb, &a.out)) return fail(r);
+    if (const Refusal r = check_views(&al, &al, kAlphaIn, elem, B, H, W, &unused, &a.alpha)) return fail(r);
+    if (int rc = alpha_ranges_apart(rgb, 3, H, W, out, 3, H, W, elem, B, "rgb and out")) return rc;
+    if (int rc = alpha_ranges_apart(&al, 1, H, W, out, 3, H, W, elem, B, "alpha and out")) return rc;
+    if (int rc = alpha_fill_plan(B, H, W, &a.plan)) return rc;
+    if (const Refusal r = check_workspace(workspace, workspace_bytes, a.plan.total)) return fail(r);
+    a.elem = elem; a.B = B; a.H = H; a.W = W;
+    a.premultiplied = premultiplied != 0;
+    a.ws = (char*)workspace;
+    return launched("alpha fill launch", [&] { return (hipError_t)launch_alpha_fill(a, hip_stream); });
+}
+
+extern "C" int mz_alpha_merge(const mz_image_view* rgb, const mz_image_view* alpha, const mz_image_view* out_rgb, const mz_image_view* out_alpha,
+                              int elem, int B, int Hin, int Win, int Hout, int Wout, int mode, int premultiply, void* hip_stream) {
+    static const ViewRules plane = {3, MZ_ELEM_NAMES_0_3, /*second_is_output*/ true, /*batch_bound*/ true, /*side_bound*/ false};
+    if (!alpha || !out_alpha || (premultiply && (!rgb || !out_rgb))) return fail(MZ_ERR_INVALID_ARGUMENT, "null image view");
+    mz_image_view al = *alpha, oa = *out_alpha;
+    al.stride[1] = oa.stride[1] = 1;
+    AlphaMergeArgs a = {};
+    if (const Refusal r = check_views(&al, &oa, plane, elem, B, Hout, Wout, &a.alpha, &a.out_alpha)) return fail(r);
+    if (premultiply)
+        if (const Refusal r = check_views(rgb, out_rgb, plane, elem, B, Hout, Wout, &a.rgb, &a.out_rgb)) return fail(r);
+    if (int rc = check_sizes(Hin, Win, Hout, Wout)) return rc;
+    if (int rc = alpha_ranges_apart(&al, 1, Hin, Win, &oa, 1, Hout, Wout, elem, B, "alpha and out_alpha")) return rc;
+    if (premultiply)
+        if (int rc = alpha_ranges_apart(&al, 1, Hin, Win, out_rgb, 3, Hout, Wout, elem, B, "alpha and out_rgb")) return rc;
+    // (the last check: a call that arrives here with a bad mode has passed every check of its views, which is how tests/test_alpha_cpu.py
+    // shows without a launch that a layout is accepted; mz_alpha_fill's last check is its workspace)
+    if (int rc = check_interp_shape(Hin, Win, Hout, Wout, mode)) return rc;
+    a.elem = elem;
+    a.B = B;
+    a.Hin = Hin; a.Win = Win; a.Hout = Hout; a.Wout = Wout;
+    a.mode = mode;
+    a.premultiply = premultiply != 0;
+    return launched("alpha merge launch", [&] { return (hipError_t)launch_alpha_merge(a, hip_stream); });
+}
+
+// Host only: the levels of the pyramid of an H x W image, level 0 first
+extern "C" int mz_debug_alpha_levels(int H, int W, int* hw, int cap) {
+    if (cap < 0 || (!hw && cap > 0)) return fail(MZ_ERR_INVALID_ARGUMENT, "null argument or negative cap");
+    AlphaPlan plan;
+    if (int rc = alpha_fill_plan(1, H, W, &plan)) return rc;
+    for (int l = 0; l < plan.n && l < cap; ++l) {
+        hw[2 * l] = plan.h[l];
+        hw[2 * l + 1] = plan.w[l];
+    }
+    return plan.n;
 }

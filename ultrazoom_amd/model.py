@@ -452,6 +452,22 @@ class MewZoom(nn.Module, PyTorchModelHubMixin):
         return upscale_ycbcr(self, y, cb, cr, depth=depth, align=align, subsampling=subsampling, matrix=matrix, range=range, siting=siting,
                              out=out)
 
+    @torch.inference_mode()
+    def upscale_rgba(self, x: Tensor, *, premultiplied: bool = False, alpha_mode: str = "bicubic", out: Optional[Tensor] = None,
+                     tile: Optional[Tuple[int, int]] = None) -> Tensor:
+        """``upscale`` on images with an alpha channel: the ``[B, 4, rH, rW]`` RGBA result of ``x``, a logical ``[B, 4, H, W]`` tensor
+        with any strides (the dtype of the parameters, or uint8; a permuted HWC array from an image decoder goes in as it is) --
+        ``ultrazoom_amd.alpha.upscale_rgba(self, ...)``: ``alpha_fill`` extrapolates the visible colour over the fully transparent
+        pixels, whose own colour is arbitrary and would fringe every visible edge; ``upscale_into`` (``upscale_tiled`` with ``tile``)
+        writes straight into ``out[:, :3]``; ``alpha_merge`` enlarges the alpha plane by ``alpha_mode`` with the arithmetic of the
+        model's skip and premultiplies if the input was ``premultiplied``.  An opaque image gives the bits of ``upscale(x[:, :3])``
+        and an alpha of exactly 1.  No host synchronisation beyond ``upscale``'s.  No reference counterpart (the reference's
+        ``decode_image(mode="RGB")`` drops alpha).  Out of scope: grey (+ alpha) images, alpha through the model, the self-ensemble,
+        metrics with alpha."""
+        from .alpha import upscale_rgba
+
+        return upscale_rgba(self, x, premultiplied=premultiplied, alpha_mode=alpha_mode, out=out, tile=tile)
+
     # ---- checkpoint ingestion (test_compare.py:32-45 of the reference) -------------------------
     def load_training_checkpoint(self, state_dict: Dict[str, Tensor], lora_alpha: Optional[float] = None) -> None:
         """Loads a raw training checkpoint: strips ``_orig_mod.`` prefixes left by torch.compile, bakes weight-norm
