@@ -96,14 +96,14 @@ int mz_weights_complete(const mz_handle* h);
  *
  * What a call touches (mz_forward, mz_forward_u8, mz_forward_view, mz_metrics, mz_metrics_luma, mz_luma, mz_yuv420_to_rgb, mz_rgb_to_yuv420,
  * mz_ycbcr_to_rgb, mz_rgb_to_ycbcr, mz_resize, mz_interpolate, mz_blur, mz_noise,
- * mz_jpeg, mz_alpha_fill, mz_alpha_merge and the mz_op_* entries alike): it READS only its
+ * mz_jpeg, mz_alpha_fill, mz_alpha_merge, mz_feather_paste and the mz_op_* entries alike): it READS only its
  * input tensors -- the elements its shape and strides name, never a byte next to them -- and the workspace bytes it has itself
  * written during that call; it WRITES only its outputs (of a view: the elements of the window) and its workspace, never an input.
  * The workspace needs no initialisation and carries nothing from one call to the next: whatever it holds, NaN patterns included,
  * the results have the same bits.  mz_metrics and mz_metrics_luma write the `out` slots of the metrics `which` selects and leave the
  * others alone.  tests/test_poison_ops_gpu.py, tests/test_poison_forward_gpu.py, tests/test_metrics_gpu.py and
- * tests/test_poison_color_gpu.py, tests/test_poison_yuv_gpu.py, tests/test_poison_ycbcr_gpu.py, tests/test_poison_alpha_gpu.py hold every
- * entry to this.
+ * tests/test_poison_color_gpu.py, tests/test_poison_yuv_gpu.py, tests/test_poison_ycbcr_gpu.py, tests/test_poison_alpha_gpu.py,
+ * tests/test_poison_feather_gpu.py hold every entry to this.
  *
  * Number range (the convolution, mix, stem and head kernels, in every storage type): subnormals of the storage type are operands and
  * results like any other value -- nothing is flushed on the way in, in the matrix unit's operands, or at the store.  Accumulation is
@@ -143,7 +143,7 @@ int mz_forward_u8(mz_handle* h, const uint8_t* x, uint8_t* out_sr, float* out_qa
  *
  * THE VIEW REFUSALS.  Every entry that takes views (mz_forward_view, mz_metrics, mz_metrics_luma, mz_luma, mz_yuv420_to_rgb, mz_rgb_to_yuv420,
  * mz_ycbcr_to_rgb, mz_rgb_to_ycbcr, mz_resize, mz_interpolate, mz_blur,
- * mz_noise, mz_jpeg, mz_dihedral, mz_ensemble_add, mz_ensemble_finish, mz_alpha_fill, mz_alpha_merge) returns
+ * mz_noise, mz_jpeg, mz_dihedral, mz_ensemble_add, mz_ensemble_finish, mz_alpha_fill, mz_alpha_merge, mz_feather_paste) returns
  * MZ_ERR_INVALID_ARGUMENT, before anything touches the GPU, for: a null view or null data; an `elem` outside the entry's codes; a view
  * that is WRITTEN whose channel, row or column stride is 0, or whose image stride is 0 when B > 1 (mz_luma's one-channel output: its
  * channel stride is never used and may be anything; strides of a view that is only read
@@ -515,6 +515,28 @@ int mz_alpha_merge(const mz_image_view* rgb, const mz_image_view* alpha, const m
 /* Host only: the level count of the pyramid of an H x W image (level 0 = H x W down to 1 x 1); the sizes of the first min(count, cap)
  * levels as hw[2 l] = H_l, hw[2 l + 1] = W_l.  Negative on bad arguments. */
 int mz_debug_alpha_levels(int H, int W, int* hw, int cap);   /* the level count and the sizes of the pyramid */
+
+/* ---- feathered tiling: no reference counterpart (the reference has no tiling code).  Tiles cut with a SMALL halo do not agree where
+ *      they meet; each tile keeps a band beyond every interior cut and the later tile is pasted onto the earlier one with a linear
+ *      cross-fade over the band (ultrazoom_amd/tiling.py: plan_feathered, upscale_feathered, feather_paste; MewZoom.upscale_feathered) ---
+ * Stateless like mz_resize: the call enqueues on the given stream, never synchronises, allocates nothing, needs no workspace and uses no
+ * atomics.  src and dst are views of [B,3,H,W] of one element type, elem 0..2 = mz_dtype, 3 = uint8.  All element offsets are 64-bit.
+ * The touch contract of the workspace paragraph above holds: src is only read, and of dst only the elements under a ramp are read.
+ * ultrazoom_amd/csrc/mz_feather.h is the one statement of the arithmetic; in short:
+ *
+ * mz_feather_paste  A ramp of n positions has the weights omega(n, k) = (2 k + 1) * rho(n) for k < n, rho(n) = 1.0 / (2 n) formed on
+ *                   the host, and omega = 1 for k >= n or n == 0: the midpoints of n equal steps, below 1 for every k < n.  Element
+ *                   (y, x) has w = omega(ramp_y, y) * omega(ramp_x, x).  Where w == 1, or src and dst hold the same bit pattern, dst
+ *                   receives the BITS of src (a select: a NaN, a -0 or uninitialised bytes of dst under w == 1 change nothing).
+ *                   Elsewhere v = d + w * (s - d) in float64, contraction off, rounded once to the element type, no clamp; uint8: s and
+ *                   d are the codes 0..255, the stored code is (int)(v + 0.5).  A ramp longer than the rectangle is cut by its border.
+ *
+ * Refuses the view refusals above (elem outside 0..3; dst is written), and: B < 1 or > 65535; H or W < 1 or > 2^28; src and dst whose
+ * byte ranges overlap (the same view twice included) or do not fit in signed 64-bit addresses; a ramp outside 0 .. 2^20. */
+int mz_feather_paste(const mz_image_view* src, const mz_image_view* dst, int elem, int B, int H, int W, int ramp_y, int ramp_x,
+                     void* hip_stream);
+/* Host only: omega(n, k) for 0 <= n <= 2^20 and k >= 0. */
+int mz_debug_feather_weight(int n, int k, double* w);
 
 /* ---- introspection ------------------------------------------------------------------------ */
 const char* mz_last_error(void);

@@ -148,6 +148,9 @@ int mz_alpha_fill(const mz_image_view* rgb, const mz_image_view* alpha, const mz
 int mz_alpha_merge(const mz_image_view* rgb, const mz_image_view* alpha, const mz_image_view* out_rgb, const mz_image_view* out_alpha,
     int elem, int B, int Hin, int Win, int Hout, int Wout, int mode, int premultiply, void* hip_stream);
 int mz_debug_alpha_levels(int H, int W, int* hw, int cap);
+int mz_feather_paste(const mz_image_view* src, const mz_image_view* dst, int elem, int B, int H, int W, int ramp_y, int ramp_x,
+    void* hip_stream);
+int mz_debug_feather_weight(int n, int k, double* w);
 const char* mz_last_error(void);
 const char* mz_version(void);
 double mz_flops_per_image(const mz_handle* h, int H, int W);
@@ -589,6 +592,19 @@ def alpha_levels(H: int, W: int):
     hw = (c_int * (2 * n))()
     _count(lib().mz_debug_alpha_levels(H, W, hw, n))
     return [(int(hw[2 * l]), int(hw[2 * l + 1])) for l in range(n)]
+
+
+def feather_paste(src, dst, elem, B, H, W, ramp_y, ramp_x, stream) -> None:
+    """mz_feather_paste: src and dst are (address, strides) pairs of two [B,3,H,W] views of element type `elem`; the ramps count
+    positions from the top and the left edge; no workspace."""
+    _call("mz_feather_paste", view(*src), view(*dst), int(elem), B, H, W, int(ramp_y), int(ramp_x), stream)
+
+
+def feather_weight(n: int, k: int) -> float:
+    """mz_debug_feather_weight (host only): omega(n, k), from the functions the kernel compiles."""
+    w = c_double()
+    _call("mz_debug_feather_weight", int(n), int(k), byref(w))
+    return float(w.value)
 
 
 class Handle:

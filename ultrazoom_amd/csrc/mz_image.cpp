@@ -1,5 +1,5 @@
 // Stateless image entry points of libmewzoom_hip.so: image-quality metrics (RGB and luma), the luma plane, YCbCr frames (8-bit 4:2:0; any depth and subsampling), antialiased resizing, plain
-// interpolation, the degradation chain, the dihedral transforms with the self-ensemble accumulator, images with alpha, and the
+// interpolation, the degradation chain, the dihedral transforms with the self-ensemble accumulator, images with alpha, the paste of feathered tiling, and the
 // host-only mz_debug_* views of what their kernels are handed.  Every check comes before anything touches the GPU.
 #include <cstring>
 
@@ -8,6 +8,7 @@
 #include "mz_degrade.h"
 #include "mz_dihedral.h"
 #include "mz_err.h"
+#include "mz_feather.h"
 #include "mz_interp.h"
 #include "mz_metrics.h"
 #include "mz_resize.h"
@@ -677,4 +678,34 @@ extern "C" int mz_debug_alpha_levels(int H, int W, int* hw, int cap) {
         hw[2 * l + 1] = plan.w[l];
     }
     return plan.n;
+}
+
+// ------------------------------------------------------------------------------------------------
+// feathered tiling (mz_feather.h): one rectangle pasted onto another with a linear cross-fade along its top and left edges.  No
+// reference counterpart (the reference has no tiling code).  Stateless like mz_resize.  Every check comes before anything touches the GPU.
+// ------------------------------------------------------------------------------------------------
+static const ViewRules kFeatherOut = {3, MZ_ELEM_NAMES_0_3, /*second_is_output*/ true, /*batch_bound*/ true, /*side_bound*/ true};
+
+static int check_ramp(const char* name, int n) {
+    return feather_ramp_ok(n) ? MZ_OK : fail(MZ_ERR_INVALID_ARGUMENT, "%s must be 0 .. 2^20 positions, got %d", name, n);
+}
+
+extern "C" int mz_feather_paste(const mz_image_view* src, const mz_image_view* dst, int elem, int B, int H, int W, int ramp_y, int ramp_x,
+                                void* hip_stream) {
+    FeatherArgs a = {};
+    if (const Refusal r = check_views(src, dst, kFeatherOut, elem, B, H, W, &a.src, &a.dst)) return fail(r);
+    if (const Refusal r = check_overlap(src, dst, elem, B, H, W, /*in_place_ok*/ false)) return fail(r);
+    if (int rc = check_ramp("ramp_y", ramp_y)) return rc;
+    if (int rc = check_ramp("ramp_x", ramp_x)) return rc;
+    a.elem = elem; a.B = B; a.H = H; a.W = W; a.ramp_y = ramp_y; a.ramp_x = ramp_x;
+    return launched("feather paste launch", [&] { return (hipError_t)launch_feather_paste(a, hip_stream); });
+}
+
+// Host only: omega(n, k), from the functions the kernel compiles
+extern "C" int mz_debug_feather_weight(int n, int k, double* w) {
+    if (!w) return fail(MZ_ERR_INVALID_ARGUMENT, "null argument");
+    if (int rc = check_ramp("n", n)) return rc;
+    if (k < 0) return fail(MZ_ERR_INVALID_ARGUMENT, "k must be at least 0, got %d", k);
+    *w = feather_omega(n, feather_rho(n), k);
+    return MZ_OK;
 }

@@ -414,6 +414,18 @@ class MewZoom(nn.Module, PyTorchModelHubMixin):
         return upscale_ensemble(self, x, n=n, out=out, tile=tile)
 
     @torch.inference_mode()
+    def upscale_feathered(self, x: Tensor, tile: Tuple[int, int] = (512, 512), halo: int = 32, overlap: Optional[int] = None,
+                          out: Optional[Tensor] = None) -> Tensor:
+        """``upscale`` (``upscale_uint8`` for uint8 tensors) of an image too large for one pass, tile by tile with a SMALL halo: every
+        tile keeps ``overlap`` (default ``halo // 2``) low-resolution pixels beyond each interior cut, and the seams are cross-faded
+        over those bands by a HIP kernel -- ``ultrazoom_amd.tiling.upscale_feathered(self, x, tile, halo, overlap, out)``, which states
+        the order of operations.  An approximation of ``upscale(x)`` at a fraction of the arithmetic of exact tiling
+        (``tiling.tile_work``); ``tiling.upscale_tiled`` is the exact mode.  No reference counterpart."""
+        from .tiling import upscale_feathered
+
+        return upscale_feathered(self, x, tile=tile, halo=halo, overlap=overlap, out=out)
+
+    @torch.inference_mode()
     def upscale_and_bicubic(self, x: Tensor) -> Tuple[Tensor, Tensor]:
         """``(sr, bicubic)``: ``upscale(x)`` (``upscale_uint8(x)`` for uint8 tensors) together with the plain bicubic enlargement of ``x``
         by the model's ratio, clamped to [0, 1] -- ``ultrazoom_amd.interpolate(x, scale_factor=r, mode="bicubic", clamp=True)``, the
